@@ -104,3 +104,23 @@ def test_counted_vmcnt_kernels_do_not_spill(tmp_path):
             sp = re.search(r"\.vgpr_spill_count:\s*(\d+)", tail)
             assert sp and int(sp.group(1)) == 0, (m.group(1), tail[:300])
     assert seen >= 3, seen
+
+
+# Environment switches the library may read: the ones the GPU tests set to pin a kernel against its reference kernel, and the
+# side-stream count of the DiT step.  A name outside this list is a tuning or timing-only switch left in a launch path.
+KEPT_SWITCHES = {
+    "UWU_GEMM_AS", "UWU_GEMM_AS_BIAS", "UWU_GEMM_M64", "UWU_GEMM_WIDE", "UWU_GEMM_BIG", "UWU_GEMM_TR", "UWU_GEMM_TRW",
+    "UWU_GEMM_R3", "UWU_GEMM_P8", "UWU_GEMM_P8N", "UWU_GEMM_P8F", "UWU_GEMM_P8F_PART", "UWU_F8_EMIT", "UWU_LN_ROW16",
+    "UWU_ATTN_P256", "UWU_ATTN_P256F", "UWU_ATTN_P256_D72", "UWU_ATTN_P256F_D72", "UWU_DIT_SIDE_STREAMS",
+}
+
+
+def test_library_reads_only_the_kept_switches():
+    """Every UWU_* string in libuwu_hip.so that include/uwu_hip.h does not declare is one of KEPT_SWITCHES (no GPU needed)."""
+    from uwudiff_amd import build
+
+    if not os.path.exists(build.LIB):
+        build.build()
+    found = {m.decode() for m in re.findall(rb"UWU_[A-Z0-9_]+", open(build.LIB, "rb").read())}
+    declared = set(re.findall(r"\bUWU_[A-Z0-9_]+\b", open(os.path.join(ROOT, "include", "uwu_hip.h")).read()))
+    assert found - declared == KEPT_SWITCHES

@@ -1,5 +1,5 @@
 """LayerNorm backward with one weight / bias vector (UNet transformer blocks), us per launch.
-Usage: [UWU_LN_AFFINE=0] python tools/probe_ln_affine.py"""
+Usage: python tools/probe_ln_affine.py"""
 import os
 import sys
 

@@ -1,5 +1,5 @@
 """DiT-S/2 weight gradients at small per-GPU batches (K = 256 x batch tokens), us per launch (slices + reduce).
-Usage: [UWU_TR_SPLIT=n] python tools/probe_wgrad_dit_small.py [batch ...]"""
+Usage: python tools/probe_wgrad_dit_small.py [batch ...]"""
 import os
 import sys
 

@@ -1,5 +1,5 @@
 """Weight-gradient launches of the SDXL-shape UNet's Linears at 4x128x128 latents (K = tokens), us per launch.
-Usage: [UWU_TR_SPLIT=n] python tools/probe_wgrad_unet.py [batch]      (default batch 12: the bench's)"""
+Usage: python tools/probe_wgrad_unet.py [batch]      (default batch 12: the bench's)"""
 import os
 import sys
 

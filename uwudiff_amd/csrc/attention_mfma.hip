@@ -549,32 +549,30 @@ __global__ void __launch_bounds__(512, 2) attn_bwd_mfma(const MArgs a) {
     // One-kernel variant (T <= 256): the accumulators hold 4 consecutive d of one key per lane -- stored directly that is 16
     // contiguous bytes per row and instruction, eight partial writes per 128-byte dK / dV row.  Every wave passes its
     // [32 keys][64 d] tiles through its own 8 KB of the (now idle) LDS and stores whole rows: 8 lanes x 16 B per key.
-    if (ROPE || a.ldt != -99) {  // (non-RoPE launches: ldt = -99 switches back to the direct stores, UWU_ATTN_ROWSTORE=0)
-      char* mine = smem + wave * 8192;  // [2 tensors][32 keys][128 B]
-      if (active) {
+    char* mine = smem + wave * 8192;  // [2 tensors][32 keys][128 B]
+    if (active) {
 #pragma unroll
-        for (int dt = 0; dt < NDT; ++dt)
+      for (int dt = 0; dt < NDT; ++dt)
 #pragma unroll
-          for (int g4 = 0; g4 < 4; ++g4) {
-            const int d0 = 32 * dt + 8 * g4 + 4 * h;
-            store4(reinterpret_cast<bf16_t*>(mine + r * 128) + d0,
-                   f32x4{dkT[dt][4 * g4] * a.scale, dkT[dt][4 * g4 + 1] * a.scale, dkT[dt][4 * g4 + 2] * a.scale,
-                         dkT[dt][4 * g4 + 3] * a.scale});
-            store4(reinterpret_cast<bf16_t*>(mine + 4096 + r * 128) + d0,
-                   f32x4{dvT[dt][4 * g4], dvT[dt][4 * g4 + 1], dvT[dt][4 * g4 + 2], dvT[dt][4 * g4 + 3]});
-          }
-        // (same wave wrote and reads: no barrier; the compiler orders the LDS accesses)
-#pragma unroll
-        for (int p = 0; p < 4; ++p) {
-          const int key = 8 * p + (lane >> 3), ch = lane & 7;
-          const uint4 kx = *reinterpret_cast<const uint4*>(mine + key * 128 + ch * 16);
-          const uint4 vx = *reinterpret_cast<const uint4*>(mine + 4096 + key * 128 + ch * 16);
-          *reinterpret_cast<uint4*>(a.dk + (int64_t)b * a.Tk * a.ldk + hd * DH + (int64_t)(k0 + key) * a.ldk + 8 * ch) = kx;
-          *reinterpret_cast<uint4*>(a.dv + (int64_t)b * a.Tk * a.ldv + hd * DH + (int64_t)(k0 + key) * a.ldv + 8 * ch) = vx;
+        for (int g4 = 0; g4 < 4; ++g4) {
+          const int d0 = 32 * dt + 8 * g4 + 4 * h;
+          store4(reinterpret_cast<bf16_t*>(mine + r * 128) + d0,
+                 f32x4{dkT[dt][4 * g4] * a.scale, dkT[dt][4 * g4 + 1] * a.scale, dkT[dt][4 * g4 + 2] * a.scale,
+                       dkT[dt][4 * g4 + 3] * a.scale});
+          store4(reinterpret_cast<bf16_t*>(mine + 4096 + r * 128) + d0,
+                 f32x4{dvT[dt][4 * g4], dvT[dt][4 * g4 + 1], dvT[dt][4 * g4 + 2], dvT[dt][4 * g4 + 3]});
         }
+      // (same wave wrote and reads: no barrier; the compiler orders the LDS accesses)
+#pragma unroll
+      for (int p = 0; p < 4; ++p) {
+        const int key = 8 * p + (lane >> 3), ch = lane & 7;
+        const uint4 kx = *reinterpret_cast<const uint4*>(mine + key * 128 + ch * 16);
+        const uint4 vx = *reinterpret_cast<const uint4*>(mine + 4096 + key * 128 + ch * 16);
+        *reinterpret_cast<uint4*>(a.dk + (int64_t)b * a.Tk * a.ldk + hd * DH + (int64_t)(k0 + key) * a.ldk + 8 * ch) = kx;
+        *reinterpret_cast<uint4*>(a.dv + (int64_t)b * a.Tk * a.ldv + hd * DH + (int64_t)(k0 + key) * a.ldv + 8 * ch) = vx;
       }
-      return;
     }
+    return;
   }
   if (active && kvalid) {
     bf16_t* dkb = a.dk + (int64_t)b * a.Tk * a.ldk + hd * DH + (int64_t)(k0 + r) * a.ldk;
@@ -773,57 +771,59 @@ bool uwu_attn_mfma_bwd_ok(int Tq, int Tk, int d, int ldq, int ldk, int ldv, int 
 
 namespace {
 
+// the LDS attribute of `kernel` on the current device (`done`: its UWU_MAX_DEV flags); false, with the error set, when the
+// device cannot give a workgroup that much
 template <typename K>
-void allow_lds(K kernel, int bytes) {
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+bool allow_lds(K kernel, int bytes, unsigned char* done, const char* what) {
+  if (uwu_func_lds(reinterpret_cast<const void*>(kernel), bytes, done)) return true;
+  uwu_set_error("%s: the device cannot give a workgroup %d bytes of LDS", what, bytes);
+  return false;
 }
 
 template <int DH>
-void launch_fwd(const MArgs& a, hipStream_t st) {
+int launch_fwd(const MArgs& a, hipStream_t st) {
   constexpr int NB = HeadGeom<DH>::NB;
   constexpr int lds = NB == 1 ? 0 : 2 * 2 * NB * 8192;  // wider heads: the two stages live in dynamic LDS
-  static bool once = false;
-  if (!once && lds) {
-    allow_lds(attn_fwd_mfma<true, DH>, lds);
-    allow_lds(attn_fwd_mfma<false, DH>, lds);
-  }
-  once = true;
+  static unsigned char done[2][UWU_MAX_DEV];
+  if (lds && !(allow_lds(attn_fwd_mfma<true, DH>, lds, done[0], "attention_fwd(mfma)") &&
+               allow_lds(attn_fwd_mfma<false, DH>, lds, done[1], "attention_fwd(mfma)")))
+    return UWU_ELAUNCH;
   const dim3 grid(((a.T + 127) / 128) * a.B * a.H);
   if (a.kbias) hipLaunchKernelGGL((attn_fwd_mfma<true, DH>), grid, dim3(256), lds, st, a);
   else hipLaunchKernelGGL((attn_fwd_mfma<false, DH>), grid, dim3(256), lds, st, a);
+  return UWU_OK;
 }
 
 template <int DH>
-void launch_bwd(const MArgs& a, hipStream_t st) {
+int launch_bwd(const MArgs& a, hipStream_t st) {
   constexpr int NB = HeadGeom<DH>::NB;
   constexpr int lds_kv = bwd_lds_kv(NB);                  // key-block variant: the two staging stages + lse / delta
   constexpr int lds_dq = NB == 1 ? 0 : 2 * 3 * NB * 8192;
-  static bool once = false;
-  if (!once) {
-    if constexpr (DH == 64) allow_lds(attn_bwd_mfma<true, false, 64>, BWD_LDS);
-    allow_lds(attn_bwd_mfma<false, false, DH>, lds_kv);
-    allow_lds(attn_bwd_mfma<false, true, DH>, lds_kv);
-    if (lds_dq) {
-      allow_lds(attn_bwd_dq_mfma<true, DH>, lds_dq);
-      allow_lds(attn_bwd_dq_mfma<false, DH>, lds_dq);
-    }
-  }
-  once = true;
+  static unsigned char done[5][UWU_MAX_DEV];
+  constexpr const char* what = "attention_bwd(mfma)";
+  if (DH == 64 && !allow_lds(attn_bwd_mfma<true, false, 64>, BWD_LDS, done[0], what)) return UWU_ELAUNCH;
+  if (!allow_lds(attn_bwd_mfma<false, false, DH>, lds_kv, done[1], what) ||
+      !allow_lds(attn_bwd_mfma<false, true, DH>, lds_kv, done[2], what))
+    return UWU_ELAUNCH;
+  if (lds_dq && !(allow_lds(attn_bwd_dq_mfma<true, DH>, lds_dq, done[3], what) &&
+                  allow_lds(attn_bwd_dq_mfma<false, DH>, lds_dq, done[4], what)))
+    return UWU_ELAUNCH;
   const dim3 gkv(a.B * a.H * ((a.Tk + 255) / 256)), gq(a.B * a.H * ((a.T + 127) / 128));
   if (a.kbias) {  // biased scores: always the two-kernel form
     hipLaunchKernelGGL((attn_bwd_mfma<false, true, DH>), gkv, dim3(512), lds_kv, st, a);
     hipLaunchKernelGGL((attn_bwd_dq_mfma<true, DH>), gq, dim3(256), lds_dq, st, a);
-    return;
+    return UWU_OK;
   }
   if constexpr (DH == 64) {
     if (a.T == a.Tk && a.T <= 256) {
       hipLaunchKernelGGL((attn_bwd_mfma<true, false, 64>), dim3(a.B * a.H), dim3(512), BWD_LDS, st, a);
-      return;
+      return UWU_OK;
     }
   }
   // dK / dV per block of 256 keys, dQ per tile of 128 queries
   hipLaunchKernelGGL((attn_bwd_mfma<false, false, DH>), gkv, dim3(512), lds_kv, st, a);
   hipLaunchKernelGGL((attn_bwd_dq_mfma<false, DH>), gq, dim3(256), lds_dq, st, a);
+  return UWU_OK;
 }
 
 }  // namespace
@@ -867,9 +867,8 @@ extern "C" int uwu_attention_rope_bwd(const void* q, const void* k, const void* 
   a.dq = (bf16_t*)dq; a.dk = (bf16_t*)dk; a.dv = (bf16_t*)dv;
   a.B = B; a.T = T; a.Tk = T; a.H = H; a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo; a.scale = scale;
   a.rope = rope_tab; a.ldt = ldt;
-  static bool once = false;
-  if (!once) allow_lds(attn_bwd_mfma<true, false, 64, true>, BWD_LDS);
-  once = true;
+  static unsigned char done[UWU_MAX_DEV];
+  if (!allow_lds(attn_bwd_mfma<true, false, 64, true>, BWD_LDS, done, "attention_rope_bwd")) return UWU_ELAUNCH;
   UwuProfScope prof(stream);
   hipLaunchKernelGGL((attn_bwd_mfma<true, false, 64, true>), dim3(B * H), dim3(512), BWD_LDS, (hipStream_t)stream, a);
   prof.done(UWU_PROF_ATTN_BWD, 0, 10.0 * B * H * T * T * d, 2.0 * B * H * d * 8.0 * T);
@@ -891,9 +890,8 @@ int uwu_attn_mfma_fwd(const void* q, const void* k, const void* v, void* o, floa
   a.q = (const bf16_t*)q; a.k = (const bf16_t*)k; a.v = (const bf16_t*)v; a.out = (bf16_t*)o; a.lse = lse;
   a.kbias = kbias;
   a.B = B; a.T = T; a.Tk = Tk; a.H = H; a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo; a.scale = scale;
-  if (d == 64) launch_fwd<64>(a, st);
-  else if (d == 72) launch_fwd<72>(a, st);
-  else launch_fwd<128>(a, st);
+  const int rc = d == 64 ? launch_fwd<64>(a, st) : d == 72 ? launch_fwd<72>(a, st) : launch_fwd<128>(a, st);
+  if (rc != UWU_OK) return rc;
   UWU_LAUNCH_CHECK("attention_fwd(mfma)");
   return UWU_OK;
 }
@@ -918,13 +916,8 @@ int uwu_attn_mfma_bwd(const void* q, const void* k, const void* v, const void* o
   a.dq = (bf16_t*)dq; a.dk = (bf16_t*)dk; a.dv = (bf16_t*)dv;
   a.kbias = kbias;
   a.B = B; a.T = T; a.Tk = Tk; a.H = H; a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo; a.scale = scale;
-  {
-    static UwuEnv rs("UWU_ATTN_ROWSTORE");  // UWU_ATTN_ROWSTORE=0: direct 8-byte dK / dV stores (A/B comparisons)
-    a.ldt = rs.get().is('0') ? -99 : 0;
-  }
-  if (d == 64) launch_bwd<64>(a, st);
-  else if (d == 72) launch_bwd<72>(a, st);
-  else launch_bwd<128>(a, st);
+  const int rc = d == 64 ? launch_bwd<64>(a, st) : d == 72 ? launch_bwd<72>(a, st) : launch_bwd<128>(a, st);
+  if (rc != UWU_OK) return rc;
   UWU_LAUNCH_CHECK("attention_bwd(mfma)");
   return UWU_OK;
 }

@@ -53,7 +53,6 @@ struct PArgs {
   const float* lse;
   int B, H, ldq, ldk, ldv, ldo, nheads;
   float scale;
-  int prio;  // UWU_P256_PRIO (A/B): 1 = waves 4-7 run at s_setprio 1, 2 = waves 0-3
 };
 
 // 16-byte chunk swizzle of the 128-byte-row images (Q / dO tiles, K image): bit0 = r2 ^ r4, bit1 = r3 ^ r4, bit2 = r1
@@ -133,20 +132,17 @@ __device__ __forceinline__ uint4 tr_pair(unsigned a0, unsigned a1) {
   return r;
 }
 
-// ABL (tools only, UWU_P256_ABL): timing-only builds with wrong results -- 1: no dQ product, 2: no global stores, 4: no phase 1
-// (dS^T image left stale)
 // DH = 72 (DiT-XL/2's 16 heads of 1152): columns 64..71 of every operand travel as TAILS -- compact images with 16-byte rows next
 // to the 128-byte-row images of columns 0..63.  As a contraction index (S = Q.K^T, dP = dO.V^T) the tail is a fifth k step whose
 // upper half is zero in the K / V fragment registers; as an output index (dV^T, dK^T, dQ^T rows 64..71) it is a third / fifth row
 // tile whose rows past 71 hold garbage nobody stores (an MFMA row only ever sees its own row of A).
-template <int ABL, int DH = 64>
+template <int DH>
 __global__ void __launch_bounds__(512, 2) attn_bwd_p256(const PArgs a) {
   using G = PGeom<DH>;
   constexpr bool TAIL = G::TAIL;
   constexpr int T = 256, NKS = TAIL ? 5 : 4, NDT = TAIL ? 3 : 2;
   constexpr int P_SLOT = G::SLOT, P_OFF_DS = G::OFF_DS, P_OFF_K = G::OFF_K, P_OFF_LSE = G::OFF_LSE, P_OFF_DELTA = G::OFF_DELTA;
   constexpr int KIMG = G::KIMG;
-  static_assert(!TAIL || ABL == 0, "the timing-only ablations exist for head dim 64");
   char* const smem = p_smem;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -324,8 +320,7 @@ __global__ void __launch_bounds__(512, 2) attn_bwd_p256(const PArgs a) {
       for (int p = 0; p < 4; ++p) {  // (same wave wrote and reads: no barrier; the compiler orders the LDS accesses)
         const int key = 8 * p + (lane >> 3), ch = lane & 7;
         const uint4 x = *reinterpret_cast<const uint4*>(mine + key * 128 + ((ch ^ (key & 7)) << 4));
-        if constexpr (!(ABL & 2)) *reinterpret_cast<uint4*>(dst + (int64_t)(k0 + key) * ld + 8 * ch) = x;
-        else asm volatile("" ::"v"(x.x), "v"(x.y), "v"(x.z), "v"(x.w));
+        *reinterpret_cast<uint4*>(dst + (int64_t)(k0 + key) * ld + 8 * ch) = x;
       }
       if constexpr (TAIL) {  // rows 64 + 4 h + i of the third tile are registers 0..3; the rest of it is garbage
         const f32x4 x = which ? dvt : dkt;
@@ -343,7 +338,6 @@ __global__ void __launch_bounds__(512, 2) attn_bwd_p256(const PArgs a) {
 
   // ---- prologue: head 0's K image / lse / fragments and tile 0, then tile 1 behind the first delta
   if (total == 0) return;
-  if ((a.prio == 1 && wave >= 4) || (a.prio == 2 && wave < 4)) __builtin_amdgcn_s_setprio(1);
   if constexpr (TAIL)
     if (tid < 4) reinterpret_cast<unsigned*>(smem + G::OFF_ZERO)[tid] = 0u;  // (the prologue's barrier publishes it)
   issue_head(0);
@@ -367,7 +361,7 @@ __global__ void __launch_bounds__(512, 2) attn_bwd_p256(const PArgs a) {
     // [A] tile g + 1 (issued one iteration ago, with the K image / lse of its head if it opens one) has landed: every
     // vector-memory operation of this wave except the youngest one -- the dq store of tile g - 1 -- is complete
     // (DH = 72: the dq tail is a second store -- two operations stay in flight)
-    __builtin_amdgcn_s_waitcnt(TAIL ? 0x0072 : (ABL & 3) ? 0x0070 : 0x0071);  // vmcnt(1) lgkmcnt(0)  (timing builds without that store: vmcnt(0))
+    __builtin_amdgcn_s_waitcnt(TAIL ? 0x0072 : 0x0071);  // vmcnt(1) lgkmcnt(0)
     asm volatile("" ::: "memory");
     __builtin_amdgcn_s_barrier();  // [B] ... everybody's pieces; everybody has finished phase 2 of tile g - 1
     if (t == 0 && j > 0) store_dkdv(j - 1);
@@ -377,92 +371,90 @@ __global__ void __launch_bounds__(512, 2) attn_bwd_p256(const PArgs a) {
       if (((g + 2) & 3) == 0) issue_head((g + 2) >> 2);
     }
     // ---- [E] phase 1: this wave's 32 keys against the 64 query rows of tile g
-    if constexpr (!(ABL & 4)) {
-      if constexpr (TAIL) phase1_consts(opaque_lane());
-      const unsigned Qs = (unsigned)((g % P_RING) * P_SLOT), Gs = Qs + 8192;
-      const float* ls = TAIL ? reinterpret_cast<const float*>(smem + (g % P_RING) * P_SLOT + G::OFF_TL)
-                             : reinterpret_cast<const float*>(smem + P_OFF_LSE + (j & 1) * 1024) + 64 * t;
-      const float* dl = reinterpret_cast<const float*>(smem + P_OFF_DELTA + (g & 1) * 256);
-      char* const dsimg = smem + P_OFF_DS;
+    if constexpr (TAIL) phase1_consts(opaque_lane());
+    const unsigned Qs = (unsigned)((g % P_RING) * P_SLOT), Gs = Qs + 8192;
+    const float* ls = TAIL ? reinterpret_cast<const float*>(smem + (g % P_RING) * P_SLOT + G::OFF_TL)
+                           : reinterpret_cast<const float*>(smem + P_OFF_LSE + (j & 1) * 1024) + 64 * t;
+    const float* dl = reinterpret_cast<const float*>(smem + P_OFF_DELTA + (g & 1) * 256);
+    char* const dsimg = smem + P_OFF_DS;
 #pragma unroll
-      for (int sub = 0; sub < 2; ++sub) {
-        // row constants as the INITIAL accumulators: S' = Q.K^T - lse / scale, dP' = dO.V^T - delta
-        f32x16 S, dP;
+    for (int sub = 0; sub < 2; ++sub) {
+      // row constants as the INITIAL accumulators: S' = Q.K^T - lse / scale, dP' = dO.V^T - delta
+      f32x16 S, dP;
 #pragma unroll
-        for (int g4 = 0; g4 < 4; ++g4) {
-          const f32x4 l4 = load4(ls + 32 * sub + 8 * g4 + 4 * h);
-          const f32x4 d4 = load4(dl + 32 * sub + 8 * g4 + 4 * h);
+      for (int g4 = 0; g4 < 4; ++g4) {
+        const f32x4 l4 = load4(ls + 32 * sub + 8 * g4 + 4 * h);
+        const f32x4 d4 = load4(dl + 32 * sub + 8 * g4 + 4 * h);
 #pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            S[4 * g4 + e] = l4[e] * ninv_scale;
-            dP[4 * g4 + e] = d4[e];
-          }
+        for (int e = 0; e < 4; ++e) {
+          S[4 * g4 + e] = l4[e] * ninv_scale;
+          dP[4 * g4 + e] = d4[e];
         }
+      }
 #pragma unroll
-        for (int s = 0; s < 4; ++s) {
-          const unsigned off = (B0 ^ (unsigned)(s << 5)) + 4096u * sub;
-          const uint4 qa = *reinterpret_cast<const uint4*>(smem + Qs + off);
-          const uint4 ga = *reinterpret_cast<const uint4*>(smem + Gs + off);
-          S = mfma32(qa, kf[s], S);
-          dP = mfma32(ga, vf[s], dP);
-        }
-        if constexpr (TAIL) {  // the upper lane half (k slots 8-15) reads the 16 zero bytes
-          const unsigned off = Qs + (unsigned)G::OFF_TT + TQ0 + 1024u * sub;
-          const uint4 qa = *reinterpret_cast<const uint4*>(smem + (h ? (unsigned)G::OFF_ZERO : off));
-          const uint4 ga = *reinterpret_cast<const uint4*>(smem + (h ? (unsigned)G::OFF_ZERO : off + 128));
-          S = mfma32(qa, kf[4], S);
-          dP = mfma32(ga, vf[4], dP);
-        }
+      for (int s = 0; s < 4; ++s) {
+        const unsigned off = (B0 ^ (unsigned)(s << 5)) + 4096u * sub;
+        const uint4 qa = *reinterpret_cast<const uint4*>(smem + Qs + off);
+        const uint4 ga = *reinterpret_cast<const uint4*>(smem + Gs + off);
+        S = mfma32(qa, kf[s], S);
+        dP = mfma32(ga, vf[s], dP);
+      }
+      if constexpr (TAIL) {  // the upper lane half (k slots 8-15) reads the 16 zero bytes
+        const unsigned off = Qs + (unsigned)G::OFF_TT + TQ0 + 1024u * sub;
+        const uint4 qa = *reinterpret_cast<const uint4*>(smem + (h ? (unsigned)G::OFF_ZERO : off));
+        const uint4 ga = *reinterpret_cast<const uint4*>(smem + (h ? (unsigned)G::OFF_ZERO : off + 128));
+        S = mfma32(qa, kf[4], S);
+        dP = mfma32(ga, vf[4], dP);
+      }
 #pragma unroll
-        for (int i = 0; i < 16; ++i) {
-          const float p = __builtin_amdgcn_exp2f(S[i] * c);
-          S[i] = p;
-          dP[i] *= p;
-        }
-        // dS rounded to bf16 once: the pairs feed the [key][q] image (4 consecutive q per 8-byte store) and the dK operand
-        bf16x2 dsp[8];
+      for (int i = 0; i < 16; ++i) {
+        const float p = __builtin_amdgcn_exp2f(S[i] * c);
+        S[i] = p;
+        dP[i] *= p;
+      }
+      // dS rounded to bf16 once: the pairs feed the [key][q] image (4 consecutive q per 8-byte store) and the dK operand
+      bf16x2 dsp[8];
 #pragma unroll
-        for (int jj = 0; jj < 8; ++jj) dsp[jj] = bf16x2{(bf16_t)dP[2 * jj], (bf16_t)dP[2 * jj + 1]};
+      for (int jj = 0; jj < 8; ++jj) dsp[jj] = bf16x2{(bf16_t)dP[2 * jj], (bf16_t)dP[2 * jj + 1]};
 #pragma unroll
-        for (int g4 = 0; g4 < 4; ++g4) {
-          uint2 w;
-          w.x = *reinterpret_cast<const unsigned*>(&dsp[2 * g4]);
-          w.y = *reinterpret_cast<const unsigned*>(&dsp[2 * g4 + 1]);
-          const int key = k0 + r;
-          *reinterpret_cast<uint2*>(dsimg + key * 128 + (((8 * sub + 2 * g4 + h) ^ Fsw(key)) << 3)) = w;
-        }
-        f32x16 tv = {}, tk = {};  // TAIL: this sub-tile's rows 64..95 of dV^T / dK^T
+      for (int g4 = 0; g4 < 4; ++g4) {
+        uint2 w;
+        w.x = *reinterpret_cast<const unsigned*>(&dsp[2 * g4]);
+        w.y = *reinterpret_cast<const unsigned*>(&dsp[2 * g4 + 1]);
+        const int key = k0 + r;
+        *reinterpret_cast<uint2*>(dsimg + key * 128 + (((8 * sub + 2 * g4 + h) ^ Fsw(key)) << 3)) = w;
+      }
+      f32x16 tv = {}, tk = {};  // TAIL: this sub-tile's rows 64..95 of dV^T / dK^T
 #pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2) {
-          const uint4 pf = pack8(S, s2);
-          uint4 dsf;
-          dsf.x = *reinterpret_cast<const unsigned*>(&dsp[4 * s2]);
-          dsf.y = *reinterpret_cast<const unsigned*>(&dsp[4 * s2 + 1]);
-          dsf.z = *reinterpret_cast<const unsigned*>(&dsp[4 * s2 + 2]);
-          dsf.w = *reinterpret_cast<const unsigned*>(&dsp[4 * s2 + 3]);
+      for (int s2 = 0; s2 < 2; ++s2) {
+        const uint4 pf = pack8(S, s2);
+        uint4 dsf;
+        dsf.x = *reinterpret_cast<const unsigned*>(&dsp[4 * s2]);
+        dsf.y = *reinterpret_cast<const unsigned*>(&dsp[4 * s2 + 1]);
+        dsf.z = *reinterpret_cast<const unsigned*>(&dsp[4 * s2 + 2]);
+        dsf.w = *reinterpret_cast<const unsigned*>(&dsp[4 * s2 + 3]);
 #pragma unroll
-          for (int dt = 0; dt < 2; ++dt) {
-            const unsigned x0 = (A0 ^ (unsigned)(0x30 * s2) ^ (unsigned)(0x40 * dt)) + 2048u * s2 + 4096u * sub;
-            const unsigned x1 = (x0 ^ 0x20u) + 1024u;
-            const uint4 gt = tr_pair(Gs + x0, Gs + x1);
-            const uint4 qt = tr_pair(Qs + x0, Qs + x1);
-            dvT[dt] = mfma32(gt, pf, dvT[dt]);
-            dkT[dt] = mfma32(qt, dsf, dkT[dt]);
-          }
-          if constexpr (TAIL) {
-            const unsigned x0 = Qs + (unsigned)G::OFF_TT + TA0 + 512u * s2 + 1024u * sub;
-            const uint4 gt = tr_pair(x0 + 128u, x0 + 128u + 256u);
-            const uint4 qt = tr_pair(x0, x0 + 256u);
-            tv = mfma32(gt, pf, tv);
-            tk = mfma32(qt, dsf, tk);
-          }
+        for (int dt = 0; dt < 2; ++dt) {
+          const unsigned x0 = (A0 ^ (unsigned)(0x30 * s2) ^ (unsigned)(0x40 * dt)) + 2048u * s2 + 4096u * sub;
+          const unsigned x1 = (x0 ^ 0x20u) + 1024u;
+          const uint4 gt = tr_pair(Gs + x0, Gs + x1);
+          const uint4 qt = tr_pair(Qs + x0, Qs + x1);
+          dvT[dt] = mfma32(gt, pf, dvT[dt]);
+          dkT[dt] = mfma32(qt, dsf, dkT[dt]);
         }
         if constexpr (TAIL) {
+          const unsigned x0 = Qs + (unsigned)G::OFF_TT + TA0 + 512u * s2 + 1024u * sub;
+          const uint4 gt = tr_pair(x0 + 128u, x0 + 128u + 256u);
+          const uint4 qt = tr_pair(x0, x0 + 256u);
+          tv = mfma32(gt, pf, tv);
+          tk = mfma32(qt, dsf, tk);
+        }
+      }
+      if constexpr (TAIL) {
 #pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            dvt[e] += tv[e];
-            dkt[e] += tk[e];
-          }
+        for (int e = 0; e < 4; ++e) {
+          dvt[e] += tv[e];
+          dkt[e] += tk[e];
         }
       }
     }
@@ -471,49 +463,46 @@ __global__ void __launch_bounds__(512, 2) attn_bwd_p256(const PArgs a) {
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this wave's dS^T (and delta) writes have reached LDS
     __builtin_amdgcn_s_barrier();                       // [F] dS^T image complete
     // ---- [G] phase 2: dQ^T[d][q] = K^T[d][key] . dS^T[key][q]; wave w owns q-block w & 3 and d-blocks 2 (w >> 2), + 1
-    if constexpr (!(ABL & 1)) {
-      if constexpr (TAIL) phase2_consts(opaque_lane());
-      const int qblk = wave & 3, db0 = 2 * (wave >> 2);
-      const unsigned Ki = (unsigned)(P_OFF_K + (j & 1) * KIMG), Di = (unsigned)P_OFF_DS;
-      const unsigned ka = K0 ^ (unsigned)(db0 << 5), kb = K0 ^ (unsigned)((db0 + 1) << 5), da = D0 ^ (unsigned)(qblk << 5);
-      f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f}, acc2 = {0.f, 0.f, 0.f, 0.f};
-      // (TAIL: waves w and w + 4 BOTH form rows 64..71 of query block w & 3 and store the same eight bytes per lane -- one
-      // instruction stream for every wave, so the hand-counted wait at the top of the tile needs no branch: behind one, hipcc's
-      // wait-count pass no longer trusted it and drained the DMA ring in front of the S / dP MFMAs of every tile)
+    if constexpr (TAIL) phase2_consts(opaque_lane());
+    const int qblk = wave & 3, db0 = 2 * (wave >> 2);
+    const unsigned Ki = (unsigned)(P_OFF_K + (j & 1) * KIMG), Di = (unsigned)P_OFF_DS;
+    const unsigned ka = K0 ^ (unsigned)(db0 << 5), kb = K0 ^ (unsigned)((db0 + 1) << 5), da = D0 ^ (unsigned)(qblk << 5);
+    f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f}, acc2 = {0.f, 0.f, 0.f, 0.f};
+    // (TAIL: waves w and w + 4 BOTH form rows 64..71 of query block w & 3 and store the same eight bytes per lane -- one
+    // instruction stream for every wave, so the hand-counted wait at the top of the tile needs no branch: behind one, hipcc's
+    // wait-count pass no longer trusted it and drained the DMA ring in front of the S / dP MFMAs of every tile)
 #pragma unroll
-      for (int kk = 0; kk < 8; ++kk) {
-        const unsigned ko = 4096u * kk;
-        const uint4 fa = tr_pair(Ki + ka + ko, Ki + (ka ^ 0x10u) + 512u + ko);
-        const uint4 fb = tr_pair(Ki + kb + ko, Ki + (kb ^ 0x10u) + 512u + ko);
-        const uint4 fd = tr_pair(Di + da + ko, Di + (da ^ 0x10u) + 512u + ko);
-        acc0 = mfma16(fa, fd, acc0);
-        acc1 = mfma16(fb, fd, acc1);
-        if constexpr (TAIL) {
-          const unsigned kt = Ki + 32768u + KT0 + 512u * kk;
-          acc2 = mfma16(tr_pair(kt, kt + 64u), fd, acc2);
-        }
-      }
-      // D[row = d = 16 db + 4 fq + reg][col = q = fr]: the lane holds 4 consecutive d of both d-blocks of one query row.
-      // v_permlane16_swap pairs fq with fq ^ 1: even fq keeps d-block db0 (8 consecutive d), odd fq takes d-block db0 + 1
-      int b, hd;
-      head_ptrs(j, b, hd);
-      const f32x4 v0 = acc0 * a.scale, v1 = acc1 * a.scale;
-      const bf16x4 p0b = {(bf16_t)v0[0], (bf16_t)v0[1], (bf16_t)v0[2], (bf16_t)v0[3]};
-      const bf16x4 p1b = {(bf16_t)v1[0], (bf16_t)v1[1], (bf16_t)v1[2], (bf16_t)v1[3]};
-      const uint2 p0 = *reinterpret_cast<const uint2*>(&p0b), p1 = *reinterpret_cast<const uint2*>(&p1b);
-      const su32x2 sx = __builtin_amdgcn_permlane16_swap(p0.x, p1.x, false, false);
-      const su32x2 sy = __builtin_amdgcn_permlane16_swap(p0.y, p1.y, false, false);
-      const bool odd = fq & 1;
-      const int d = odd ? 16 * (db0 + 1) + 4 * (fq - 1) : 16 * db0 + 4 * fq;
-      bf16_t* dst = a.dq + ((int64_t)b * T + 64 * t + 16 * qblk + fr) * a.ldq + hd * DH + d;
-      if constexpr (!(ABL & 2)) *reinterpret_cast<uint4*>(dst) = uint4{sx[0], sy[0], sx[1], sy[1]};
-      else asm volatile("" ::"v"(sx[0]), "v"(sy[0]), "v"(sx[1]), "v"(sy[1]), "v"(dst));
+    for (int kk = 0; kk < 8; ++kk) {
+      const unsigned ko = 4096u * kk;
+      const uint4 fa = tr_pair(Ki + ka + ko, Ki + (ka ^ 0x10u) + 512u + ko);
+      const uint4 fb = tr_pair(Ki + kb + ko, Ki + (kb ^ 0x10u) + 512u + ko);
+      const uint4 fd = tr_pair(Di + da + ko, Di + (da ^ 0x10u) + 512u + ko);
+      acc0 = mfma16(fa, fd, acc0);
+      acc1 = mfma16(fb, fd, acc1);
       if constexpr (TAIL) {
-        // D[row = 64 + 4 fq + reg][col = q = fr]: lanes fq < 2 hold the eight real rows; the K tail's transposing reads fetch
-        // columns 0..7 twice, so rows 72..79 -- lanes fq >= 2 -- are copies of rows 64..71 and store the same bytes again
-        const f32x4 v2 = acc2 * a.scale;
-        store4(a.dq + ((int64_t)b * T + 64 * t + 16 * qblk + fr) * a.ldq + hd * DH + 64 + 4 * (fq & 1), v2);
+        const unsigned kt = Ki + 32768u + KT0 + 512u * kk;
+        acc2 = mfma16(tr_pair(kt, kt + 64u), fd, acc2);
       }
+    }
+    // D[row = d = 16 db + 4 fq + reg][col = q = fr]: the lane holds 4 consecutive d of both d-blocks of one query row.
+    // v_permlane16_swap pairs fq with fq ^ 1: even fq keeps d-block db0 (8 consecutive d), odd fq takes d-block db0 + 1
+    int b, hd;
+    head_ptrs(j, b, hd);
+    const f32x4 v0 = acc0 * a.scale, v1 = acc1 * a.scale;
+    const bf16x4 p0b = {(bf16_t)v0[0], (bf16_t)v0[1], (bf16_t)v0[2], (bf16_t)v0[3]};
+    const bf16x4 p1b = {(bf16_t)v1[0], (bf16_t)v1[1], (bf16_t)v1[2], (bf16_t)v1[3]};
+    const uint2 p0 = *reinterpret_cast<const uint2*>(&p0b), p1 = *reinterpret_cast<const uint2*>(&p1b);
+    const su32x2 sx = __builtin_amdgcn_permlane16_swap(p0.x, p1.x, false, false);
+    const su32x2 sy = __builtin_amdgcn_permlane16_swap(p0.y, p1.y, false, false);
+    const bool odd = fq & 1;
+    const int d = odd ? 16 * (db0 + 1) + 4 * (fq - 1) : 16 * db0 + 4 * fq;
+    bf16_t* dst = a.dq + ((int64_t)b * T + 64 * t + 16 * qblk + fr) * a.ldq + hd * DH + d;
+    *reinterpret_cast<uint4*>(dst) = uint4{sx[0], sy[0], sx[1], sy[1]};
+    if constexpr (TAIL) {
+      // D[row = 64 + 4 fq + reg][col = q = fr]: lanes fq < 2 hold the eight real rows; the K tail's transposing reads fetch
+      // columns 0..7 twice, so rows 72..79 -- lanes fq >= 2 -- are copies of rows 64..71 and store the same bytes again
+      const f32x4 v2 = acc2 * a.scale;
+      store4(a.dq + ((int64_t)b * T + 64 * t + 16 * qblk + fr) * a.ldq + hd * DH + 64 + 4 * (fq & 1), v2);
     }
   }
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -556,7 +545,6 @@ struct FArgs {
   float* lse;
   int B, H, ldq, ldk, ldv, ldo, nheads;
   float scale;
-  int prio;
 };
 
 template <int N>
@@ -671,7 +659,6 @@ __global__ void __launch_bounds__(512, 2) attn_fwd_p256(const FArgs a) {
     return y;
   };
   if (total == 0) return;
-  if ((a.prio == 1 && wave >= 4) || (a.prio == 2 && wave < 4)) __builtin_amdgcn_s_setprio(1);
   static_assert(AHEAD == 4 || AHEAD == 3, "the tile issued in iteration g belongs to the next head from t = 4 - AHEAD on");
   if constexpr (TAIL)
     if (tid < 4) reinterpret_cast<unsigned*>(smem + G::OFF_ZERO)[tid] = 0u;  // (published by the first tile's barrier)
@@ -811,27 +798,25 @@ __global__ void __launch_bounds__(512, 2) attn_fwd_p256(const FArgs a) {
 
 }  // namespace
 
-static int p256_prio() {
-  static UwuEnv e("UWU_P256_PRIO");
-  return e.get().set ? e.ival : 0;
-}
-
 bool uwu_attn_p256_ok(int T, int Tk, int d, int ldq, int ldk, int ldv, int ldo) {
-  static UwuEnv on("UWU_ATTN_P256");  // "0": the one-workgroup-per-head kernel of attention_mfma.hip (A/B comparisons)
+  // "0": the one-workgroup-per-head kernel of attention_mfma.hip
+  // (test_attention_p256_kernels_are_bit_identical_to_the_per_head_kernels)
+  static UwuEnv on("UWU_ATTN_P256");
   // (a device that cannot give one workgroup P_LDS bytes falls through to the per-head kernels of attention_mfma.hip)
   if (on.get().is('0') || T != 256 || Tk != 256 || ldq % 8 || ldk % 8 || ldv % 8 || ldo % 8 || uwu_dev_cus() <= 0) return false;
   if (d == 64) return uwu_dev_lds_fits(P_LDS);
-  static UwuEnv on72("UWU_ATTN_P256_D72");  // "0": head dim 72 stays on the key-block + dq kernels of attention_mfma.hip
+  // "0": head dim 72 stays on the key-block + dq kernels of attention_mfma.hip (test_attention_p256_head_dim_72)
+  static UwuEnv on72("UWU_ATTN_P256_D72");
   return d == 72 && !on72.get().is('0') && uwu_dev_lds_fits(PGeom<72>::LDS);
 }
 
 int uwu_attn_p256_bwd(const void* q, const void* k, const void* v, const void* o, const void* dO, const float* lse, void* dq,
                       void* dk, void* dv, int B, int H, int d, int ldq, int ldk, int ldv, int ldo, float scale, hipStream_t st) {
-  static unsigned char done[5][UWU_MAX_DEV];  // per kernel instance, per device
+  static unsigned char done[UWU_MAX_DEV];  // per device
   const int n_cu = uwu_dev_cus();
   if (d == 72) {
     static unsigned char done72[UWU_MAX_DEV];
-    if (n_cu <= 0 || !uwu_func_lds(reinterpret_cast<const void*>(attn_bwd_p256<0, 72>), PGeom<72>::LDS, done72)) {
+    if (n_cu <= 0 || !uwu_func_lds(reinterpret_cast<const void*>(attn_bwd_p256<72>), PGeom<72>::LDS, done72)) {
       uwu_set_error("attention_bwd(p256, d = 72): the device cannot give a workgroup %d bytes of LDS", (int)PGeom<72>::LDS);
       return UWU_ELAUNCH;
     }
@@ -839,17 +824,12 @@ int uwu_attn_p256_bwd(const void* q, const void* k, const void* v, const void* o
     a.q = (const bf16_t*)q; a.k = (const bf16_t*)k; a.v = (const bf16_t*)v; a.o = (const bf16_t*)o; a.dO = (const bf16_t*)dO;
     a.dq = (bf16_t*)dq; a.dk = (bf16_t*)dk; a.dv = (bf16_t*)dv; a.lse = lse;
     a.B = B; a.H = H; a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo; a.nheads = B * H; a.scale = scale;
-    a.prio = p256_prio();
     const int grid = a.nheads < n_cu ? a.nheads : n_cu;
-    hipLaunchKernelGGL((attn_bwd_p256<0, 72>), dim3(grid), dim3(512), PGeom<72>::LDS, st, a);
+    hipLaunchKernelGGL(attn_bwd_p256<72>, dim3(grid), dim3(512), PGeom<72>::LDS, st, a);
     UWU_LAUNCH_CHECK("attention_bwd(p256, d = 72)");
     return UWU_OK;
   }
-  if (n_cu <= 0 || !uwu_func_lds(reinterpret_cast<const void*>(attn_bwd_p256<0>), P_LDS, done[0]) ||
-      !uwu_func_lds(reinterpret_cast<const void*>(attn_bwd_p256<1>), P_LDS, done[1]) ||
-      !uwu_func_lds(reinterpret_cast<const void*>(attn_bwd_p256<2>), P_LDS, done[2]) ||
-      !uwu_func_lds(reinterpret_cast<const void*>(attn_bwd_p256<3>), P_LDS, done[3]) ||
-      !uwu_func_lds(reinterpret_cast<const void*>(attn_bwd_p256<4>), P_LDS, done[4])) {
+  if (n_cu <= 0 || !uwu_func_lds(reinterpret_cast<const void*>(attn_bwd_p256<64>), P_LDS, done)) {
     uwu_set_error("attention_bwd(p256): the device cannot give a workgroup %d bytes of LDS", (int)P_LDS);
     return UWU_ELAUNCH;
   }
@@ -857,23 +837,17 @@ int uwu_attn_p256_bwd(const void* q, const void* k, const void* v, const void* o
   a.q = (const bf16_t*)q; a.k = (const bf16_t*)k; a.v = (const bf16_t*)v; a.o = (const bf16_t*)o; a.dO = (const bf16_t*)dO;
   a.dq = (bf16_t*)dq; a.dk = (bf16_t*)dk; a.dv = (bf16_t*)dv; a.lse = lse;
   a.B = B; a.H = H; a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo; a.nheads = B * H; a.scale = scale;
-  a.prio = p256_prio();
   // one workgroup per CU (150 KB of LDS each); every workgroup exits after its last head -- no inter-workgroup waits
   const int grid = a.nheads < n_cu ? a.nheads : n_cu;
-  static UwuEnv abl("UWU_P256_ABL");  // timing-only ablations / stamps (tools/bench_attn.py); results are wrong with them
-  switch (abl.get().ival) {
-    case 1: hipLaunchKernelGGL(attn_bwd_p256<1>, dim3(grid), dim3(512), P_LDS, st, a); break;
-    case 2: hipLaunchKernelGGL(attn_bwd_p256<2>, dim3(grid), dim3(512), P_LDS, st, a); break;
-    case 3: hipLaunchKernelGGL(attn_bwd_p256<3>, dim3(grid), dim3(512), P_LDS, st, a); break;
-    case 4: hipLaunchKernelGGL(attn_bwd_p256<4>, dim3(grid), dim3(512), P_LDS, st, a); break;
-    default: hipLaunchKernelGGL(attn_bwd_p256<0>, dim3(grid), dim3(512), P_LDS, st, a);
-  }
+  hipLaunchKernelGGL(attn_bwd_p256<64>, dim3(grid), dim3(512), P_LDS, st, a);
   UWU_LAUNCH_CHECK("attention_bwd(p256)");
   return UWU_OK;
 }
 
 bool uwu_attn_p256_fwd_ok(int nheads, int T, int Tk, int d, int ldq, int ldk, int ldv, int ldo) {
-  static UwuEnv on("UWU_ATTN_P256F");  // "0": the kernel of attention_mfma.hip (A/B comparisons); "1": at every head count
+  // "0": the kernel of attention_mfma.hip, "1": at every head count
+  // (test_attention_p256_kernels_are_bit_identical_to_the_per_head_kernels, test_attention_p256_head_dim_72)
+  static UwuEnv on("UWU_ATTN_P256F");
   if (on.get().is('0')) return false;
   // One workgroup per CU walking nheads / 256 heads: with few heads per workgroup the uneven shares (384 heads: 19.6 us
   // against 16.0 for the two-workgroups-per-head kernel) and the lack of a second workgroup per CU cost more than the
@@ -881,7 +855,8 @@ bool uwu_attn_p256_fwd_ok(int nheads, int T, int Tk, int d, int ldq, int ldk, in
   if (!on.is('1') && nheads < 1024) return false;
   if (T != 256 || Tk != 256 || ldq % 8 || ldk % 8 || ldv % 8 || ldo % 8 || uwu_dev_cus() <= 0) return false;
   if (d == 64) return uwu_dev_lds_fits(F_LDS);
-  static UwuEnv on72("UWU_ATTN_P256F_D72");  // "0": head dim 72 stays on the kernel of attention_mfma.hip
+  // "0": head dim 72 stays on the kernel of attention_mfma.hip (test_attention_p256_head_dim_72)
+  static UwuEnv on72("UWU_ATTN_P256F_D72");
   return d == 72 && !on72.get().is('0') && uwu_dev_lds_fits(FGeom<72>::LDS);
 }
 
@@ -898,7 +873,6 @@ int uwu_attn_p256_fwd(const void* q, const void* k, const void* v, void* o, floa
   FArgs a{};
   a.q = (const bf16_t*)q; a.k = (const bf16_t*)k; a.v = (const bf16_t*)v; a.out = (bf16_t*)o; a.lse = lse;
   a.B = B; a.H = H; a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo; a.nheads = B * H; a.scale = scale;
-  a.prio = p256_prio();
   const int grid = a.nheads < n_cu ? a.nheads : n_cu;
   if (d == 72) hipLaunchKernelGGL(attn_fwd_p256<72>, dim3(grid), dim3(512), lds, st, a);
   else hipLaunchKernelGGL(attn_fwd_p256<64>, dim3(grid), dim3(512), lds, st, a);

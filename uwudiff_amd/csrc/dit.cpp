@@ -193,10 +193,6 @@ int lin_fwd(const void* X, const void* W, const float* bias, void* Y, void* Y2, 
             int epi, void* st) {
   return uwu_gemm(X, W, Y, Y2, bias, nullptr, M, N, K, K, K, N, 0, 0, 0, dt, cdt, epi, 1, st);
 }
-static bool fc2_dgrad_as() {  // UWU_DIT_FC2DG_AS=0: the 256x256 kernel on the K-major weight (A/B comparisons)
-  static UwuEnv on("UWU_DIT_FC2DG_AS");  // (UwuEnv: re-read after uwu_env_refresh(), so in-process A/B runs compare two paths)
-  return !on.get().is('0');
-}
 // the fp32 conditioning Linears ([B, *] rows): matrix-vector kernels when the shape is covered (csrc/skinny.hip)
 int lin_fwd32(const float* X, const float* W, const float* bias, float* Y, float* Y2, int M, int N, int K, int epi, void* st) {
   // measured at batch 16 (us, matrix-vector kernel vs 128x128-tile GEMM): 256 -> 384: 19 vs 25, 1280 -> 384: 22 vs 87; the
@@ -214,10 +210,9 @@ int lin_dgrad(const void* dY, const void* W, void* dX, const void* aux, int M, i
 // weight; silu(c) and d(mod) cast once), fp32 accumulate and fp32 outputs.  In the exact-fp32 MFMA mode (1/16 of the bf16 rate) its
 // three GEMMs were 0.85 ms of the 45 ms step at B = 768 (16.5 GFLOP each).  The reference runs this Linear under bf16 autocast
 // like every other one (Lightning precision "bf16-mixed", configs/demo_training_latent.yaml); the fp32 parity mode and small
-// batches (where the matrix-vector kernels take the conditioning Linears) are unchanged.  UWU_DIT_MOD_BF16=0: off (A/B).
+// batches (where the matrix-vector kernels take the conditioning Linears) are unchanged.
 static bool mod_bf16(const uwu_dit_desc& d) {
-  static UwuEnv on("UWU_DIT_MOD_BF16");
-  return !on.get().is('0') && d.dtype == UWU_BF16 && d.B >= 64 && d.mod_total % 8 == 0;
+  return d.dtype == UWU_BF16 && d.B >= 64 && d.mod_total % 8 == 0;
 }
 // dX[M,K] = dY[M,N] . W[N,K] for a LONG reduction N and few rows M (the batched adaLN linear: N = L*6*D+2*D):
 // split the reduction over workgroups and accumulate with fp32 atomics into a zeroed dX.
@@ -330,7 +325,8 @@ int f8_bwd(const F8& f, const void* dY, const void* X8t, const void* W8t, float*
 // Delayed scaling knows the scale of a tensor before the tensor exists, so the two widest ones of a block -- gelu(u) (fc2's
 // input) and du (fc1's output gradient), [M, 4 D] each -- leave the GEMM that produces them as fp8 (row-major and transposed)
 // and the quantising pass over their bf16 copy (4 bytes of HBM traffic per element) is gone.  The first step (just-in-time
-// scaling: the scale comes from the tensor) keeps the two-pass form.  UWU_F8_EMIT=0: off (A/B).
+// scaling: the scale comes from the tensor) keeps the two-pass form.  UWU_F8_EMIT=0: off
+// (test_dit_fp8_emit_switch_compares_two_paths).
 static bool f8_emit(const uwu_dit_desc& d);
 // h = LN(x_in + gate * y) * (1 + scale) + shift feeding ONLY an fp8 Linear: with delayed scaling the LayerNorm kernel writes the
 // e4m3 images itself (row-major into the shared x8, transposed into the layer's saved copy) and no bf16 h exists.
@@ -364,10 +360,6 @@ struct Fork {
   hipEvent_t ev[8];     // 0-3: producer done (recorded on main); 4-7: consumer done (recorded on side[slot])
   bool on = false;
 };
-unsigned fork_event_flags() {
-  const char* e = getenv("UWU_DIT_EVENT_SYSTEM");  // =1: default (system-scope) events, for A/B comparisons
-  return (e && e[0] == '1') ? hipEventDisableTiming : (hipEventDisableTiming | hipEventReleaseToDevice);
-}
 bool fork_resources(Fork& f, hipStream_t caller_side) {
   static hipEvent_t pool[8];
   static hipStream_t extra[3];
@@ -376,7 +368,7 @@ bool fork_resources(Fork& f, hipStream_t caller_side) {
     for (auto& e : pool)
       // device-scope release: these events only order streams of this GPU.  The default system-scope fence (cache writeback +
       // invalidate so that the HOST could read the results) sat in front of every kernel that followed a record on the main stream
-      if (hipEventCreateWithFlags(&e, fork_event_flags()) != hipSuccess) return false;
+      if (hipEventCreateWithFlags(&e, hipEventDisableTiming | hipEventReleaseToDevice) != hipSuccess) return false;
     for (auto& x : extra)
       if (hipStreamCreateWithFlags(&x, hipStreamNonBlocking) != hipSuccess) return false;
     made = true;
@@ -704,7 +696,7 @@ extern "C" int uwu_dit_backward(const uwu_dit_desc* dp, const float* dout, void*
     if (side_used[1]) RUN(join_side(fk, 1));  // the previous block's fc1 weight gradient still reads du
     // du = (dy.W2) * gelu'(u).  The fc1 bias gradient = colsum(du) comes out of the fc1 weight-gradient kernel (extra MFMAs
     // against an all-ones fragment, free there) -- as fp32 atomics in this epilogue it cost 79 us per launch at B = 768
-    if (dt == UWU_BF16 && D == 384 && M % 256 == 0 && M >= 256 * 256 && D4 % 64 == 0 && D4 >= 1024 && D4 <= 2048 && fc2_dgrad_as()) {
+    if (dt == UWU_BF16 && D == 384 && M % 256 == 0 && M >= 256 * 256 && D4 % 64 == 0 && D4 >= 1024 && D4 <= 2048) {
       // the store-heavy input gradient (604 MB in, 604 MB out for 151 MB of dy): W2 transposed once (1.2 MB), then the
       // A-stationary kernel with dy held in fragment registers and the dGELU epilogue between the K-steps
       RUN(uwu_transpose_bf16(w.fc2_w, P.at(L.w2t), D, D4, D4, D, st));

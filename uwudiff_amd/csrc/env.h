@@ -2,7 +2,10 @@
 #pragma once
 #include <stdlib.h>
 
-// ---- environment switches (A/B comparisons, sweeps, tests) --------------------------------------------------
+// ---- environment switches -------------------------------------------------------------------------------------
+// Every UwuEnv switch turns a kernel path off or forces it, so that a GPU test (tests/test_gemm_gpu.py, test_kernels_gpu.py,
+// test_fp8_gpu.py) can compare it with its reference kernel; the comment at each switch names the test.  The only other
+// variable the library reads is UWU_DIT_SIDE_STREAMS (dit.cpp).  tests/test_cabi_symbols.py holds the list of names.
 // Read once per switch and cached: a launch does not call getenv().  uwu_env_refresh() (api.cpp) bumps the generation so
 // that the next use re-reads -- the tests flip switches inside one process.
 int uwu_env_generation();

@@ -1598,7 +1598,7 @@ __global__ void __launch_bounds__(512, 2) gemm_f8_kernel(const GemmArgs g, const
     }
   } else if constexpr (EMIT) {
     // (the dGELU form keeps the masked epilogue only: a second copy of it cost that kernel 32 spilled registers)
-    if (EPI == UWU_EPI_BIAS_GELU && g.p8_cont && m0 + 256 <= g.M && n0 + 256 <= g.N) f8_emit_epilogue<EPI, EPI == UWU_EPI_BIAS_GELU>(acc, g, smem, m0, n0, tid);
+    if (EPI == UWU_EPI_BIAS_GELU && m0 + 256 <= g.M && n0 + 256 <= g.N) f8_emit_epilogue<EPI, EPI == UWU_EPI_BIAS_GELU>(acc, g, smem, m0, n0, tid);
     else f8_emit_epilogue<EPI, false>(acc, g, smem, m0, n0, tid);
   } else {
     EpiPre<bf16_t, 8, 4> pre;
@@ -1612,11 +1612,10 @@ __global__ void __launch_bounds__(512, 2) gemm_f8_kernel(const GemmArgs g, const
 template <typename T, typename TC, bool TA, bool TB, bool ACC, bool GL = false, int EPI = -1>
 int launch(const GemmArgs& g, int split, hipStream_t st) {
   auto kern = gemm_kernel<T, TC, TA, TB, ACC, GL, EPI>;
-  static bool attr_done = false;  // per instantiation
-  if (!attr_done) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                        4 * TILE_BYTES);
-    attr_done = true;
+  static unsigned char done[UWU_MAX_DEV];
+  if (!uwu_func_lds(reinterpret_cast<const void*>(kern), 4 * TILE_BYTES, done)) {
+    uwu_set_error("gemm: the device cannot give a workgroup %d bytes of LDS", 4 * TILE_BYTES);
+    return UWU_ELAUNCH;
   }
   dim3 grid(g.tiles_m * g.tiles_n, 1, split);
   UwuProfScope prof(st);
@@ -1630,10 +1629,10 @@ template <typename TC, int EPI, bool TB, int FI, int CONV = 0>
 int launch_r3(GemmArgs g, hipStream_t st) {
   auto kern = gemm_r3_kernel<TC, EPI, TB, FI, CONV>;
   constexpr int LDS = (FI == 8 ? 3 : 4) * (32 * FI * R_ROWB + R_BSUB);
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    attr_done = true;
+  static unsigned char done[UWU_MAX_DEV];
+  if (!uwu_func_lds(reinterpret_cast<const void*>(kern), LDS, done)) {
+    uwu_set_error("gemm_r3: the device cannot give a workgroup %d bytes of LDS", LDS);
+    return UWU_ELAUNCH;
   }
   g.tiles_m = (g.M + 32 * FI - 1) / (32 * FI);
   g.tiles_n = (g.N + 127) / 128;
@@ -1648,10 +1647,10 @@ template <typename TC, int EPI, bool TB>
 int launch_big(GemmArgs g, hipStream_t st) {
   auto kern = gemm_big_kernel<TC, EPI, TB>;
   constexpr int LDS = 2 * 4 * TILE_BYTES;
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    attr_done = true;
+  static unsigned char done[UWU_MAX_DEV];
+  if (!uwu_func_lds(reinterpret_cast<const void*>(kern), LDS, done)) {
+    uwu_set_error("gemm_big: the device cannot give a workgroup %d bytes of LDS", LDS);
+    return UWU_ELAUNCH;
   }
   g.tiles_m = (g.M + 255) / 256;
   g.tiles_n = (g.N + 255) / 256;
@@ -1662,27 +1661,28 @@ int launch_big(GemmArgs g, hipStream_t st) {
   return UWU_OK;
 }
 // A-stationary kernel: K = 384, whole 256-row panels, 64-column chunks, bf16 output with the paired 16-byte stores.
-// UWU_GEMM_AS=0 turns it off (A/B comparisons).
+// UWU_GEMM_AS=0 turns it off (test_gemm_as_bias_gelu_matches_big_kernel).
 static bool use_as(const GemmArgs& g, int out_bytes) {
-  static UwuEnv on("UWU_GEMM_AS"), nmin_e("UWU_AS_NMIN");  // UWU_AS_NMIN=n: sweeps
+  static UwuEnv on("UWU_GEMM_AS");
   if (on.get().is('0')) return false;
-  const int nmin = nmin_e.get().set ? nmin_e.ival : 1024;
   // one workgroup per 256 rows: below one per CU the chip is under-filled (per-GPU batch 64: 9.8k -> 8.2k images/s with it)
-  return g.K == AS_K && g.M % 256 == 0 && g.M >= 256 * 256 && g.N % AS_BN == 0 && g.N <= 2048 && g.N >= nmin && out_bytes == 2 &&
+  return g.K == AS_K && g.M % 256 == 0 && g.M >= 256 * 256 && g.N % AS_BN == 0 && g.N <= 2048 && g.N >= 1024 && out_bytes == 2 &&
          g.lda % 8 == 0 &&
          g.ldb % 8 == 0 && g.ldc % 8 == 0 && (((uintptr_t)g.A | (uintptr_t)g.B | (uintptr_t)g.C | (uintptr_t)g.C2) & 15) == 0;
 }
-static bool use_as_bias() {  // the plain bias Linears with N >= 1024 (qkv forward: 285 -> 231 us in the step); UWU_GEMM_AS_BIAS=0: off
+// the plain bias Linears with N >= 1024 (qkv forward: 285 -> 231 us in the step); UWU_GEMM_AS_BIAS=0: off
+// (test_gemm_as_bias_matches_other_kernels)
+static bool use_as_bias() {
   static UwuEnv on("UWU_GEMM_AS_BIAS");
   return !on.get().is('0');
 }
 template <typename TC, int EPI>
 int launch_as(GemmArgs g, hipStream_t st) {
   auto kern = gemm_as_kernel<TC, EPI>;
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, AS_LDS);
-    attr_done = true;
+  static unsigned char done[UWU_MAX_DEV];
+  if (!uwu_func_lds(reinterpret_cast<const void*>(kern), AS_LDS, done)) {
+    uwu_set_error("gemm_as: the device cannot give a workgroup %d bytes of LDS", AS_LDS);
+    return UWU_ELAUNCH;
   }
   g.wide = 1;  // paired 16-byte stores
   UwuProfScope prof(st);
@@ -1695,10 +1695,10 @@ template <typename TC, int EPI, bool TB>
 int launch_m64(GemmArgs g, hipStream_t st) {
   auto kern = gemm_m64_kernel<TC, EPI, TB>;
   constexpr int LDS = M64_NST * (64 * ROW_BYTES + TILE_BYTES);
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    attr_done = true;
+  static unsigned char done[UWU_MAX_DEV];
+  if (!uwu_func_lds(reinterpret_cast<const void*>(kern), LDS, done)) {
+    uwu_set_error("gemm_m64: the device cannot give a workgroup %d bytes of LDS", LDS);
+    return UWU_ELAUNCH;
   }
   g.tiles_m = (g.M + 63) / 64;
   g.tiles_n = (g.N + 127) / 128;
@@ -1708,24 +1708,24 @@ int launch_m64(GemmArgs g, hipStream_t st) {
   UWU_LAUNCH_CHECK("gemm_m64");
   return UWU_OK;
 }
-// 64x128 kernel: when the 128x128 grid has fewer tiles than the chip has CUs.  UWU_GEMM_M64=0 turns it off.
+// 64x128 kernel: when the 128x128 grid has fewer tiles than the chip has CUs.  UWU_GEMM_M64=0 turns it off
+// (test_gemm_m64_tile_matches_128_kernel).
 static bool use_m64(const GemmArgs& g, bool tb) {
-  static UwuEnv on("UWU_GEMM_M64"), thr_e("UWU_M64_TILES");  // UWU_M64_TILES=n: sweeps
+  static UwuEnv on("UWU_GEMM_M64");
   if (on.get().is('0')) return false;
   if (g.K % 64 || (((uintptr_t)g.A | (uintptr_t)g.B) & 15) || g.lda % 8 || g.ldb % 8) return false;
   if (tb && (g.N % 8 || g.N < 8)) return false;
   const int64_t tiles = (int64_t)((g.M + 127) / 128) * ((g.N + 127) / 128);
-  const int thr = thr_e.get().set ? thr_e.ival : 256;
-  return tiles < thr && g.M > 64;
+  return tiles < 256 && g.M > 64;
 }
 template <typename TC, int EPI, bool TB>
 int launch_wide(GemmArgs g, hipStream_t st) {
   auto kern = gemm_wide_kernel<TC, EPI, TB>;
   constexpr int LDS = 2 * (192 + 384) * ROW_BYTES;
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    attr_done = true;
+  static unsigned char done[UWU_MAX_DEV];
+  if (!uwu_func_lds(reinterpret_cast<const void*>(kern), LDS, done)) {
+    uwu_set_error("gemm_wide: the device cannot give a workgroup %d bytes of LDS", LDS);
+    return UWU_ELAUNCH;
   }
   g.tiles_m = (g.M + 191) / 192;
   g.tiles_n = g.N / 384;
@@ -1738,7 +1738,8 @@ int launch_wide(GemmArgs g, hipStream_t st) {
 // 192x384 kernel: N a multiple of 384 (and not of 256), and enough tiles that the last round of one-workgroup-per-CU
 // tiles is not mostly empty.  Same box, M = 131072: qkv fwd 193 -> 183 us, fc2 fwd 207 -> 185, qkv / fc1 input gradients
 // 149 -> 138 / 191 -> 172; at M = 65536 (342 tiles of 192 rows = 1.3 rounds of 256 CUs) it loses 5-10 %, hence the
-// fill rule.  UWU_GEMM_WIDE=0 turns it off, =1 forces it (tests, A/B comparisons).
+// fill rule.  UWU_GEMM_WIDE=0 turns it off, =1 forces it
+// (test_gemm_wide_tile_matches_128_kernel).
 static bool use_wide(const GemmArgs& g) {
   if (g.K % 64 || g.N % 384 || g.N % 256 == 0) return false;
   static UwuEnv on("UWU_GEMM_WIDE");
@@ -1751,7 +1752,8 @@ static bool use_wide(const GemmArgs& g) {
 // 256x256 kernel: taken where the 256x128 ring would be and N is a multiple of 256 (no padded column tiles).
 // Same-box A/B of the whole step: DiT-S/2 +1.8 % (only its two GELU Linears qualify: fc1 + GELU 187 -> 167 us at B = 256;
 // the dGELU input gradient is a wash there),
-// DiT-B/2 +5.5 %, DiT-L/2 +1.9 %, SDXL UNet +-0.  UWU_GEMM_BIG=0 turns it off (A/B comparisons).
+// DiT-B/2 +5.5 %, DiT-L/2 +1.9 %, SDXL UNet +-0.  UWU_GEMM_BIG=0 turns it off
+// (test_gemm_big_tile_matches_128_kernel).
 // (A masked ragged last column tile was tried on DiT-XL/2's N = 3456 / 1152 Linears: +0.4 % at 4 % padding, -1.8 % at
 // 11 % -- not taken.)
 static bool use_big(const GemmArgs& g) {
@@ -1802,11 +1804,10 @@ __global__ void __launch_bounds__(256) splitk_reduce4_kernel(const float* __rest
     __syncthreads();
   }
 }
-// launches the reduce (UWU_SPLITK_REDUCE4=0: the one-thread-per-float4 form)
+// launches the reduce: the four-lane form from 8 slices on, one thread per float4 below
 static void launch_splitk_reduce(const float* part, float* C, int M, int N, int ldc, int split, hipStream_t st) {
-  static UwuEnv r4("UWU_SPLITK_REDUCE4");
   const int64_t quads = (int64_t)M * N / 4;
-  if (!r4.get().is('0') && split >= 8) {
+  if (split >= 8) {
     int rg = (int)((quads + 63) / 64);
     if (rg > 8192) rg = 8192;
     hipLaunchKernelGGL(splitk_reduce4_kernel, dim3(rg), dim3(256), 0, st, part, C, M, N, ldc, split);
@@ -1822,12 +1823,8 @@ static void launch_splitk_reduce(const float* part, float* C, int M, int N, int 
 // Outputs with >= 64 tiles of a reduction of a few thousand rows: fewer slices, the XCDs divided between slices and tiles
 // (gemm_tr_kernel's xs): every halving of the slice count halves the fp32 slice traffic.
 int tr_split(int tiles, int steps) {
-  static UwuEnv forced_e("UWU_TR_SPLIT"), min_e("UWU_TR_MINSTEPS");  // sweeps
-  const int forced = forced_e.get().ival;
   int split;
-  if (forced > 0) {
-    split = forced;
-  } else if (tiles >= 320 && steps <= 1024) {  // (sweep at 6144 / 24576 tokens: 400 tiles 361 -> 193 us, 200 tiles 166 -> 115,
+  if (tiles >= 320 && steps <= 1024) {  // (sweep at 6144 / 24576 tokens: 400 tiles 361 -> 193 us, 200 tiles 166 -> 115,
     split = 1;                                 //  150 tiles 122 -> 107, 100 tiles 223 -> 217; 50 tiles stay at 8 slices)
   } else if (tiles >= 140 && steps <= 1024) {
     split = 2;
@@ -1837,8 +1834,7 @@ int tr_split(int tiles, int steps) {
     int per_xcd = 64 / tiles;
     if (per_xcd < 1) per_xcd = 1;
     split = 8 * per_xcd;
-    const int min_steps = min_e.get().set ? min_e.ival : 32;
-    while (split > 8 && split * min_steps > steps) split -= 8;  // keep >= 32 K-steps per slice (batch 16: 3.82k -> 4.13k img/s, batch 64: 9.05k -> 9.79k with the four side streams)
+    while (split > 8 && split * 32 > steps) split -= 8;  // keep >= 32 K-steps per slice (batch 16: 3.82k -> 4.13k img/s, batch 64: 9.05k -> 9.79k with the four side streams)
   }
   if (split > steps) split = steps;
   return split < 1 ? 1 : split;
@@ -1848,13 +1844,11 @@ int tr_xs(int split) { return split % 8 == 0 ? 8 : (split % 4 == 0 ? 4 : (split 
 
 template <int FI, int FJ, bool CONVW = false>
 int launch_tr(GemmArgs g, void* scratch, size_t scratch_bytes, hipStream_t st) {
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tr_kernel<FI, FJ, false, CONVW>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, T_NST * T_STAGE);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tr_kernel<FI, FJ, true, CONVW>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, T_NST * T_STAGE);
-    attr_done = true;
+  static unsigned char done_a[UWU_MAX_DEV], done_p[UWU_MAX_DEV];
+  if (!uwu_func_lds(reinterpret_cast<const void*>(gemm_tr_kernel<FI, FJ, false, CONVW>), T_NST * T_STAGE, done_a) ||
+      !uwu_func_lds(reinterpret_cast<const void*>(gemm_tr_kernel<FI, FJ, true, CONVW>), T_NST * T_STAGE, done_p)) {
+    uwu_set_error("gemm_tr: the device cannot give a workgroup %d bytes of LDS", T_NST * T_STAGE);
+    return UWU_ELAUNCH;
   }
   g.tiles_m = (g.M + 32 * FI - 1) / (32 * FI);
   g.tiles_n = (g.N + 32 * FJ - 1) / (32 * FJ);
@@ -1900,12 +1894,14 @@ int trw_split(int tiles, int steps) {
   if (split > steps) split = steps;
   return split < 1 ? 1 : split;
 }
-// 0 = not taken, 1 = 192 x 384 tiles, 2 = 384 x 192 tiles.  UWU_GEMM_TRW=0 turns it off (A/B comparisons).
+// 0 = not taken, 1 = 192 x 384 tiles, 2 = 384 x 192 tiles.  UWU_GEMM_TRW=0 turns it off
+// (test_gemm_wgrad_many_tiles_xcd_partition).
 int pick_trw(const GemmArgs& g) {
   static UwuEnv on("UWU_GEMM_TRW");
   if (on.get().is('0')) return 0;
   // short reductions (per-GPU batch < 128 images): the 4-stage ring of a whole-LDS workgroup barely fills and nothing else fits
-  // on its CU; the 256x128 kernel (two workgroups per CU) measured 1-2 % faster there.  UWU_GEMM_TRW=1 forces it (tests).
+  // on its CU; the 256x128 kernel (two workgroups per CU) measured 1-2 % faster there.  UWU_GEMM_TRW=1 forces it
+  // (test_gemm_wgrad_scratch_path).
   const bool force = on.is('1');
   if (g.K % 32 || g.K < (force ? 4096 : 32768) || g.M % 8 || g.N % 8) return 0;
   if ((((uintptr_t)g.A | (uintptr_t)g.B) & 15) || g.lda % 8 || g.ldb % 8) return 0;
@@ -1921,10 +1917,10 @@ template <int WM, int WN, int FI, int FJ>
 int launch_trw(GemmArgs g, void* scratch, hipStream_t st) {
   constexpr int NST = 4;
   auto kern = gemm_trw_kernel<WM, WN, FI, FJ, NST>;
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, NST * W_STAGE);
-    attr_done = true;
+  static unsigned char done[UWU_MAX_DEV];
+  if (!uwu_func_lds(reinterpret_cast<const void*>(kern), NST * W_STAGE, done)) {
+    uwu_set_error("gemm_trw: the device cannot give a workgroup %d bytes of LDS", NST * W_STAGE);
+    return UWU_ELAUNCH;
   }
   g.tiles_m = (g.M + 16 * FI * WM - 1) / (16 * FI * WM);
   g.tiles_n = (g.N + 16 * FJ * WN - 1) / (16 * FJ * WN);
@@ -1944,7 +1940,7 @@ int launch_trw(GemmArgs g, void* scratch, hipStream_t st) {
 }
 // K-major x K-major accumulate (the weight gradients): 0 = keep the 128x128 kernel, 1 = 256x128, 2 = 128x256
 int pick_tr(const GemmArgs& g) {
-  static UwuEnv on("UWU_GEMM_TR");  // "0": off (A/B comparisons)
+  static UwuEnv on("UWU_GEMM_TR");  // "0": off (test_gemm_tr_exact_integers, test_gemm_tr_random)
   if (on.get().is('0')) return 0;
   if (g.K % 32 || g.K < 96 || g.M % 8 || g.N % 8 || g.M < 8 || g.N < 8) return 0;
   if ((((uintptr_t)g.A | (uintptr_t)g.B) & 15) || g.lda % 8 || g.ldb % 8) return 0;
@@ -1961,25 +1957,18 @@ int pick_tr(const GemmArgs& g) {
 // (N = 384) the second round of 512 workgroup slots would be half empty.  The 128x128 ring (4 stages) replaces
 // gemm_kernel's register-staged input-gradient path (K-major weight: qkv dgrad 96 -> 70 us, fc1 dgrad 111 -> 90).
 int pick_r3(const GemmArgs& g, bool tb) {
-  static UwuEnv on("UWU_GEMM_R3"), t8_e("UWU_R3_T8"), t4_e("UWU_R3_T4");  // "0": off (A/B comparisons); thresholds: sweeps
+  static UwuEnv on("UWU_GEMM_R3");  // "0": off (test_gemm_r3_exact_integers_and_dgelu)
   if (on.get().is('0')) return 0;
   if (g.K % 32 || g.K < 96) return 0;
   if ((((uintptr_t)g.A | (uintptr_t)g.B) & 15) || g.lda % 8 || g.ldb % 8) return 0;
   if (tb && (g.N % 8 || g.N < 8)) return 0;
-  const int thr8 = t8_e.get().set ? t8_e.ival : 512;  // sweep at per-GPU batches 16..256: 512 / 128 never lose
-  const int thr4 = t4_e.get().set ? t4_e.ival : 128;
+  // tile thresholds 512 / 128: the sweep at per-GPU batches 16..256 found them never losing
   const int64_t t8 = (int64_t)((g.M + 255) / 256) * ((g.N + 127) / 128);
   // long contractions (the UNet's K = 640 .. 5120): the larger tile's operand reuse pays from one workgroup per CU on
   // (SDXL shape, 12 x 4x128x128: 480 tiles of 256x128 per 1280-wide Linear; 30.6 -> 31.8 images/s)
-  const bool t8_env = t8_e.set;
-  if (t8 >= ((g.K >= 640 && !t8_env) ? 256 : thr8)) return 8;
+  if (t8 >= (g.K >= 640 ? 256 : 512)) return 8;
   const int64_t t4 = (int64_t)((g.M + 127) / 128) * ((g.N + 127) / 128);
-  return (tb && t4 >= thr4) ? 4 : 0;  // K-contiguous B at N = 384: gemm_kernel's 128-byte rows measured faster (proj 35 vs 43 us)
-}
-
-bool no_glds() {
-  static UwuEnv on("UWU_GEMM_NO_GLDS");
-  return on.get().is('1');
+  return (tb && t4 >= 128) ? 4 : 0;  // K-contiguous B at N = 384: gemm_kernel's 128-byte rows measured faster (proj 35 vs 43 us)
 }
 
 template <typename T, typename TC>
@@ -2040,7 +2029,7 @@ int dispatch_trans(const GemmArgs& g, int ta, int tb, bool acc, int split, hipSt
         if (g.epi == UWU_EPI_BIAS_GELU) return launch_m64<TC, UWU_EPI_BIAS_GELU, false>(g, st);
       }
     }
-    if (g.K % GT<T>::BK == 0 && !no_glds()) {
+    if (g.K % GT<T>::BK == 0) {
       if constexpr (hot) {
         if (g.epi == UWU_EPI_NONE) return launch<T, TC, false, false, false, true, UWU_EPI_NONE>(g, split, st);
         if (g.epi == UWU_EPI_BIAS) return launch<T, TC, false, false, false, true, UWU_EPI_BIAS>(g, split, st);
@@ -2082,10 +2071,10 @@ template <int EPI, int FA>
 int launch_f8(GemmArgs g, const float* sa, const float* sb, hipStream_t st) {
   auto kern = gemm_f8_kernel<bf16_t, EPI, FA, false>;
   constexpr int LDS = 2 * 4 * TILE_BYTES;
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    attr_done = true;
+  static unsigned char done[UWU_MAX_DEV];
+  if (!uwu_func_lds(reinterpret_cast<const void*>(kern), LDS, done)) {
+    uwu_set_error("gemm_f8: the device cannot give a workgroup %d bytes of LDS", LDS);
+    return UWU_ELAUNCH;
   }
   g.tiles_m = (g.M + 255) / 256;
   g.tiles_n = (g.N + 255) / 256;
@@ -2106,10 +2095,6 @@ int launch_f8_emit(GemmArgs g, const float* sa, const float* sb, hipStream_t st)
   }
   g.tiles_m = (g.M + 255) / 256;
   g.tiles_n = (g.N + 255) / 256;
-  {
-    static UwuEnv full("UWU_F8_EMIT_FULL");  // "0": the masked epilogue for full tiles too (A/B)
-    g.p8_cont = full.get().is('0') ? 0 : 1;
-  }
   UwuProfScope prof(st);
   hipLaunchKernelGGL(kern, dim3(g.tiles_m * g.tiles_n), dim3(512), LDS, st, g, sa, sb);
   // bytes: operands once, the bf16 output (if any), the dGELU aux, both fp8 images
@@ -2130,10 +2115,10 @@ template <int FA>
 int launch_f8_part(GemmArgs g, const float* sa, const float* sb, void* scratch, hipStream_t st) {
   auto kern = gemm_f8_kernel<float, UWU_EPI_NONE, FA, true>;
   constexpr int LDS = 2 * 4 * TILE_BYTES;
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    attr_done = true;
+  static unsigned char done[UWU_MAX_DEV];
+  if (!uwu_func_lds(reinterpret_cast<const void*>(kern), LDS, done)) {
+    uwu_set_error("gemm_f8(split-K): the device cannot give a workgroup %d bytes of LDS", LDS);
+    return UWU_ELAUNCH;
   }
   g.tiles_m = (g.M + 255) / 256;
   g.tiles_n = (g.N + 255) / 256;
@@ -2363,15 +2348,7 @@ extern "C" int uwu_gemm(const void* A, const void* B, void* C, void* C2, const f
   // 16-byte epilogue stores need 8-column granularity and 16-byte aligned rows
   g.wide = (!acc && c_dtype == UWU_BF16 && N % 8 == 0 && ldc % 8 == 0 && ((uintptr_t)C & 15) == 0 &&
             (C2 == nullptr || epilogue == UWU_EPI_DGELU || ((uintptr_t)C2 & 15) == 0)) ? 1 : 0;
-  {
-    static UwuEnv ntc("UWU_GEMM_NT_C");
-    g.nt_c = ntc.get().set ? ntc.ival : 0;
-  }
   g.aux16 = (epilogue == UWU_EPI_DGELU && dtype == UWU_BF16 && N % 8 == 0 && ldaux % 8 == 0 && ((uintptr_t)aux & 15) == 0) ? 1 : 0;
-  {
-    static UwuEnv a16("UWU_GEMM_AUX16");  // "0": the 8-byte aux loads (A/B comparisons)
-    if (a16.get().is('0')) g.aux16 = 0;
-  }
 
   const int ktiles = (K + bk - 1) / bk;
   int split = split_k < 1 ? 1 : split_k;

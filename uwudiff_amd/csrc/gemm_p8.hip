@@ -45,9 +45,6 @@ using IC = std::integral_constant<int, H>;
 // address of fragment 0 plus 2048 i: one address register per operand and k half instead of one per fragment.
 __device__ __forceinline__ int p8_swz(int row, int chunk) { return row * ROW_BYTES + (((chunk ^ (row >> 1)) & 7) << 4); }
 
-// ABL: timing-only builds (UWU_P8_ABL, plain forward only): 1 = no output stores, 2 = two K steps, 3 = wave groups in step,
-// 4 = no MFMAs, 5 = no LDS-DMA inside the K loop, 6 = no fragment reads
-//
 // PERSISTENT: grid = one workgroup per CU; a workgroup walks tiles L = blockIdx.x, + gridDim.x, ... (same XCD-chunked order as
 // the one-tile-per-workgroup kernels).  After the K loop of a tile the first seven half-tiles of the NEXT tile are requested
 // BEFORE the epilogue of this one: the first fetch of a tile and the drain of the previous tile's stores -- a third of the
@@ -55,7 +52,7 @@ __device__ __forceinline__ int p8_swz(int row, int chunk) { return row * ROW_BYT
 // K steps) -- run under each other and under the first K steps.  Vector-memory operations retire in issue order, so the wait
 // for K step 0 of the next tile is vmcnt(6 + S) with S = the stores this wave is known to have issued after the request
 // (16, 32 with two outputs, 0 for a ragged tile: waiting for more than needed is always safe).
-template <typename TC, int EPI, bool TB, int ABL = 0>
+template <typename TC, int EPI, bool TB>
 __global__ void __launch_bounds__(512, 2) gemm_p8_kernel(const GemmArgs g) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   typedef bf16_t T;
@@ -64,7 +61,7 @@ __global__ void __launch_bounds__(512, 2) gemm_p8_kernel(const GemmArgs g) {
   const int grp = wave >> 2, wc = wave & 3;
   const int fr = lane & 15, fq = lane >> 4;
   const int nblk = g.tiles_m * g.tiles_n;
-  const int nk = ABL == 2 ? 2 : g.K >> 6;
+  const int nk = g.K >> 6;
   auto tile_of = [&](int L) __attribute__((always_inline)) {  // XCD-aware tile order as in gemm_kernel
     const int xcd = L & 7, loc = L >> 3;
     const int q = nblk >> 3, rm = nblk & 7;
@@ -137,7 +134,6 @@ __global__ void __launch_bounds__(512, 2) gemm_p8_kernel(const GemmArgs g) {
   uint4 af[4][2], bf0[2][2], bf1[2][2];
 
   auto read_a = [&](auto slotc) __attribute__((always_inline)) {  // 8 reads
-    if constexpr (ABL == 6) return;
     constexpr unsigned hi = decltype(slotc)::value >= 4 ? 65536u : 0u, off = decltype(slotc)::value * P8_HT - hi;
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk)
@@ -150,7 +146,6 @@ __global__ void __launch_bounds__(512, 2) gemm_p8_kernel(const GemmArgs g) {
       }
   };
   auto read_b = [&](auto slotc, uint4 (&bf)[2][2]) __attribute__((always_inline)) {  // 4 reads (TB: 8 transposing reads)
-    if constexpr (ABL == 6) return;
     constexpr unsigned up = decltype(slotc)::value >= 4 ? 65536u : 0u, off = decltype(slotc)::value * P8_HT - up;
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk)
@@ -176,10 +171,7 @@ __global__ void __launch_bounds__(512, 2) gemm_p8_kernel(const GemmArgs g) {
 #pragma unroll
       for (int i = 0; i < 4; ++i)
 #pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          if constexpr (ABL == 4) asm volatile("" ::"v"(*reinterpret_cast<const gu32x4*>(&bf[j][kk])), "v"(*reinterpret_cast<const gu32x4*>(&af[i][kk])));
-          else mma_frag<T>(bf[j][kk], af[i][kk], c[i][j]);
-        }
+        for (int j = 0; j < 2; ++j) mma_frag<T>(bf[j][kk], af[i][kk], c[i][j]);
     __builtin_amdgcn_s_setprio(0);
     __builtin_amdgcn_sched_barrier(0);
   };
@@ -199,8 +191,8 @@ __global__ void __launch_bounds__(512, 2) gemm_p8_kernel(const GemmArgs g) {
   // q of the next K step 0), so a tile boundary has no drain, no refill and no extra barrier.  Otherwise (dGELU: its epilogue
   // loads would drain the queue; odd K step counts) a tile ends with the two wave groups back in step, requests the next tile
   // ahead of its epilogue and starts over.
-  constexpr bool can_cont = EPI != UWU_EPI_DGELU && ABL != 3;
-  const bool cont = can_cont && g.p8_cont && !(nk & 1) && nk >= 4;
+  constexpr bool can_cont = EPI != UWU_EPI_DGELU;
+  const bool cont = can_cont && !(nk & 1) && nk >= 4;
   int s_prev = 0;       // stores this wave issued behind the request for K step 1 of the tile (0 unless all are known to exist)
   bool pending = false; // the accumulators still hold the PREVIOUS tile (continuous mode)
   int m0, n0, em0 = 0, en0 = 0;  // tile being loaded / tile whose results are in the accumulators
@@ -223,29 +215,22 @@ __global__ void __launch_bounds__(512, 2) gemm_p8_kernel(const GemmArgs g) {
   // epilogue of quadrant (x, y) of tile (em0, en0); the accumulators are zero afterwards
   auto epi_quadrant = [&](auto xc, auto yc) __attribute__((always_inline)) {
     constexpr int x = decltype(xc)::value, y = decltype(yc)::value;
-    if constexpr (ABL == 1) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) asm volatile("" ::"v"(acc[x][y][i][j]));
+    const int m_q = em0 + 128 * x + 64 * grp, n_q = en0 + 128 * y + 32 * wc;
+    EpiPre<T, 4, 2> pre;
+    if constexpr (has_bias) {
+      const uint4 b0 = r_read128<128 * y>(bias_ad), b1 = r_read128<128 * y + 64>(bias_ad);
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_sched_barrier(0);
+      pre.bias[0] = *reinterpret_cast<const f32x4*>(&b0);
+      pre.bias[1] = *reinterpret_cast<const f32x4*>(&b1);
     } else {
-      const int m_q = em0 + 128 * x + 64 * grp, n_q = en0 + 128 * y + 32 * wc;
-      EpiPre<T, 4, 2> pre;
-      if constexpr (has_bias) {
-        const uint4 b0 = r_read128<128 * y>(bias_ad), b1 = r_read128<128 * y + 64>(bias_ad);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
-        pre.bias[0] = *reinterpret_cast<const f32x4*>(&b0);
-        pre.bias[1] = *reinterpret_cast<const f32x4*>(&b1);
-      } else {
-        pre.bias[0] = pre.bias[1] = f32x4{0.f, 0.f, 0.f, 0.f};
-      }
-      if constexpr (EPI == UWU_EPI_DGELU) {
-#pragma unroll
-        for (int i = 0; i < EpiPre<T, 4, 2>::PD; ++i) epi_load_aux_row<T, 4, 2>(g, m_q, n_q, fr, fq, i, pre.aux[i]);
-      }
-      epilogue_tile<T, TC, 4, 2, EPI>(acc[x][y], pre, g, m_q, n_q, fr, fq, nullptr, 0, 0, -1, EPI == UWU_EPI_DGELU ? cs[y] : nullptr);
+      pre.bias[0] = pre.bias[1] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
+    if constexpr (EPI == UWU_EPI_DGELU) {
+#pragma unroll
+      for (int i = 0; i < EpiPre<T, 4, 2>::PD; ++i) epi_load_aux_row<T, 4, 2>(g, m_q, n_q, fr, fq, i, pre.aux[i]);
+    }
+    epilogue_tile<T, TC, 4, 2, EPI>(acc[x][y], pre, g, m_q, n_q, fr, fq, nullptr, 0, 0, -1, EPI == UWU_EPI_DGELU ? cs[y] : nullptr);
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -261,7 +246,7 @@ __global__ void __launch_bounds__(512, 2) gemm_p8_kernel(const GemmArgs g) {
     constexpr int par = decltype(pc)::value;
     const int t1 = t + 1, t2 = t + 2;
     const bool strm = can_cont && stream;
-    const bool iss1 = ABL != 5 && (par == 1 || t != 0) && (t1 < nk || strm), iss2 = ABL != 5 && (t2 < nk || strm);
+    const bool iss1 = (par == 1 || t != 0) && (t1 < nk || strm), iss2 = t2 < nk || strm;
     const int k1 = t1 < nk ? t1 : t1 - nk, k2 = t2 < nk ? t2 : t2 - nk;
     const bool ep = can_cont && par == 0 && t == 0 && pending;
     // phase 0: (a0, b0)
@@ -320,16 +305,8 @@ __global__ void __launch_bounds__(512, 2) gemm_p8_kernel(const GemmArgs g) {
     issue(IC<2>{}, IC<1>{}, 1);
     issue(IC<3>{}, IC<1>{}, 1);
   };
-  // ABL 9: wave 0 / wave 4 stamp the 100 MHz clock into g.q8 ([workgroup][tile][16] uint64; UWU_P8_STAMPS=<address>)
-  int iter = 0;
-  auto stamp = [&](int slot) __attribute__((always_inline)) {
-    if constexpr (ABL == 9) {
-      if ((wave & 3) == 0 && lane == 0 && iter < 16)
-        reinterpret_cast<unsigned long long*>(g.q8)[((size_t)blockIdx.x * 16 + iter) * 16 + 8 * grp + slot] = __builtin_amdgcn_s_memrealtime();
-    }
-  };
   auto full_tile = [&]() __attribute__((always_inline)) {
-    return em0 + 256 <= g.M && en0 + 256 <= g.N && g.wide && sizeof(TC) == 2 && ABL != 1;
+    return em0 + 256 <= g.M && en0 + 256 <= g.N && g.wide && sizeof(TC) == 2;
   };
 
 #pragma unroll
@@ -346,31 +323,24 @@ __global__ void __launch_bounds__(512, 2) gemm_p8_kernel(const GemmArgs g) {
   prologue();
   r_wait_vm<8>();  // K step 0 has landed when all but elements 4-7 have
   bar();
-  if (grp == 1 && ABL != 3) bar();  // waves 4-7 run one barrier behind their SIMD partners
+  if (grp == 1) bar();  // waves 4-7 run one barrier behind their SIMD partners
   for (;;) {
-    stamp(0);
     Ln = L + gridDim.x;
     const bool has_next = Ln < nblk;
     stream = cont && has_next;
     for (int t = 0; t < nk; t += 2) {
       kstep(IC<0>{}, t);
-      if (t == 0) stamp(1);
       if (t + 1 < nk) kstep(IC<1>{}, t + 1);
-      if (t == 0) stamp(2);
-      if (t == 2) stamp(3);
     }
-    stamp(4);
     if (can_cont && stream) {
       // (the sources, m0 / n0 and em0 / en0 were switched in K step nk - 2)
       issue(IC<3>{}, IC<1>{}, 1);  // next tile's (1, A1): its slot was last read in phase 2 of the last K step
       pending = true;
       s_prev = full_tile() ? NST : 0;
       L = Ln;
-      stamp(6);
-      ++iter;
       continue;
     }
-    if (grp == 0 && ABL != 3) bar();  // every wave has passed the same number of barriers; nobody reads LDS any more
+    if (grp == 0) bar();  // every wave has passed the same number of barriers; nobody reads LDS any more
     em0 = m0;
     en0 = n0;
     // dGELU: the epilogue's aux loads would each drain the queue behind the request (trap (b)): request after the epilogue
@@ -380,7 +350,6 @@ __global__ void __launch_bounds__(512, 2) gemm_p8_kernel(const GemmArgs g) {
       prologue();
       __builtin_amdgcn_sched_barrier(0);
     }
-    stamp(5);
 #pragma unroll
     for (int y = 0; y < 2; ++y)
 #pragma unroll
@@ -408,8 +377,6 @@ __global__ void __launch_bounds__(512, 2) gemm_p8_kernel(const GemmArgs g) {
         __syncthreads();  // (the next tile's epilogue writes cs_lds again)
       }
     }
-    stamp(6);
-    ++iter;
     if (!has_next) break;
     if (!early) {
       setup(tile_of(Ln), m0, n0);
@@ -427,22 +394,20 @@ __global__ void __launch_bounds__(512, 2) gemm_p8_kernel(const GemmArgs g) {
       r_wait_vm<8>();
     }
     bar();
-    if (grp == 1 && ABL != 3) bar();
+    if (grp == 1) bar();
   }
 }
 
 // workgroups of the persistent grid: one per CU of the current device (a multiple of 8, so that a workgroup's tiles stay on
-// one XCD chunk); UWU_P8_GRID=n overrides (sweeps)
+// one XCD chunk)
 int p8_cus_impl() {
-  static UwuEnv ge("UWU_P8_GRID");
-  if (ge.get().set && ge.ival >= 8) return ge.ival & ~7;
   const int cus = uwu_dev_cus();
   return cus >= 8 ? cus & ~7 : 256;
 }
 
-template <typename TC, int EPI, bool TB, int ABL = 0>
+template <typename TC, int EPI, bool TB>
 int launch_p8(GemmArgs g, hipStream_t st) {
-  auto kern = gemm_p8_kernel<TC, EPI, TB, ABL>;
+  auto kern = gemm_p8_kernel<TC, EPI, TB>;
   static unsigned char done[UWU_MAX_DEV];
   if (!uwu_func_lds(reinterpret_cast<const void*>(kern), P8_LDS, done)) {
     uwu_set_error("gemm_p8: the device cannot give a workgroup %d bytes of LDS", P8_LDS);
@@ -451,10 +416,6 @@ int launch_p8(GemmArgs g, hipStream_t st) {
   g.tiles_m = (g.M + 255) / 256;
   g.tiles_n = (g.N + 255) / 256;
   const int nblk = g.tiles_m * g.tiles_n, ncu = p8_cus_impl();
-  {
-    static UwuEnv ce("UWU_P8_CONT");
-    g.p8_cont = ce.get().is('0') ? 0 : 1;
-  }
   UwuProfScope prof(st);
   hipLaunchKernelGGL(kern, dim3(nblk < ncu ? nblk : ncu), dim3(512), P8_LDS, st, g);
   prof.done(gemm_tag(g, TB, false), 0, 2.0 * g.M * g.N * g.K, gemm_bytes(g, 2, sizeof(TC)));
@@ -467,9 +428,9 @@ int launch_p8(GemmArgs g, hipStream_t st) {
 int uwu_p8_cus() { return p8_cus_impl(); }
 
 // bf16 in / bf16 out, K a multiple of 64, 16-byte addressable operands.  UWU_GEMM_P8=0: off, =1: every shape it can run
-// (tests, A/B comparisons); default: K >= 512 and at least one tile per CU.
+// (test_gemm_p8_exact_integers, test_gemm_p8n_exact_integers); default: K >= 512 and at least one tile per CU.
 bool uwu_gemm_p8_ok(const GemmArgs& g, bool tb) {
-  static UwuEnv on("UWU_GEMM_P8"), kmin_e("UWU_P8_KMIN"), tmin_e("UWU_P8_MINTILES");
+  static UwuEnv on("UWU_GEMM_P8");
   if (on.get().is('0') || !uwu_dev_lds_fits(P8_LDS)) return false;
   if (g.K % 64 || g.K < 128) return false;
   if ((((uintptr_t)g.A | (uintptr_t)g.B) & 15) || g.lda % 8 || g.ldb % 8) return false;
@@ -479,35 +440,17 @@ bool uwu_gemm_p8_ok(const GemmArgs& g, bool tb) {
   if (on.is('1')) return true;
   // dGELU: its epilogue loads keep a tile from streaming into the next (every tile drains): in the step the 256 x 256 two-stage
   // kernel is faster (DiT-B/2 fc2 input gradient: 697 vs 668 TFLOP/s)
-  static UwuEnv dg("UWU_P8_DGELU");  // "1": try it anyway (A/B)
-  if (g.epi == UWU_EPI_DGELU && !dg.get().is('1')) return false;
-  const int kmin = kmin_e.get().set ? kmin_e.ival : 512;
+  if (g.epi == UWU_EPI_DGELU) return false;
   const int64_t tiles = (int64_t)((g.M + 255) / 256) * ((g.N + 255) / 256);
   // padded column tiles: at most 1/8 of the columns may be padding (N = 1152 -> 5 tiles of 256: 10 %)
   const int64_t npad = (int64_t)((g.N + 255) / 256) * 256;
-  const int tmin = tmin_e.get().set ? tmin_e.ival : 160;  // (SDXL-shape UNet, 4x128x128 x 12: its 240-tile Linears on this kernel 32.3 -> 32.8 images/s)
-  return g.K >= kmin && tiles >= tmin && (npad - g.N) * 8 <= npad;
+  // at least 160 tiles (SDXL-shape UNet, 4x128x128 x 12: its 240-tile Linears on this kernel 32.3 -> 32.8 images/s)
+  return g.K >= 512 && tiles >= 160 && (npad - g.N) * 8 <= npad;
 }
 
 int uwu_launch_gemm_p8(const GemmArgs& g, bool tb, hipStream_t st) {
   if (!tb) {
-    if (g.epi == UWU_EPI_NONE) {
-      static UwuEnv abl("UWU_P8_ABL");
-      if (abl.get().set) {
-        if (abl.ival == 1) return launch_p8<bf16_t, UWU_EPI_NONE, false, 1>(g, st);
-        if (abl.ival == 2) return launch_p8<bf16_t, UWU_EPI_NONE, false, 2>(g, st);
-        if (abl.ival == 3) return launch_p8<bf16_t, UWU_EPI_NONE, false, 3>(g, st);
-        if (abl.ival == 4) return launch_p8<bf16_t, UWU_EPI_NONE, false, 4>(g, st);
-        if (abl.ival == 5) return launch_p8<bf16_t, UWU_EPI_NONE, false, 5>(g, st);
-        if (abl.ival == 6) return launch_p8<bf16_t, UWU_EPI_NONE, false, 6>(g, st);
-        if (abl.ival == 9 && getenv("UWU_P8_STAMPS")) {
-          GemmArgs g9 = g;
-          g9.q8 = (void*)strtoull(getenv("UWU_P8_STAMPS"), nullptr, 0);
-          return launch_p8<bf16_t, UWU_EPI_NONE, false, 9>(g9, st);
-        }
-      }
-      return launch_p8<bf16_t, UWU_EPI_NONE, false>(g, st);
-    }
+    if (g.epi == UWU_EPI_NONE) return launch_p8<bf16_t, UWU_EPI_NONE, false>(g, st);
     if (g.epi == UWU_EPI_BIAS) return launch_p8<bf16_t, UWU_EPI_BIAS, false>(g, st);
     if (g.epi == UWU_EPI_BIAS_GELU) return launch_p8<bf16_t, UWU_EPI_BIAS_GELU, false>(g, st);
   } else {

@@ -46,7 +46,6 @@ __global__ void __launch_bounds__(512, 2) gemm_p8f_kernel(const GemmArgs g, cons
   extern __shared__ __attribute__((aligned(16))) char smem[];
   typedef bf16_t T;  // (the epilogue's bias / output conversions; the operands are bytes)
   constexpr bool TB = false;
-  constexpr int ABL = 0;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int grp = wave >> 2, wc = wave & 3;
@@ -177,7 +176,7 @@ __global__ void __launch_bounds__(512, 2) gemm_p8f_kernel(const GemmArgs g, cons
   // loads would drain the queue; odd K step counts) a tile ends with the two wave groups back in step, requests the next tile
   // ahead of its epilogue and starts over.
   constexpr bool can_cont = true;
-  const bool cont = can_cont && g.p8_cont && !(nk & 1) && nk >= 4;
+  const bool cont = can_cont && !(nk & 1) && nk >= 4;
   int s_prev = 0;       // stores this wave issued behind the request for K step 1 of the tile (0 unless all are known to exist)
   bool pending = false; // the accumulators still hold the PREVIOUS tile (continuous mode)
   int m0, n0, em0 = 0, en0 = 0;  // tile being loaded / tile whose results are in the accumulators
@@ -199,48 +198,41 @@ __global__ void __launch_bounds__(512, 2) gemm_p8f_kernel(const GemmArgs g, cons
   // epilogue of quadrant (x, y) of tile (em0, en0); the accumulators are zero afterwards
   auto epi_quadrant = [&](auto xc, auto yc) __attribute__((always_inline)) {
     constexpr int x = decltype(xc)::value, y = decltype(yc)::value;
-    if constexpr (ABL == 1) {
+    const int m_q = em0 + 128 * x + 64 * grp, n_q = en0 + 128 * y + 32 * wc;
+    // (the lane's share of the output addresses is rebuilt here from a lane id hipcc cannot see through: hoisted out of the
+    // tile loop, eight copies of this epilogue kept a dozen 64-bit addresses alive across the K loop and spilled them)
+    // (the MFMAs are inline asm: hipcc's hazard recogniser does not know that acc[x][y] is a matrix-pipe result.  Its last
+    // write is at least three phases -- barriers -- back; the wait states make the distance explicit anyway)
+    int ln = lane;
+    asm volatile("s_nop 15\n\ts_nop 15" : "+v"(ln));
+    const int fr = ln & 15, fq = ln >> 4;
 #pragma unroll
-      for (int i = 0; i < 4; ++i)
+    for (int i = 0; i < 4; ++i)
 #pragma unroll
-        for (int j = 0; j < 2; ++j) asm volatile("" ::"v"(acc[x][y][i][j]));
+      for (int j = 0; j < 2; ++j) acc[x][y][i][j] = acc[x][y][i][j] * alpha;
+    EpiPre<T, 4, 2> pre;
+    if constexpr (has_bias) {
+      const uint4 b0 = r_read128<128 * y>(bias_ad), b1 = r_read128<128 * y + 64>(bias_ad);
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_sched_barrier(0);
+      pre.bias[0] = *reinterpret_cast<const f32x4*>(&b0);
+      pre.bias[1] = *reinterpret_cast<const f32x4*>(&b1);
     } else {
-      const int m_q = em0 + 128 * x + 64 * grp, n_q = en0 + 128 * y + 32 * wc;
-      // (the lane's share of the output addresses is rebuilt here from a lane id hipcc cannot see through: hoisted out of the
-      // tile loop, eight copies of this epilogue kept a dozen 64-bit addresses alive across the K loop and spilled them)
-      // (the MFMAs are inline asm: hipcc's hazard recogniser does not know that acc[x][y] is a matrix-pipe result.  Its last
-      // write is at least three phases -- barriers -- back; the wait states make the distance explicit anyway)
-      int ln = lane;
-      asm volatile("s_nop 15\n\ts_nop 15" : "+v"(ln));
-      const int fr = ln & 15, fq = ln >> 4;
+      pre.bias[0] = pre.bias[1] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    if constexpr (PART) {  // fp32 partial sums of K slice ezs: dense [M][N] slab ezs of the scratch (g.C2)
+      float* P = static_cast<float*>(g.C2) + (int64_t)ezs * g.M * g.N;
 #pragma unroll
-      for (int i = 0; i < 4; ++i)
+      for (int i = 0; i < 4; ++i) {
+        const int m = m_q + 16 * i + fr;
 #pragma unroll
-        for (int j = 0; j < 2; ++j) acc[x][y][i][j] = acc[x][y][i][j] * alpha;
-      EpiPre<T, 4, 2> pre;
-      if constexpr (has_bias) {
-        const uint4 b0 = r_read128<128 * y>(bias_ad), b1 = r_read128<128 * y + 64>(bias_ad);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
-        pre.bias[0] = *reinterpret_cast<const f32x4*>(&b0);
-        pre.bias[1] = *reinterpret_cast<const f32x4*>(&b1);
-      } else {
-        pre.bias[0] = pre.bias[1] = f32x4{0.f, 0.f, 0.f, 0.f};
-      }
-      if constexpr (PART) {  // fp32 partial sums of K slice ezs: dense [M][N] slab ezs of the scratch (g.C2)
-        float* P = static_cast<float*>(g.C2) + (int64_t)ezs * g.M * g.N;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const int m = m_q + 16 * i + fr;
-#pragma unroll
-          for (int j = 0; j < 2; ++j) {
-            const int n = n_q + 16 * j + 4 * fq;
-            if (m < g.M && n < g.N) store4(P + (int64_t)m * g.N + n, acc[x][y][i][j]);
-          }
+        for (int j = 0; j < 2; ++j) {
+          const int n = n_q + 16 * j + 4 * fq;
+          if (m < g.M && n < g.N) store4(P + (int64_t)m * g.N + n, acc[x][y][i][j]);
         }
-      } else {
-        epilogue_tile<T, TC, 4, 2, EPI>(acc[x][y], pre, g, m_q, n_q, fr, fq, nullptr, 0, 0, -1, nullptr);
       }
+    } else {
+      epilogue_tile<T, TC, 4, 2, EPI>(acc[x][y], pre, g, m_q, n_q, fr, fq, nullptr, 0, 0, -1, nullptr);
     }
 #pragma unroll
     for (int i = 0; i < 4; ++i)
@@ -257,7 +249,7 @@ __global__ void __launch_bounds__(512, 2) gemm_p8f_kernel(const GemmArgs g, cons
     constexpr int par = decltype(pc)::value;
     const int t1 = t + 1, t2 = t + 2;
     const bool strm = can_cont && stream;
-    const bool iss1 = ABL != 5 && (par == 1 || t != 0) && (t1 < nk || strm), iss2 = ABL != 5 && (t2 < nk || strm);
+    const bool iss1 = (par == 1 || t != 0) && (t1 < nk || strm), iss2 = t2 < nk || strm;
     const int k1 = t1 < nk ? t1 : t1 - nk, k2 = t2 < nk ? t2 : t2 - nk;
     const bool ep = can_cont && par == 0 && t == 0 && pending;
     // phase 0: (a0, b0)
@@ -317,7 +309,6 @@ __global__ void __launch_bounds__(512, 2) gemm_p8f_kernel(const GemmArgs g, cons
     issue(IC<2>{}, IC<1>{}, 1);
     issue(IC<3>{}, IC<1>{}, 1);
   };
-  auto stamp = [&](int) __attribute__((always_inline)) {};
   auto full_tile = [&]() __attribute__((always_inline)) {
     return !PART && em0 + 256 <= g.M && en0 + 256 <= g.N && g.wide && sizeof(TC) == 2;
   };
@@ -336,30 +327,24 @@ __global__ void __launch_bounds__(512, 2) gemm_p8f_kernel(const GemmArgs g, cons
   prologue();
   r_wait_vm<8>();  // K step 0 has landed when all but elements 4-7 have
   bar();
-  if (grp == 1 && ABL != 3) bar();  // waves 4-7 run one barrier behind their SIMD partners
+  if (grp == 1) bar();  // waves 4-7 run one barrier behind their SIMD partners
   for (;;) {
-    stamp(0);
     Ln = L + gridDim.x;
     const bool has_next = Ln < nblk;
     stream = cont && has_next;
     for (int t = 0; t < nk; t += 2) {
       kstep(IC<0>{}, t);
-      if (t == 0) stamp(1);
       if (t + 1 < nk) kstep(IC<1>{}, t + 1);
-      if (t == 0) stamp(2);
-      if (t == 2) stamp(3);
     }
-    stamp(4);
     if (can_cont && stream) {
       // (the sources, m0 / n0 and em0 / en0 were switched in K step nk - 2)
       issue(IC<3>{}, IC<1>{}, 1);  // next tile's (1, A1): its slot was last read in phase 2 of the last K step
       pending = true;
       s_prev = full_tile() ? NST : 0;
       L = Ln;
-      stamp(6);
       continue;
     }
-    if (grp == 0 && ABL != 3) bar();  // every wave has passed the same number of barriers; nobody reads LDS any more
+    if (grp == 0) bar();  // every wave has passed the same number of barriers; nobody reads LDS any more
     em0 = m0;
     en0 = n0;
     ezs = zs;
@@ -369,12 +354,10 @@ __global__ void __launch_bounds__(512, 2) gemm_p8f_kernel(const GemmArgs g, cons
       prologue();
       __builtin_amdgcn_sched_barrier(0);
     }
-    stamp(5);
     epi_quadrant(IC<0>{}, IC<0>{});
     epi_quadrant(IC<0>{}, IC<1>{});
     epi_quadrant(IC<1>{}, IC<1>{});
     epi_quadrant(IC<1>{}, IC<0>{});
-    stamp(6);
     if (!has_next) break;
     if (!early) {
       setup(tile_of(Ln), m0, n0);
@@ -392,7 +375,7 @@ __global__ void __launch_bounds__(512, 2) gemm_p8f_kernel(const GemmArgs g, cons
       r_wait_vm<8>();
     }
     bar();
-    if (grp == 1 && ABL != 3) bar();
+    if (grp == 1) bar();
   }
 }
 
@@ -406,7 +389,6 @@ int launch_p8f(GemmArgs g, const float* sa, const float* sb, hipStream_t st) {
     return UWU_ELAUNCH;
   }
   const int units = g.tiles_m * g.tiles_n * (PART ? g.wide : 1), ncu = uwu_p8_cus();
-  g.p8_cont = 1;
   hipLaunchKernelGGL(kern, dim3(units < ncu ? units : ncu), dim3(512), P8_LDS, st, g, sa, sb);
   UWU_LAUNCH_CHECK("gemm_p8f");
   return UWU_OK;
@@ -415,17 +397,16 @@ int launch_p8f(GemmArgs g, const float* sa, const float* sb, hipStream_t st) {
 }  // namespace
 
 // fp8 in / bf16 out (forward, input gradient): K a multiple of 128, at least 4 K steps, enough tiles (an even number of K steps
-// runs as one continuous element stream across tiles, an odd one drains at every tile end).  UWU_GEMM_P8F=0: off, =1: every shape it can run (tests, A/B comparisons).
+// runs as one continuous element stream across tiles, an odd one drains at every tile end).  UWU_GEMM_P8F=0: off, =1: every
+// shape it can run (test_gemm_p8f_exact_on_integers_and_equal_to_the_two_stage_kernel).
 bool uwu_gemm_p8f_ok(const GemmArgs& g) {
-  static UwuEnv on("UWU_GEMM_P8F"), tmin_e("UWU_P8F_MINTILES");
+  static UwuEnv on("UWU_GEMM_P8F");
   if (on.get().is('0') || !uwu_dev_lds_fits(P8_LDS)) return false;
-  static UwuEnv odd("UWU_P8F_ODD");  // "0": only even K step counts (the continuous stream); odd ones drain at every tile end
-  if (g.K % 128 || g.K < 512 || (odd.get().is('0') && g.K % 256)) return false;
+  if (g.K % 128 || g.K < 512) return false;
   if (g.epi != UWU_EPI_NONE && g.epi != UWU_EPI_BIAS) return false;
   if (on.is('1')) return true;
   const int64_t tiles = (int64_t)((g.M + 255) / 256) * ((g.N + 255) / 256);
-  const int tmin = tmin_e.get().set ? tmin_e.ival : 160;
-  return tiles >= tmin;
+  return tiles >= 160;
 }
 
 int uwu_launch_gemm_p8f(GemmArgs g, int fmt_a, const float* sa, const float* sb, hipStream_t st) {
@@ -462,7 +443,7 @@ int uwu_gemm_p8f_split(int tiles, int steps) {
 }
 
 bool uwu_gemm_p8f_part_ok(const GemmArgs& g) {
-  static UwuEnv on("UWU_GEMM_P8F_PART");
+  static UwuEnv on("UWU_GEMM_P8F_PART");  // "0": off (test_gemm_p8f_weight_gradient_slices)
   if (on.get().is('0') || !uwu_dev_lds_fits(P8_LDS) || g.K % 128) return false;
   const int tiles = ((g.M + 255) / 256) * ((g.N + 255) / 256);
   return uwu_gemm_p8f_split(tiles, g.K / 128) > 0;

@@ -21,6 +21,8 @@
 //     loads (plain / bias / bias + GELU; K-major W: plain) -- other cases stay on the older kernels.
 #include "gemm_shared.h"
 
+int uwu_p8_cus();  // gemm_p8.hip
+
 namespace {
 
 constexpr int N8_HT = 128 * ROW_BYTES;  // a third of W: 128 rows x 128 B = 16 KB
@@ -43,8 +45,7 @@ __device__ __forceinline__ void n8_wait_vm() {
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
-// ABL (UWU_P8_ABL, plain forward): 1 = no output stores (timing only)
-template <typename TC, int EPI, bool TB, int FI, int ABL = 0>
+template <typename TC, int EPI, bool TB, int FI>
 __global__ void __launch_bounds__(512, 2) gemm_p8n_kernel(const GemmArgs g) {
   typedef N8<FI> G;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -210,25 +211,18 @@ __global__ void __launch_bounds__(512, 2) gemm_p8n_kernel(const GemmArgs g) {
   // epilogue of third y of tile (em0, en0); the accumulators are zero afterwards
   auto epi_third = [&](auto yc) __attribute__((always_inline)) {
     constexpr int y = decltype(yc)::value;
-    if constexpr (ABL == 1) {
-#pragma unroll
-      for (int i = 0; i < FI; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) asm volatile("" ::"v"(acc[y][i][j]));
+    const int m_q = em0 + 16 * FI * grp, n_q = en0 + 128 * y + 32 * wc;
+    EpiPre<T, FI, 2> pre;
+    if constexpr (has_bias) {
+      const uint4 b0 = r_read128<128 * y>(bias_ad), b1 = r_read128<128 * y + 64>(bias_ad);
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_sched_barrier(0);
+      pre.bias[0] = *reinterpret_cast<const f32x4*>(&b0);
+      pre.bias[1] = *reinterpret_cast<const f32x4*>(&b1);
     } else {
-      const int m_q = em0 + 16 * FI * grp, n_q = en0 + 128 * y + 32 * wc;
-      EpiPre<T, FI, 2> pre;
-      if constexpr (has_bias) {
-        const uint4 b0 = r_read128<128 * y>(bias_ad), b1 = r_read128<128 * y + 64>(bias_ad);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
-        pre.bias[0] = *reinterpret_cast<const f32x4*>(&b0);
-        pre.bias[1] = *reinterpret_cast<const f32x4*>(&b1);
-      } else {
-        pre.bias[0] = pre.bias[1] = f32x4{0.f, 0.f, 0.f, 0.f};
-      }
-      epilogue_tile<T, TC, FI, 2, EPI>(acc[y], pre, g, m_q, n_q, fr, fq, nullptr, 0, 0, -1, nullptr);
+      pre.bias[0] = pre.bias[1] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
+    epilogue_tile<T, TC, FI, 2, EPI>(acc[y], pre, g, m_q, n_q, fr, fq, nullptr, 0, 0, -1, nullptr);
 #pragma unroll
     for (int i = 0; i < FI; ++i)
 #pragma unroll
@@ -254,7 +248,7 @@ __global__ void __launch_bounds__(512, 2) gemm_p8n_kernel(const GemmArgs g) {
     const bool ep = par == 0 && t == 0 && pending;
     // stores of the previous tile that may stay in flight at the waits of this K step: all of them leave ahead of phase 0 of K step 0,
     // i.e. behind the requests the three waits of K step 0 and the first wait of K step 1 are for ((1, B2) is the first younger one)
-    const int sf = (pending && pfull && ABL != 1) ? 1 : 0;
+    const int sf = (pending && pfull) ? 1 : 0;
     const int st0 = sf * (t <= 1 ? 3 : 0), st1 = sf * (t == 0 ? 3 : 0), st2 = st1;
     // phase 0: third 0
     if (ep) {  // every fragment register is free here (ahead of phases 1 and 2 the A fragments are live: the 192-row form spilled)
@@ -338,16 +332,9 @@ __global__ void __launch_bounds__(512, 2) gemm_p8n_kernel(const GemmArgs g) {
   epi_third(IC<2>{});
 }
 
-int p8n_cus() {
-  static UwuEnv ge("UWU_P8_GRID");
-  if (ge.get().set && ge.ival >= 8) return ge.ival & ~7;
-  const int cus = uwu_dev_cus();
-  return cus >= 8 ? cus & ~7 : 256;
-}
-
-template <typename TC, int EPI, bool TB, int FI, int ABL = 0>
+template <typename TC, int EPI, bool TB, int FI>
 int launch_p8n_fi(GemmArgs g, hipStream_t st) {
-  auto kern = gemm_p8n_kernel<TC, EPI, TB, FI, ABL>;
+  auto kern = gemm_p8n_kernel<TC, EPI, TB, FI>;
   static unsigned char done[UWU_MAX_DEV];
   if (!uwu_func_lds(reinterpret_cast<const void*>(kern), N8<FI>::LDS, done)) {
     uwu_set_error("gemm_p8n: the device cannot give a workgroup %d bytes of LDS", N8<FI>::LDS);
@@ -355,7 +342,7 @@ int launch_p8n_fi(GemmArgs g, hipStream_t st) {
   }
   g.tiles_m = (g.M + 32 * FI - 1) / (32 * FI);
   g.tiles_n = g.N / 384;
-  const int nblk = g.tiles_m * g.tiles_n, ncu = p8n_cus();
+  const int nblk = g.tiles_m * g.tiles_n, ncu = uwu_p8_cus();
   UwuProfScope prof(st);
   hipLaunchKernelGGL(kern, dim3(nblk < ncu ? nblk : ncu), dim3(512), N8<FI>::LDS, st, g);
   prof.done(gemm_tag(g, TB, false), 0, 2.0 * g.M * g.N * g.K, gemm_bytes(g, 2, sizeof(TC)));
@@ -363,20 +350,19 @@ int launch_p8n_fi(GemmArgs g, hipStream_t st) {
   return UWU_OK;
 }
 
-// 192-row tiles unless UWU_P8N_ROWS=128 (A/B comparisons) or the 128-row grid fills the chip and the 192-row one does not
-template <typename TC, int EPI, bool TB, int ABL = 0>
+// 192-row tiles unless the 128-row grid fills the chip and the 192-row one does not
+template <typename TC, int EPI, bool TB>
 int launch_p8n(const GemmArgs& g, hipStream_t st) {
-  static UwuEnv rows("UWU_P8N_ROWS");
   const int64_t t192 = (int64_t)((g.M + 191) / 192) * (g.N / 384);
   // (the two-output GELU form of the 192-row kernel spills inside the K loop: 128 rows)
-  const bool small = g.M % 192 != 0 || EPI == UWU_EPI_BIAS_GELU || (rows.get().set ? rows.ival == 128 : t192 < p8n_cus());
-  return small ? launch_p8n_fi<TC, EPI, TB, 4, ABL>(g, st) : launch_p8n_fi<TC, EPI, TB, 6, ABL>(g, st);
+  const bool small = g.M % 192 != 0 || EPI == UWU_EPI_BIAS_GELU || t192 < uwu_p8_cus();
+  return small ? launch_p8n_fi<TC, EPI, TB, 4>(g, st) : launch_p8n_fi<TC, EPI, TB, 6>(g, st);
 }
 
 }  // namespace
 
 // bf16 in / bf16 out, N a multiple of 384, an even number >= 4 of 64-deep K steps, 16-byte addressable operands.
-// UWU_GEMM_P8N=0: off, =1: every shape it can run (tests, A/B comparisons); default: at least one tile per CU.
+// UWU_GEMM_P8N=0: off, =1: every shape it can run (test_gemm_p8n_exact_integers); default: at least one tile per CU.
 bool uwu_gemm_p8n_ok(const GemmArgs& g, bool tb) {
   static UwuEnv on("UWU_GEMM_P8N");
   if (on.get().is('0') || !uwu_dev_lds_fits(N8<6>::LDS)) return false;
@@ -393,11 +379,7 @@ bool uwu_gemm_p8n_ok(const GemmArgs& g, bool tb) {
 
 int uwu_launch_gemm_p8n(const GemmArgs& g, bool tb, hipStream_t st) {
   if (!tb) {
-    if (g.epi == UWU_EPI_NONE) {
-      static UwuEnv abl("UWU_P8_ABL");
-      if (abl.get().set && abl.ival == 1) return launch_p8n<bf16_t, UWU_EPI_NONE, false, 1>(g, st);
-      return launch_p8n<bf16_t, UWU_EPI_NONE, false>(g, st);
-    }
+    if (g.epi == UWU_EPI_NONE) return launch_p8n<bf16_t, UWU_EPI_NONE, false>(g, st);
     if (g.epi == UWU_EPI_BIAS) return launch_p8n<bf16_t, UWU_EPI_BIAS, false>(g, st);
     if (g.epi == UWU_EPI_BIAS_GELU) return launch_p8n<bf16_t, UWU_EPI_BIAS_GELU, false>(g, st);
   } else if (g.epi == UWU_EPI_NONE) {

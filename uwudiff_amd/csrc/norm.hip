@@ -638,19 +638,16 @@ extern "C" int uwu_add_ln_modulate_fwd_q8(const void* x_in, const void* y, const
   UWU_CHECK_ARG(ldq >= D && ldq % 8 == 0 && ldqt >= M && ldqt % 16 == 0, "add_ln_modulate_fwd_q8: bad leading dimension");
   hipStream_t st = (hipStream_t)stream;
   // tile = 8 rows per wave: 8 waves (64-byte runs of the transposed image) while two such workgroups fit a CU's LDS, else 4
-  static UwuEnv nw_e("UWU_LN_Q8_NW");
-  int nw = (size_t)64 * (D + 8) * 2 <= 150 * 1024 ? 8 : 4;
-  if (nw_e.get().set && (nw_e.get().ival == 4 || nw_e.get().ival == 8)) nw = nw_e.get().ival;
+  const int nw = (size_t)64 * (D + 8) * 2 <= 150 * 1024 ? 8 : 4;
   UWU_CHECK_ARG(M % (8 * nw) == 0, "add_ln_modulate_fwd_q8: B*T must be a multiple of %d", 8 * nw);
   const size_t lds = (size_t)8 * nw * (D + 8);
   UwuProfScope prof(stream);
 #define Q8_LAUNCH(NIT, NW)                                                                                                 \
   {                                                                                                                        \
-    static bool done = false;                                                                                              \
-    if (!done) {                                                                                                           \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(add_ln_mod_fwd_q8_kernel<NIT, NW>),                         \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 8 * NW * (1536 + 8));                          \
-      done = true;                                                                                                         \
+    static unsigned char done[UWU_MAX_DEV];                                                                                \
+    if (!uwu_func_lds(reinterpret_cast<const void*>(add_ln_mod_fwd_q8_kernel<NIT, NW>), 8 * NW * (1536 + 8), done)) {    \
+      uwu_set_error("add_ln_modulate_fwd_q8: the device cannot give a workgroup %d bytes of LDS", 8 * NW * (1536 + 8));   \
+      return UWU_ELAUNCH;                                                                                                  \
     }                                                                                                                      \
     hipLaunchKernelGGL((add_ln_mod_fwd_q8_kernel<NIT, NW>), dim3(M / (8 * NW)), dim3(64 * NW), lds, st,                   \
                        (const bf16_t*)x_in, (const bf16_t*)y, gate, shift, scale, mod_ld, (bf16_t*)x_out,                 \
@@ -685,7 +682,8 @@ extern "C" int uwu_add_ln_modulate_fwd(const void* x_in, const void* y, const fl
   hipStream_t st = (hipStream_t)stream;
   UWU_CHECK_ARG(dtype == UWU_F32 || dtype == UWU_BF16, "add_ln_modulate_fwd: bad dtype");
   UwuProfScope prof(stream);
-  static UwuEnv r16("UWU_LN_ROW16");  // "0": the one-row-per-wave kernel at every width (A/B comparisons)
+  // "0": the one-row-per-wave kernel at every width (test_add_ln_modulate_fwd_four_rows_per_wave)
+  static UwuEnv r16("UWU_LN_ROW16");
   const bool al16 = (((uintptr_t)x_in | (uintptr_t)h | (uintptr_t)y | (uintptr_t)x_out) & 15) == 0 && (mod_ld % 4 == 0);
   // (up to D = 768: 126 registers, 4 waves per SIMD; at D = 1152 its 174 registers left 2 waves per SIMD and it ran at 3.6 TB/s
   //  against the one-row-per-wave kernel's 4.7 -- UWU_LN_ROW16=1 forces it up to D = 1536)
@@ -735,11 +733,6 @@ extern "C" int uwu_add_ln_modulate_fwd(const void* x_in, const void* y, const fl
   return UWU_OK;
 }
 
-static bool small_ln_on() {  // UWU_LN_SMALL=0: the 4-wave kernel at every size (A/B comparisons)
-  static UwuEnv on("UWU_LN_SMALL");
-  return !on.get().is('0');
-}
-
 extern "C" int uwu_add_ln_modulate_bwd(const void* dh, const void* x, const float* mean, const float* rstd,
                                        const float* scale, const void* dx_in, const void* y, const float* gate,
                                        int mod_ld, void* dx_out, void* dy, float* dshift, float* dscale, float* dgate,
@@ -752,33 +745,25 @@ extern "C" int uwu_add_ln_modulate_bwd(const void* dh, const void* x, const floa
   const int M = B * T;
   hipStream_t st = (hipStream_t)stream;
   UWU_CHECK_ARG(dtype == UWU_F32 || dtype == UWU_BF16, "add_ln_modulate_bwd: bad dtype");
-  static UwuEnv aff_e("UWU_LN_AFFINE");  // UWU_LN_AFFINE=0: the per-sample kernel for every case (A/B comparisons)
-  const bool aff_on = !aff_e.get().is('0');
-  if (aff_on && affine && mod_ld == 0 && scale && !y && dshift && dscale && D <= 2048 && (dx_in == nullptr || ((uintptr_t)dx_in & 15) == 0)) {
+  if (affine && mod_ld == 0 && scale && !y && dshift && dscale && D <= 2048 && (dx_in == nullptr || ((uintptr_t)dx_in & 15) == 0)) {
     // one weight / bias vector for every row: 8-wave workgroups, LDS-folded column sums
-    int rpb = M >= 16384 ? 64 : (M >= 4096 ? 32 : 16);
-    {
-      static UwuEnv rows_e("UWU_LN_ROWS");
-      const int forced = rows_e.get().set ? rows_e.ival : 0;
-      if (forced > 0) rpb = forced;
-    }
+    const int rpb = M >= 16384 ? 64 : (M >= 4096 ? 32 : 16);
     const int grid = (M + rpb - 1) / rpb;
     const size_t lds2 = (size_t)8 * 2 * D * sizeof(float);
     if (lds2 > 64 * 1024) {
-      static bool done_f = false, done_b = false;
-      bool& done = dtype == UWU_F32 ? done_f : done_b;
-      if (!done) {
-        for (int nit = 1; nit <= 4; ++nit) {
-          const void* kf = nullptr;
-          if (dtype == UWU_F32)
-            kf = nit == 1 ? (const void*)ln_affine_bwd_kernel<float, 1> : nit == 2 ? (const void*)ln_affine_bwd_kernel<float, 2>
-                 : nit == 3 ? (const void*)ln_affine_bwd_kernel<float, 3> : (const void*)ln_affine_bwd_kernel<float, 4>;
-          else
-            kf = nit == 1 ? (const void*)ln_affine_bwd_kernel<bf16_t, 1> : nit == 2 ? (const void*)ln_affine_bwd_kernel<bf16_t, 2>
-                 : nit == 3 ? (const void*)ln_affine_bwd_kernel<bf16_t, 3> : (const void*)ln_affine_bwd_kernel<bf16_t, 4>;
-          (void)hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+      static unsigned char done[2][4][UWU_MAX_DEV];
+      for (int nit = 1; nit <= 4; ++nit) {
+        const void* kf = nullptr;
+        if (dtype == UWU_F32)
+          kf = nit == 1 ? (const void*)ln_affine_bwd_kernel<float, 1> : nit == 2 ? (const void*)ln_affine_bwd_kernel<float, 2>
+               : nit == 3 ? (const void*)ln_affine_bwd_kernel<float, 3> : (const void*)ln_affine_bwd_kernel<float, 4>;
+        else
+          kf = nit == 1 ? (const void*)ln_affine_bwd_kernel<bf16_t, 1> : nit == 2 ? (const void*)ln_affine_bwd_kernel<bf16_t, 2>
+               : nit == 3 ? (const void*)ln_affine_bwd_kernel<bf16_t, 3> : (const void*)ln_affine_bwd_kernel<bf16_t, 4>;
+        if (!uwu_func_lds(kf, 160 * 1024, done[dtype == UWU_F32][nit - 1])) {
+          uwu_set_error("ln_affine_bwd: the device cannot give a workgroup %d bytes of LDS", 160 * 1024);
+          return UWU_ELAUNCH;
         }
-        done = true;
       }
     }
     UwuProfScope prof(stream);
@@ -808,14 +793,9 @@ extern "C" int uwu_add_ln_modulate_bwd(const void* dh, const void* x, const floa
   // M = 4096 the 128 workgroups of 32 rows took 18.5 us, most of it eight dependent row passes per wave
   // ... but every workgroup adds its column sums to the sample's 3 D floats: at M = 4096 the 1024 workgroups of 4 rows issued
   // 1.2 M global atomics (13 us for 19 MB).  Small batches: 8 waves x 2 rows per workgroup, a quarter of the atomics.
-  const bool small = M / rows < 1024 && T % 16 == 0 && D <= 640 && small_ln_on();  // (8 x 3 x D floats of LDS <= 64 KB)
+  const bool small = M / rows < 1024 && T % 16 == 0 && D <= 640;  // (8 x 3 x D floats of LDS <= 64 KB)
   if (small) rows = 16;
   while (!small && rows > 4 && M / rows < 1024) rows >>= 1;
-  {
-    static UwuEnv rows_e("UWU_LN_ROWS");
-    const int forced = rows_e.get().set ? rows_e.ival : 0;
-    if (forced > 0 && T % forced == 0) rows = forced;
-  }
   const size_t lds = (size_t)(small ? 8 : (D > 1024 ? 1 : 4)) * 3 * D * sizeof(float);  // (D > 1024: MAX_IT >= 3, one slab)
   if (small) {
     UwuProfScope prof(stream);
@@ -838,14 +818,13 @@ extern "C" int uwu_add_ln_modulate_bwd(const void* dh, const void* x, const floa
   UwuProfScope prof(stream);
 #define BWD_CASE(NIT)                                                                                               \
   case NIT:                                                                                                         \
-    if (lds > 64 * 1024) { /* above the default dynamic-LDS limit: raise it once per instantiation */              \
-      static bool done_f = false, done_b = false;                                                                   \
-      bool& done = dtype == UWU_F32 ? done_f : done_b;                                                              \
-      if (!done) {                                                                                                  \
-        const void* kf = dtype == UWU_F32 ? reinterpret_cast<const void*>(add_ln_mod_bwd_kernel<float, NIT>)        \
-                                          : reinterpret_cast<const void*>(add_ln_mod_bwd_kernel<bf16_t, NIT>);      \
-        (void)hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);                      \
-        done = true;                                                                                                \
+    if (lds > 64 * 1024) { /* above the default dynamic-LDS limit: raise it once per device */                     \
+      static unsigned char done[2][UWU_MAX_DEV];                                                                    \
+      const void* kf = dtype == UWU_F32 ? reinterpret_cast<const void*>(add_ln_mod_bwd_kernel<float, NIT>)          \
+                                        : reinterpret_cast<const void*>(add_ln_mod_bwd_kernel<bf16_t, NIT>);        \
+      if (!uwu_func_lds(kf, 160 * 1024, done[dtype == UWU_F32])) {                                                  \
+        uwu_set_error("add_ln_modulate_bwd: the device cannot give a workgroup %d bytes of LDS", 160 * 1024);       \
+        return UWU_ELAUNCH;                                                                                         \
       }                                                                                                             \
     }                                                                                                               \
     if (dtype == UWU_F32)                                                                                           \

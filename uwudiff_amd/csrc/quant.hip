@@ -169,9 +169,8 @@ extern "C" int uwu_fp8_amax(const void* x, int dtype, int64_t n, float* amax, vo
   UWU_CHECK_ARG(dtype == UWU_F32 || dtype == UWU_BF16, "fp8_amax: bad dtype");
   UWU_CHECK_ARG(((uintptr_t)x & 15) == 0, "fp8_amax: x must be 16-byte aligned");
   int grid = ew_grid((n + 7) / 8, 256);
-  static UwuEnv wide("UWU_FP8_AMAX_WIDE");  // "1": the uncapped grid (A/B)
   const int cap = 2 * (uwu_dev_cus() > 0 ? uwu_dev_cus() : 256);
-  if (grid > cap && !wide.get().is('1')) grid = cap;
+  if (grid > cap) grid = cap;
   hipStream_t st = (hipStream_t)stream;
   if (dtype == UWU_F32) hipLaunchKernelGGL((amax_kernel<float>), dim3(grid), dim3(256), 0, st, (const float*)x, n, amax);
   else hipLaunchKernelGGL((amax_kernel<bf16_t>), dim3(grid), dim3(256), 0, st, (const bf16_t*)x, n, amax);

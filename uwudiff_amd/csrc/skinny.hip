@@ -138,13 +138,13 @@ __global__ void __launch_bounds__(256) skinny_wgrad_kernel(const float* __restri
   }
 }
 
-// (one call per kernel instantiation: every use site carries its own flag)
+// (one call per kernel instantiation: every use site carries its own per-device flags)
 #define SK_ALLOW_LDS(kern)                                                                                                  \
   do {                                                                                                                      \
-    static bool done_ = false;                                                                                              \
-    if (!done_) {                                                                                                           \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, SK_MAX_LDS); \
-      done_ = true;                                                                                                         \
+    static unsigned char done_[UWU_MAX_DEV];                                                                                \
+    if (!uwu_func_lds(reinterpret_cast<const void*>(kern), SK_MAX_LDS, done_)) {                                           \
+      uwu_set_error("skinny_linear: the device cannot give a workgroup %d bytes of LDS", SK_MAX_LDS);                      \
+      return UWU_ELAUNCH;                                                                                                   \
     }                                                                                                                       \
   } while (0)
 

@@ -144,9 +144,6 @@ def _wgrad_blocks(M, N, K):
     return 768 if tiles >= 16 else 256
 
 
-_SKINNY = os.environ.get("UWU_UNET_SKINNY", "1") != "0"  # A/B switch: the generic fp32 GEMM for the few-row Linears
-
-
 class _LinearFn(torch.autograd.Function):
     """y = x W^T (+ b); W is a [N, K] view of the flat parameters, grads accumulate into the flat grad buffer."""
 
@@ -158,7 +155,7 @@ class _LinearFn(torch.autograd.Function):
         b = P.w32(bname) if bname else None
         # fp32 Linears on a handful of rows (time / text-time embedding MLPs, the resblocks' time_emb_proj: M = batch): the
         # matrix-vector kernels of the conditioning path (csrc/skinny.hip) instead of a 128-row MFMA tile with 12 live rows
-        skinny = (fp32 and x.dtype == torch.float32 and x.is_contiguous() and x.shape[0] <= 64 and _SKINNY
+        skinny = (fp32 and x.dtype == torch.float32 and x.is_contiguous() and x.shape[0] <= 64
                   and ops.skinny_linear_ok(x.shape[0], W.shape[0], x.shape[1]))
         if skinny:
             y = ops.skinny_linear_fwd(x, W, b)
