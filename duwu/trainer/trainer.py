@@ -1,6 +1,7 @@
 """reference src/duwu/trainer/trainer.py: ``DMTrainer`` (constructor signature, ``training_step`` contract,
-``configure_optimizers``) without Lightning.  LyCORIS adapters and Lightning checkpoint fix-ups are out of scope.
+``configure_optimizers``, LyCORIS adapter training) without Lightning.  Lightning checkpoint fix-ups are out of scope.
 """
+import os
 from typing import Any
 
 import torch
@@ -42,6 +43,9 @@ class BaseTrainer(nn.Module):
         if opt_cls is optim.AdamW and all(p.is_cuda for p in params):
             opt_cls = FusedAdamW  # same update rule, one HIP launch over the flat buffer
         optimizer = opt_cls(params, lr=self.lr, **self.opt_config)
+        lyc = getattr(self, "lycoris_model", None)
+        if lyc is not None:  # every step changes the adapters: the UNet merges them again before its next forward
+            optimizer.register_step_post_hook(lambda opt, args, kwargs: lyc.mark_dirty())
         sched = self.lr_sch(optimizer, **self.lr_sch_config) if self.lr_sch is not None else None
         if self.use_warm_up:
             sched = GradualWarmupScheduler(optimizer, 1, self.warm_up_period, sched)
@@ -58,8 +62,6 @@ class DMTrainer(BaseTrainer):
         super().__init__(*args, name=name, lr=lr, optimizer=optimizer, opt_config=opt_config,
                          lr_scheduler=lr_scheduler, lr_scheduler_config=lr_scheduler_config, use_warm_up=use_warm_up,
                          warm_up_period=warm_up_period)
-        if lycoris_config is not None:
-            raise NotImplementedError("LyCORIS adapters are out of scope of the MI355X hot path")
         self.unet = load_any(model_config["unet"])
         self.te = load_any(model_config["te"]) if model_config.get("te") is not None else None
         # trainer.py:136,241-244: any frozen module with `.encode(x).latent_dist.sample()` (diffusers.AutoencoderKL needs
@@ -72,8 +74,22 @@ class DMTrainer(BaseTrainer):
         self.vae_std, self.vae_mean = vae_std, vae_mean or 0
         self.register_buffer("ema_loss", torch.tensor(0.0))
         self.ema_decay = 0.99
-        self.unet.requires_grad_(True).train()
-        self.train_params = self.unet.parameters()
+        # trainer.py:148-169: LyCORIS adapters (uwudiff_amd/adapters.py) on a frozen UNet; only the adapters train
+        if lycoris_config is not None:
+            from uwudiff_amd.adapters import LycorisNetwork
+
+            if not hasattr(self.unet, "attach_adapters"):
+                raise NotImplementedError(f"lycoris_config: adapters are implemented for the UNet, not for "
+                                          f"{type(self.unet).__name__}")
+            self.lycoris_model = LycorisNetwork(self.unet, lycoris_config)
+            self.lycoris_model.apply_to(self.unet)
+            self.lycoris_model.train()
+            self.unet.requires_grad_(False)
+            self.train_params = self.lycoris_model.parameters()
+        else:
+            self.lycoris_model = None
+            self.unet.requires_grad_(True).train()
+            self.train_params = self.unet.parameters()
         if loss_config is None:  # trainer.py:171-178: default = SDXL scheduler, epsilon objective
             from duwu.loss import DiffusionLoss
             from uwudiff_amd.scheduler import EulerDiscreteScheduler
@@ -116,3 +132,22 @@ class DMTrainer(BaseTrainer):
         with torch.no_grad():
             return self.loss(x, self.unet, encoder_hidden_states=ctx, encoder_attention_mask=attn_mask,
                              added_cond_kwargs=added_cond, cross_attention_kwargs=cross_attn_kwargs)
+
+    # trainer.py:184-187
+    def merge_lycoris(self):
+        """Fold the adapters into the UNet's base weights and detach them: a plain UNet remains (for sampling)."""
+        self.lycoris_model.restore()
+        self.lycoris_model.merge_to(self.unet)
+
+    # trainer.py:189-215 (no loggers here: <default_root_dir>/lycoris_weight/epoch=N.pt)
+    def on_train_epoch_end(self):
+        if self.lycoris_model is None:
+            return
+        trainer = self._trainer
+        epoch = trainer.current_epoch if trainer is not None else 0
+        if trainer is not None and getattr(trainer, "global_rank", 0) != 0:
+            return
+        root = getattr(trainer, "default_root_dir", None) or "."
+        d = os.path.join(root, "lycoris_weight")
+        os.makedirs(d, exist_ok=True)
+        torch.save(self.lycoris_model.state_dict(), os.path.join(d, f"epoch={epoch}.pt"))

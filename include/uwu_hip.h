@@ -175,6 +175,32 @@ int uwu_adamw_step(float* p, float* g, float* m, float* v, void* p_bf16, int64_t
 int uwu_cast_f32_to_bf16(const float* src, void* dst, int64_t n, void* stream);
 int uwu_cast_bf16_to_f32(const void* src, float* dst, int64_t n, void* stream);
 
+/* ------------------------------------------------------------------ LyCORIS adapters
+ * Segment table of uwu_adapter_merge: one row of 13 int64 per adapted tensor [rows, cols] (a norm vector: rows = 1):
+ *   kind, rows, cols, base_off, eff_off, shadow_off, pa, pb, pc, r, out_k, in_n, scale (fp32 bits in the low word)
+ * offsets in elements (base / eff / shadow: multiples of 64; eff_off / shadow_off < 0: no such output);
+ * pa / pb / pc index the adapter parameter buffer p:
+ *   UWU_ADAPTER_NORM           delta[e]   = p[pa + e]
+ *   UWU_ADAPTER_LORA           delta[i,j] = scale * sum_t up[i,t] down[t,j]            up = p+pa [rows, r], down = p+pb [r, cols]
+ *   UWU_ADAPTER_LOKR           delta      = scale * kron(w1, w2)                       w1 = p+pa [rows/out_k, cols/in_n], w2 = p+pb [out_k, in_n]
+ *   UWU_ADAPTER_LOKR_LOWRANK   as LOKR with w2 = w2_a w2_b                             w2_a = p+pb [out_k, r], w2_b = p+pc [r, in_n]
+ * uwu_adapter_merge writes W_eff = base + delta to eff (fp32) and / or shadow (bf16, rounded as uwu_cast_f32_to_bf16) in
+ * one launch of nblocks workgroups; blk_start [nseg + 1] = exclusive prefix sum of ceil(rows * cols / 4096) per row.
+ * r <= 128.  eff may alias base (merging into the base weights in place). */
+#define UWU_ADAPTER_NORM 0
+#define UWU_ADAPTER_LORA 1
+#define UWU_ADAPTER_LOKR 2
+#define UWU_ADAPTER_LOKR_LOWRANK 3
+int uwu_adapter_merge(const float* base, const float* p, const int64_t* table, const int64_t* blk_start, int nseg,
+                      int64_t nblocks, float* eff, void* shadow, void* stream);
+/* Adapter gradient of one adapted [N, K] weight from its fp32 weight gradient dw (row-major, overwritten form), ACCUMULATED
+ * into g (same offsets pa / pb / pc as in p); kinds LORA, LOKR, LOKR_LOWRANK as above.  Deterministic: dw is read once,
+ * workgroup partials go to ws and are summed in a fixed order (no float atomics).  ws_elems: floats of ws --
+ *   LORA:  ceil(K/256) N r + ceil(N/32) r K
+ *   LOKR*: out_l ceil(out_k in_n / 2048) in_m + out_l out_k in_n + 2 out_k in_n   (out_l = N/out_k, in_m = K/in_n) */
+int uwu_adapter_grad(const float* dw, int64_t N, int64_t K, int kind, const float* p, float* g, int64_t pa, int64_t pb,
+                     int64_t pc, int r, int out_k, int in_n, float scale, float* ws, int64_t ws_elems, void* stream);
+
 /* ------------------------------------------------------------------ gradient exchange (section 8e)
  * One RCCL communicator per rank (librccl resolved at run time), created once; uwu_allreduce_flat sums a slice of the
  * flat fp32 gradient buffer over the ranks in place on the caller's stream (reference: the bucketed all-reduce of
@@ -413,7 +439,7 @@ int uwu_add_pos(void* x, const float* pos, int B, int T, int D, int dtype, void*
 /* y = GroupNorm(x; G groups, eps, gamma, beta) [then SiLU if silu]; mean/rstd: fp32 [B*G]. */
 int uwu_groupnorm_fwd(const void* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd,
                       int B, int HW, int C, int G, float eps, int silu, int dtype, void* stream);
-/* dgamma/dbeta are accumulated (fp32 atomics).  ws: fp32 scratch of 2*B*G floats (per-group sums).
+/* dgamma/dbeta are accumulated (fp32 atomics); either may be NULL (a frozen norm).  ws: fp32 scratch of 2*B*G floats.
  * Both directions: C % 8 == 0, C <= 4096, 16-byte aligned tensors (whole-row vector accesses). */
 int uwu_groupnorm_bwd(const void* dy, const void* x, const float* mean, const float* rstd, const float* gamma,
                       const float* beta, void* dx, float* dgamma, float* dbeta, float* ws, int B, int HW, int C, int G,

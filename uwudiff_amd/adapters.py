@@ -1,0 +1,337 @@
+"""LyCORIS adapters (LoRA, LoKr, norm) on the flat UNet: configuration, layer matching, one flat adapter parameter.
+
+The reference trainer wraps the UNet with the ``lycoris`` library (reference src/duwu/trainer/trainer.py:148-169): a
+``config`` table (algo, dims, alpha, ...) and a ``preset`` table (which module classes / names are adapted).  The library
+is not a dependency of this build; the subset below is this project's contract:
+
+  * LoRA   dW = alpha / dim * up @ down                     down [dim, in] kaiming-uniform(a=sqrt 5), up [out, dim] zeros
+  * LoKr   dW = scale * kron(w1, w2)                         w1 [out_l, in_m] kaiming-uniform, w2 [out_k, in_n] zeros
+           (out_l, out_k) = factorization(out, factor), (in_m, in_n) = factorization(in, factor); w2 = w2_a @ w2_b
+           (w2_b the zero factor, scale alpha / dim) when not full_matrix and dim < max(out_k, in_n) / 2, else scale 1
+  * norm   gamma + w_norm, beta + b_norm                     both zeros
+
+so a freshly attached network leaves the model's output unchanged.  Every adapter tensor is a named view of ONE flat
+fp32 parameter (the fused AdamW and the gradient exchange work on it as on the UNet's flat buffer); the UNet merges them
+into its effective weights with one kernel launch (csrc/adapter.hip) and computes their gradients from the weight
+gradients of the adapted layers.  Matching runs on the UNet's name / shape registry only: a UNet built on the ``meta``
+device (no storage) is enough.
+"""
+import fnmatch
+import math
+import re
+
+import torch
+import torch.nn as nn
+
+CONFIG_DEFAULTS = dict(algo="lora", linear_dim=4, linear_alpha=1.0, factor=-1, full_matrix=False, train_norm=False,
+                       conv_dim=None, conv_alpha=None, use_tucker=False)
+PRESET_KEYS = ("target_module", "target_name", "enable_conv", "module_algo_map")
+ALGOS = ("lora", "lokr")
+KIND_NORM, KIND_LORA, KIND_LOKR, KIND_LOKR_LOWRANK = 0, 1, 2, 3  # UWU_ADAPTER_* of include/uwu_hip.h
+MAX_RANK = 128
+
+
+def factorization(dim, factor=-1):
+    """(m, n), m <= n, m * n = dim: (factor, dim / factor) when factor divides dim, else the largest divisor pair whose
+    smaller member does not exceed factor (factor < 0: no bound)."""
+    dim, factor = int(dim), int(factor)
+    if factor > 0 and dim % factor == 0:
+        m, n = factor, dim // factor
+        return (m, n) if m <= n else (n, m)
+    if factor < 0:
+        factor = dim
+    m, n = 1, dim
+    while m < n:
+        new_m = m + 1
+        while dim % new_m:
+            new_m += 1
+        if new_m > factor:
+            break
+        m, n = new_m, dim // new_m
+    return (m, n) if m <= n else (n, m)
+
+
+def load_config(cfg):
+    """A ``lycoris_config``: dict, or path of a TOML file (read with tomli).  Returns (config, preset), validated."""
+    if isinstance(cfg, (str, bytes)) or hasattr(cfg, "__fspath__"):
+        try:
+            import tomli as _toml
+        except ImportError:  # (the standard library's copy of the same parser)
+            import tomllib as _toml
+        with open(cfg, "rb") as f:
+            cfg = _toml.load(f)
+    if not isinstance(cfg, dict):
+        raise ValueError(f"lycoris_config must be a dict or a TOML path, got {type(cfg).__name__}")
+    extra = set(cfg) - {"config", "preset"}
+    if extra:
+        raise ValueError(f"lycoris_config: unknown table(s) {sorted(extra)} (known: config, preset)")
+    if "preset" not in cfg:
+        raise ValueError("lycoris_config needs a [preset] table (target_module / target_name)")
+    config = _check_algo_table(dict(cfg.get("config") or {}), "config")
+    config = {**CONFIG_DEFAULTS, **config}
+    preset = dict(cfg["preset"])
+    extra = set(preset) - set(PRESET_KEYS)
+    if extra:
+        raise ValueError(f"lycoris_config.preset: unknown key(s) {sorted(extra)} (known: {', '.join(PRESET_KEYS)})")
+    preset.setdefault("target_module", [])
+    preset.setdefault("target_name", [])
+    preset.setdefault("enable_conv", False)
+    amap = {}
+    for cls, table in dict(preset.get("module_algo_map") or {}).items():
+        if not isinstance(table, dict):
+            raise ValueError(f"lycoris_config.preset.module_algo_map.{cls} must be a table")
+        amap[cls] = _check_algo_table(dict(table), f"preset.module_algo_map.{cls}")
+    preset["module_algo_map"] = amap
+    for k in ("target_module", "target_name"):
+        if isinstance(preset[k], str) or not all(isinstance(v, str) for v in preset[k]):
+            raise ValueError(f"lycoris_config.preset.{k} must be a list of strings")
+    return config, preset
+
+
+def _check_algo_table(t, where):
+    extra = set(t) - set(CONFIG_DEFAULTS)
+    if extra:
+        raise ValueError(f"lycoris_config.{where}: unknown key(s) {sorted(extra)} (known: {', '.join(CONFIG_DEFAULTS)})")
+    if "algo" in t and t["algo"] not in ALGOS:
+        raise NotImplementedError(f"lycoris_config.{where}: algo {t['algo']!r} is not implemented (supported: "
+                                  f"{', '.join(ALGOS)})")
+    return t
+
+
+# ------------------------------------------------------------------------------------------ class names of the UNet names
+_CONTAINERS = [
+    (re.compile(r"^(down_blocks|up_blocks)\.\d+\.attentions\.\d+$|^mid_block\.attentions\.\d+$"), "Transformer2DModel"),
+    (re.compile(r"\.transformer_blocks\.\d+$"), "BasicTransformerBlock"),
+    (re.compile(r"\.attn[12]$"), "Attention"),
+    (re.compile(r"\.ff$"), "FeedForward"),
+    (re.compile(r"\.ff\.net\.0$"), "GEGLU"),
+    (re.compile(r"\.resnets\.\d+$"), "ResnetBlock2D"),
+    (re.compile(r"\.downsamplers\.0$"), "Downsample2D"),
+    (re.compile(r"\.upsamplers\.0$"), "Upsample2D"),
+    (re.compile(r"^(time_embedding|add_embedding)$"), "TimestepEmbedding"),
+    (re.compile(r"^mid_block$"), "UNetMidBlock2DCrossAttn"),
+]
+
+
+def module_classes(unet):
+    """{module name: diffusers class name} for every layer of the flat UNet and every module containing one."""
+    kinds = getattr(unet, "module_kinds", None)
+    if kinds is None:
+        raise NotImplementedError(f"LyCORIS adapters are implemented for the UNet only, not for {type(unet).__name__}")
+    cfg = getattr(unet, "cfg_dict", {})
+    out = {"": "UNet2DConditionModel"}
+    for leaf, kind in kinds.items():
+        parts = leaf.split(".")
+        for i in range(1, len(parts)):
+            name = ".".join(parts[:i])
+            if name in out:
+                continue
+            cls = None
+            for rx, c in _CONTAINERS:
+                if rx.search(name):
+                    cls = c
+                    break
+            m = re.match(r"^(down|up)_blocks\.(\d+)$", name)
+            if m and cls is None:
+                cls = cfg.get(f"{m.group(1)}_block_types", [None] * 99)[int(m.group(2))]
+            out[name] = cls or "Module"
+        out[leaf] = kind
+    return out
+
+
+class Spec:
+    """One adapted layer: ``name`` (module), ``algo`` ('lora' / 'lokr' / 'norm'), ``shape`` ([out, in] or [C]), the
+    adapter tensors [(tensor name, shape)], and the factors the kernels need."""
+
+    def __init__(self, name, algo, shape, dim=0, alpha=1.0, factor=-1, full_matrix=False):
+        self.name, self.algo, self.shape = name, algo, tuple(shape)
+        self.dim, self.alpha, self.r, self.out_k, self.in_n, self.lowrank = 0, None, 0, 0, 0, False
+        if algo == "norm":
+            self.tensors = [("w_norm", self.shape), ("b_norm", self.shape)]
+            self.scale = 1.0
+            return
+        out, inn = self.shape
+        dim = int(dim)
+        if dim < 1:
+            raise ValueError(f"{name}: linear_dim must be >= 1")
+        self.dim, self.alpha = dim, float(alpha)
+        if algo == "lora":
+            if dim > MAX_RANK:
+                raise ValueError(f"{name}: LoRA dim {dim} > {MAX_RANK}")
+            self.r, self.scale = dim, self.alpha / dim
+            self.tensors = [("lora_down.weight", (dim, inn)), ("lora_up.weight", (out, dim))]
+            return
+        out_l, out_k = factorization(out, factor)
+        in_m, in_n = factorization(inn, factor)
+        self.out_k, self.in_n = out_k, in_n
+        self.tensors = [("lokr_w1", (out_l, in_m))]
+        if not full_matrix and dim < max(out_k, in_n) / 2:
+            if dim > MAX_RANK:
+                raise ValueError(f"{name}: LoKr dim {dim} > {MAX_RANK}")
+            self.lowrank, self.r, self.scale = True, dim, self.alpha / dim
+            self.tensors += [("lokr_w2_a", (out_k, dim)), ("lokr_w2_b", (dim, in_n))]
+        else:
+            self.scale = 1.0
+            self.tensors += [("lokr_w2", (out_k, in_n))]
+
+    @property
+    def key(self):
+        return "lycoris_" + self.name.replace(".", "_")
+
+    @property
+    def numel(self):
+        return sum(math.prod(s) for _, s in self.tensors)
+
+    def __repr__(self):
+        return f"Spec({self.name!r}, {self.algo!r}, {self.shape}, tensors={self.tensors})"
+
+
+def match_layers(unet, lycoris_config):
+    """The adapted layers of ``unet`` under ``lycoris_config`` (dict / TOML path / (config, preset)), in registry order.
+
+    A Linear takes the algo (and settings) of its nearest ancestor listed in ``module_algo_map``; otherwise the
+    ``config`` algo, if an ancestor's class is in ``target_module`` or its name matches ``target_name``.  With
+    ``train_norm`` every LayerNorm / GroupNorm inside a target gets a norm adapter.  3x3 convolutions inside a target:
+    skipped, or NotImplementedError with ``enable_conv``."""
+    config, preset = lycoris_config if isinstance(lycoris_config, tuple) else load_config(lycoris_config)
+    classes = module_classes(unet)
+    tmod, tname, amap = set(preset["target_module"]), list(preset["target_name"]), preset["module_algo_map"]
+    registry = unet.P.registry
+    specs = []
+    for leaf, kind in unet.module_kinds.items():
+        parts = leaf.split(".")
+        chain = [".".join(parts[:i]) for i in range(len(parts) + 1)]  # "", ..., leaf
+        over = None
+        for n in reversed(chain):
+            if classes[n] in amap:
+                over = amap[classes[n]]
+                break
+        targeted = over is not None or any(classes[n] in tmod for n in chain) or any(
+            fnmatch.fnmatchcase(n, pat) for n in chain if n for pat in tname)
+        if not targeted:
+            continue
+        cfg = {**config, **(over or {})}
+        if kind == "Linear":
+            specs.append(Spec(leaf, cfg["algo"], registry[leaf + ".weight"][1], dim=cfg["linear_dim"],
+                              alpha=cfg["linear_alpha"], factor=cfg["factor"], full_matrix=cfg["full_matrix"]))
+        elif kind in ("LayerNorm", "GroupNorm"):
+            if cfg["train_norm"]:
+                specs.append(Spec(leaf, "norm", registry[leaf + ".weight"][1]))
+        elif kind == "Conv2d":
+            if preset["enable_conv"]:
+                raise NotImplementedError(f"lycoris_config: enable_conv reaches the 3x3 convolution {leaf!r}; "
+                                          "convolution adapters are not implemented")
+    if not specs:
+        raise ValueError("lycoris_config matches no layer of the UNet")
+    order = {n: i for i, n in enumerate(registry)}
+    specs.sort(key=lambda s: order[s.name + ".weight"])
+    return specs
+
+
+def grad_ws_elems(spec, N, K):
+    """floats of uwu_adapter_grad's workspace (include/uwu_hip.h)"""
+    if spec.algo == "lora":
+        return -(-K // 256) * N * spec.r + -(-N // 32) * spec.r * K
+    out_l, in_m, W2 = N // spec.out_k, K // spec.in_n, spec.out_k * spec.in_n
+    return out_l * -(-W2 // 2048) * in_m + out_l * W2 + 2 * W2
+
+
+class LycorisNetwork(nn.Module):
+    """The adapters of one UNet: ``flat`` (one fp32 parameter) with every adapter tensor as a named view.
+
+    ``apply_to(unet)`` makes the UNet run with W + dW (merged by the UNet before its next forward whenever the adapters
+    changed), ``restore()`` detaches them again, ``merge_to()`` folds dW into the UNet's base weights."""
+
+    def __init__(self, unet, lycoris_config, device=None):
+        super().__init__()
+        self.specs = match_layers(unet, lycoris_config)
+        self.offsets = {}  # (spec name, tensor name) -> (offset, shape)
+        n = 0
+        for s in self.specs:
+            for t, shape in s.tensors:
+                self.offsets[(s.name, t)] = (n, shape)
+                n += (math.prod(shape) + 63) // 64 * 64
+        self.n = n
+        if device is None:
+            device = unet.flat.device if unet.flat.device.type != "meta" else "cpu"
+        self.flat = nn.Parameter(torch.zeros(n, dtype=torch.float32, device=device))
+        self._dirty = True
+        self.reset_parameters()
+
+    # ------------------------------------------------------------------ views / init
+    def view(self, spec_name, tensor, buf=None):
+        off, shape = self.offsets[(spec_name, tensor)]
+        return (self.flat.data if buf is None else buf)[off:off + math.prod(shape)].view(shape)
+
+    @torch.no_grad()
+    def reset_parameters(self):
+        """kaiming_uniform(a=sqrt 5) on lora_down / lokr_w1 / lokr_w2_a (torch's default generator), zeros elsewhere:
+        dW = 0 and the adapted model computes what the bare one does."""
+        self.flat.data.zero_()
+        for s in self.specs:
+            for t, shape in s.tensors:
+                if t in ("lora_down.weight", "lokr_w1", "lokr_w2_a"):
+                    w = torch.empty(shape, dtype=torch.float32)
+                    nn.init.kaiming_uniform_(w, a=math.sqrt(5))
+                    self.view(s.name, t).copy_(w)
+        self.mark_dirty()
+
+    def mark_dirty(self):
+        """the adapter weights changed (optimizer step, load): the UNet merges again before its next forward"""
+        self._dirty = True
+
+    def num_adapter_params(self):
+        return sum(s.numel for s in self.specs)
+
+    # ------------------------------------------------------------------ state dict (lycoris_<name>.<tensor>)
+    def state_dict(self, *args, destination=None, prefix="", keep_vars=False):
+        sd = destination if destination is not None else {}
+        for s in self.specs:
+            for t, _ in s.tensors:
+                sd[f"{prefix}{s.key}.{t}"] = self.view(s.name, t).detach().clone()
+            if s.alpha is not None:
+                sd[f"{prefix}{s.key}.alpha"] = torch.tensor(s.alpha)
+        return sd
+
+    def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys,
+                              error_msgs):
+        mine = set()
+        with torch.no_grad():
+            for s in self.specs:
+                for t, shape in s.tensors:
+                    k = f"{prefix}{s.key}.{t}"
+                    mine.add(k)
+                    if k not in state_dict:
+                        missing_keys.append(k)
+                        continue
+                    v = state_dict[k]
+                    if tuple(v.shape) != tuple(shape):
+                        error_msgs.append(f"size mismatch for {k}: checkpoint {tuple(v.shape)}, adapter {tuple(shape)}")
+                        continue
+                    self.view(s.name, t).copy_(v.float())
+                if s.alpha is not None:
+                    k = f"{prefix}{s.key}.alpha"
+                    mine.add(k)
+                    if k in state_dict and abs(float(state_dict[k]) - s.alpha) > 1e-6 * max(1.0, abs(s.alpha)):
+                        error_msgs.append(f"{k}: checkpoint alpha {float(state_dict[k])} != configured {s.alpha}")
+        for k in state_dict:
+            if k.startswith(prefix) and k not in mine:
+                unexpected_keys.append(k)
+        self.mark_dirty()
+
+    # ------------------------------------------------------------------ attach / detach / fold
+    def apply_to(self, unet=None):
+        unet = unet if unet is not None else self._unet
+        object.__setattr__(self, "_unet", unet)  # (not a sub-module: the UNet's state dict stays the base weights)
+        unet.attach_adapters(self)
+        return self
+
+    def restore(self):
+        unet = self.__dict__.get("_unet")
+        if unet is not None:
+            unet.detach_adapters()
+
+    def merge_to(self, unet=None):
+        """W += dW in the UNet's flat fp32 weights (one uwu_adapter_merge launch) and detach: a plain UNet remains."""
+        unet = unet if unet is not None else self._unet
+        unet.fold_adapters(self)

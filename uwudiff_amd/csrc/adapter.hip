@@ -1,0 +1,308 @@
+// LyCORIS-style adapters on the frozen UNet: the merge of every adapted tensor into the
+// effective weights (one launch) and the adapter gradients of one layer from its fp32 weight gradient.
+//
+//   merge: W_eff = W + dW_adapter, written as fp32 (where an fp32 effective copy exists) and as bf16 (the GEMM shadow);
+//          one pass over the adapted elements, the factors come from L1 / L2.
+//   grad:  LoRA  d_up += s dW down^T, d_down += s up^T dW;  LoKr  dw1[i,j] += s <dW block (i,j), w2>,
+//          dw2 += s sum_ij w1[i,j] dW block (i,j) (through w2 = w2_a w2_b for the low-rank form).  dW is read once; the
+//          partial sums of the workgroups go to a workspace and a second launch adds them in a fixed order: no float
+//          atomics, the result is bit-identical run to run.
+#include "common.h"
+
+namespace {
+
+constexpr int AD_NF = 13;  // int64 fields per segment row (see uwu_hip.h)
+constexpr int AD_MERGE_ELEMS = 4096;  // elements per workgroup: 256 threads x 4 x 4
+constexpr int AD_MAX_RANK = 128;
+
+__device__ __forceinline__ float ad_delta(const int64_t* __restrict__ row, const float* __restrict__ p, int e) {
+  const int kind = (int)row[0];
+  const int cols = (int)row[2];
+  if (kind == UWU_ADAPTER_NORM) return p[row[6] + e];
+  const int i = e / cols, j = e - i * cols;
+  const float scale = __int_as_float((int)row[12]);
+  const int r = (int)row[9];
+  if (kind == UWU_ADAPTER_LORA) {
+    const float* up = p + row[6] + (int64_t)i * r;
+    const float* down = p + row[7] + j;
+    float acc = 0.f;
+    for (int t = 0; t < r; ++t) acc += up[t] * down[(int64_t)t * cols];
+    return acc * scale;
+  }
+  const int out_k = (int)row[10], in_n = (int)row[11], in_m = cols / in_n;
+  const int i1 = i / out_k, k = i - i1 * out_k, j1 = j / in_n, l = j - j1 * in_n;
+  const float w1 = p[row[6] + (int64_t)i1 * in_m + j1];
+  float w2;
+  if (kind == UWU_ADAPTER_LOKR) {
+    w2 = p[row[7] + (int64_t)k * in_n + l];
+  } else {  // low-rank w2 = w2_a [out_k, r] . w2_b [r, in_n], formed before the Kronecker product
+    const float* a = p + row[7] + (int64_t)k * r;
+    const float* b = p + row[8] + l;
+    w2 = 0.f;
+    for (int t = 0; t < r; ++t) w2 += a[t] * b[(int64_t)t * in_n];
+  }
+  return (w1 * w2) * scale;
+}
+
+__global__ void __launch_bounds__(256) adapter_merge_kernel(const float* __restrict__ base, const float* __restrict__ p,
+                                                            const int64_t* __restrict__ table,
+                                                            const int64_t* __restrict__ blk_start, int nseg,
+                                                            float* __restrict__ eff, bf16_t* __restrict__ shadow) {
+  // the segment of this workgroup: blk_start is the exclusive prefix sum of the workgroups per segment
+  const int64_t bid = blockIdx.x;
+  int lo = 0, hi = nseg;  // blk_start[lo] <= bid < blk_start[hi]
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (blk_start[mid] <= bid) lo = mid;
+    else hi = mid;
+  }
+  const int64_t* row = table + (int64_t)lo * AD_NF;
+  const int n = (int)(row[1] * row[2]);
+  const int64_t boff = row[3], eoff = row[4], soff = row[5];
+  const int e0 = (int)(bid - blk_start[lo]) * AD_MERGE_ELEMS;
+#pragma unroll
+  for (int it = 0; it < AD_MERGE_ELEMS / 1024; ++it) {
+    const int e = e0 + it * 1024 + 4 * threadIdx.x;
+    if (e >= n) break;
+    if (e + 4 <= n) {  // offsets are multiples of 64 elements: 16-byte aligned fp32, 8-byte aligned bf16
+      f32x4 v = load4(base + boff + e);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) v[q] += ad_delta(row, p, e + q);
+      if (eoff >= 0) store4(eff + eoff + e, v);
+      if (shadow && soff >= 0) store4(shadow + soff + e, v);
+    } else {
+      for (int q = e; q < n; ++q) {
+        const float v = base[boff + q] + ad_delta(row, p, q);
+        if (eoff >= 0) eff[eoff + q] = v;
+        if (shadow && soff >= 0) shadow[soff + q] = (bf16_t)v;
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------- LoRA
+constexpr int LR_RT = 32, LR_CT = 256;  // dW tile of one workgroup: 32 rows x 256 columns, staged in LDS
+
+// partials: du_part[ct][n][r] = sum_{c in tile ct} dW[n,c] down[t,c];  dd_part[rt][t][k] = sum_{i in tile rt} up[i,t] dW[i,k]
+__global__ void __launch_bounds__(256) lora_grad_partial_kernel(const float* __restrict__ dw, int N, int K,
+                                                                const float* __restrict__ up,
+                                                                const float* __restrict__ down, int r,
+                                                                float* __restrict__ du_part,
+                                                                float* __restrict__ dd_part) {
+  __shared__ float tile[LR_RT][LR_CT + 1];
+  const int ct = blockIdx.x, rt = blockIdx.y, tid = threadIdx.x;
+  const int i0 = rt * LR_RT, j0 = ct * LR_CT;
+  const int nr = min(LR_RT, N - i0), nc = min(LR_CT, K - j0);
+  for (int i = 0; i < LR_RT; ++i) tile[i][tid] = (i < nr && tid < nc) ? dw[(int64_t)(i0 + i) * K + j0 + tid] : 0.f;
+  __syncthreads();
+  if (tid < nc) {
+    for (int t = 0; t < r; ++t) {
+      float acc = 0.f;
+      for (int i = 0; i < nr; ++i) acc += up[(int64_t)(i0 + i) * r + t] * tile[i][tid];
+      dd_part[((int64_t)rt * r + t) * K + j0 + tid] = acc;
+    }
+  }
+  for (int o = tid; o < nr * r; o += 256) {
+    const int i = o / r, t = o - i * r;
+    const float* dn = down + (int64_t)t * K + j0;
+    float acc = 0.f;
+    for (int c = 0; c < nc; ++c) acc += tile[i][c] * dn[c];
+    du_part[((int64_t)ct * N + i0 + i) * r + t] = acc;
+  }
+}
+
+__global__ void __launch_bounds__(256) lora_grad_reduce_kernel(const float* __restrict__ du_part,
+                                                               const float* __restrict__ dd_part, int N, int K, int r,
+                                                               int nct, int nrt, float scale, float* __restrict__ gu,
+                                                               float* __restrict__ gd) {
+  const int64_t o = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t nu = (int64_t)N * r, nd = (int64_t)r * K;
+  if (o < nu) {
+    float acc = 0.f;
+    for (int c = 0; c < nct; ++c) acc += du_part[(int64_t)c * nu + o];
+    gu[o] += scale * acc;
+  } else if (o < nu + nd) {
+    const int64_t q = o - nu;
+    float acc = 0.f;
+    for (int c = 0; c < nrt; ++c) acc += dd_part[(int64_t)c * nd + q];
+    gd[q] += scale * acc;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------- LoKr
+constexpr int LK_GROUP = 2048;  // w2 elements per workgroup (8 per thread)
+
+// w2 = w2_a . w2_b (low-rank form), [out_k, in_n]
+__global__ void __launch_bounds__(256) lokr_form_w2_kernel(const float* __restrict__ a, const float* __restrict__ b,
+                                                           int out_k, int in_n, int r, float* __restrict__ w2) {
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= (int64_t)out_k * in_n) return;
+  const int k = (int)(e / in_n), l = (int)(e - (int64_t)k * in_n);
+  float acc = 0.f;
+  for (int t = 0; t < r; ++t) acc += a[(int64_t)k * r + t] * b[(int64_t)t * in_n + l];
+  w2[e] = acc;
+}
+
+// workgroup (g, i): the w2 elements [g*2048, (g+1)*2048) of every Kronecker block (i, j), j = 0..in_m-1.
+//   p1[(i*G + g)*in_m + j] = sum_{e in group} dW[i,k,j,l] w2[e]      (partial of dw1[i,j])
+//   p2[i*W2 + e]           = sum_j w1[i,j] dW[i,k,j,l]                (partial of dw2[e])
+__global__ void __launch_bounds__(256) lokr_grad_partial_kernel(const float* __restrict__ dw, int K, int out_k,
+                                                                int in_n, int in_m, const float* __restrict__ w1,
+                                                                const float* __restrict__ w2, float* __restrict__ p1,
+                                                                float* __restrict__ p2) {
+  __shared__ float red[4];
+  const int g = blockIdx.x, i = blockIdx.y, G = gridDim.x, tid = threadIdx.x;
+  const int W2 = out_k * in_n;
+  float acc[8], w2v[8];
+  int64_t roff[8];
+#pragma unroll
+  for (int q = 0; q < 8; ++q) {
+    const int e = g * LK_GROUP + q * 256 + tid;
+    acc[q] = 0.f;
+    w2v[q] = 0.f;
+    roff[q] = -1;
+    if (e < W2) {
+      const int k = e / in_n, l = e - k * in_n;
+      roff[q] = (int64_t)(i * out_k + k) * K + l;
+      w2v[q] = w2[e];
+    }
+  }
+  for (int j = 0; j < in_m; ++j) {
+    const float w1v = w1[(int64_t)i * in_m + j];
+    float dot = 0.f;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      if (roff[q] >= 0) {
+        const float v = dw[roff[q] + (int64_t)j * in_n];
+        acc[q] += w1v * v;
+        dot += v * w2v[q];
+      }
+    }
+    dot = block_sum<4>(dot, red);
+    if (tid == 0) p1[((int64_t)i * G + g) * in_m + j] = dot;
+  }
+#pragma unroll
+  for (int q = 0; q < 8; ++q) {
+    const int e = g * LK_GROUP + q * 256 + tid;
+    if (e < W2) p2[(int64_t)i * W2 + e] = acc[q];
+  }
+}
+
+// dw1[i,j] += s sum_g p1;  dw2[e] (+)= s sum_i p2 -- into the gradient (full w2) or into the workspace (low-rank form)
+__global__ void __launch_bounds__(256) lokr_grad_reduce_kernel(const float* __restrict__ p1, const float* __restrict__ p2,
+                                                               int out_l, int in_m, int W2, int G, float scale,
+                                                               float* __restrict__ g1, float* __restrict__ g2,
+                                                               int g2_accumulate) {
+  const int64_t o = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t n1 = (int64_t)out_l * in_m;
+  if (o < n1) {
+    const int i = (int)(o / in_m), j = (int)(o - (int64_t)i * in_m);
+    float acc = 0.f;
+    for (int g = 0; g < G; ++g) acc += p1[((int64_t)i * G + g) * in_m + j];
+    g1[o] += scale * acc;
+  } else if (o < n1 + W2) {
+    const int64_t e = o - n1;
+    float acc = 0.f;
+    for (int i = 0; i < out_l; ++i) acc += p2[(int64_t)i * W2 + e];
+    if (g2_accumulate) g2[e] += scale * acc;
+    else g2[e] = scale * acc;
+  }
+}
+
+// low-rank chain: d_w2a[k,t] += sum_l dw2[k,l] w2_b[t,l];  d_w2b[t,l] += sum_k w2_a[k,t] dw2[k,l]
+__global__ void __launch_bounds__(256) lokr_grad_lowrank_kernel(const float* __restrict__ dw2, const float* __restrict__ a,
+                                                                const float* __restrict__ b, int out_k, int in_n, int r,
+                                                                float* __restrict__ ga, float* __restrict__ gb) {
+  const int64_t o = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t na = (int64_t)out_k * r, nb = (int64_t)r * in_n;
+  if (o < na) {
+    const int k = (int)(o / r), t = (int)(o - (int64_t)k * r);
+    float acc = 0.f;
+    for (int l = 0; l < in_n; ++l) acc += dw2[(int64_t)k * in_n + l] * b[(int64_t)t * in_n + l];
+    ga[o] += acc;
+  } else if (o < na + nb) {
+    const int64_t q = o - na;
+    const int t = (int)(q / in_n), l = (int)(q - (int64_t)t * in_n);
+    float acc = 0.f;
+    for (int k = 0; k < out_k; ++k) acc += a[(int64_t)k * r + t] * dw2[(int64_t)k * in_n + l];
+    gb[q] += acc;
+  }
+}
+
+// workspace of uwu_adapter_grad in floats (mirrored by uwudiff_amd/adapters.py: grad_ws_elems)
+int64_t ad_grad_ws_elems(int kind, int64_t N, int64_t K, int r, int out_k, int in_n) {
+  if (kind == UWU_ADAPTER_LORA) {
+    const int64_t nct = (K + LR_CT - 1) / LR_CT, nrt = (N + LR_RT - 1) / LR_RT;
+    return nct * N * r + nrt * r * K;
+  }
+  const int64_t out_l = N / out_k, in_m = K / in_n, W2 = (int64_t)out_k * in_n;
+  const int64_t G = (W2 + LK_GROUP - 1) / LK_GROUP;
+  return out_l * G * in_m + out_l * W2 + 2 * W2;
+}
+
+}  // namespace
+
+extern "C" int uwu_adapter_merge(const float* base, const float* p, const int64_t* table, const int64_t* blk_start,
+                                 int nseg, int64_t nblocks, float* eff, void* shadow, void* stream) {
+  UWU_CHECK_ARG(base && p && table && blk_start && nseg > 0 && nblocks > 0 && nblocks < (1ll << 31),
+                "adapter_merge: bad args (nseg=%d nblocks=%lld)", nseg, (long long)nblocks);
+  UWU_CHECK_ARG(eff || shadow, "adapter_merge: no output");
+  hipLaunchKernelGGL(adapter_merge_kernel, dim3((unsigned)nblocks), dim3(256), 0, (hipStream_t)stream, base, p, table,
+                     blk_start, nseg, eff, (bf16_t*)shadow);
+  UWU_LAUNCH_CHECK("adapter_merge");
+  return UWU_OK;
+}
+
+extern "C" int uwu_adapter_grad(const float* dw, int64_t N, int64_t K, int kind, const float* p, float* g, int64_t pa,
+                                int64_t pb, int64_t pc, int r, int out_k, int in_n, float scale, float* ws,
+                                int64_t ws_elems, void* stream) {
+  UWU_CHECK_ARG(dw && p && g && ws && N > 0 && K > 0 && N < (1 << 30) && K < (1 << 30) && N * K < (1ll << 31),
+                "adapter_grad: bad args");
+  hipStream_t st = (hipStream_t)stream;
+  if (kind == UWU_ADAPTER_LORA) {
+    UWU_CHECK_ARG(r >= 1 && r <= AD_MAX_RANK, "adapter_grad: LoRA rank %d outside [1, %d]", r, AD_MAX_RANK);
+    const int nct = (int)((K + LR_CT - 1) / LR_CT), nrt = (int)((N + LR_RT - 1) / LR_RT);
+    const int64_t need = (int64_t)nct * N * r + (int64_t)nrt * r * K;
+    UWU_CHECK_ARG(ws_elems >= need, "adapter_grad: workspace %lld < %lld floats", (long long)ws_elems, (long long)need);
+    float* du = ws;
+    float* dd = ws + (int64_t)nct * N * r;
+    hipLaunchKernelGGL(lora_grad_partial_kernel, dim3(nct, nrt), dim3(256), 0, st, dw, (int)N, (int)K, p + pa, p + pb, r,
+                       du, dd);
+    const int64_t nout = N * r + (int64_t)r * K;
+    hipLaunchKernelGGL(lora_grad_reduce_kernel, dim3((unsigned)((nout + 255) / 256)), dim3(256), 0, st, du, dd, (int)N,
+                       (int)K, r, nct, nrt, scale, g + pa, g + pb);
+    UWU_LAUNCH_CHECK("adapter_grad");
+    return UWU_OK;
+  }
+  UWU_CHECK_ARG(kind == UWU_ADAPTER_LOKR || kind == UWU_ADAPTER_LOKR_LOWRANK, "adapter_grad: bad kind %d", kind);
+  UWU_CHECK_ARG(out_k >= 1 && in_n >= 1 && N % out_k == 0 && K % in_n == 0, "adapter_grad: LoKr shape %lldx%lld / (%d, %d)",
+                (long long)N, (long long)K, out_k, in_n);
+  const bool low = kind == UWU_ADAPTER_LOKR_LOWRANK;
+  UWU_CHECK_ARG(!low || (r >= 1 && r <= AD_MAX_RANK), "adapter_grad: LoKr rank %d outside [1, %d]", r, AD_MAX_RANK);
+  const int out_l = (int)(N / out_k), in_m = (int)(K / in_n);
+  const int W2 = out_k * in_n;
+  const int G = (W2 + LK_GROUP - 1) / LK_GROUP;
+  const int64_t need = ad_grad_ws_elems(kind, N, K, r, out_k, in_n);
+  UWU_CHECK_ARG(ws_elems >= need, "adapter_grad: workspace %lld < %lld floats", (long long)ws_elems, (long long)need);
+  float* p1 = ws;
+  float* p2 = p1 + (int64_t)out_l * G * in_m;
+  float* w2f = p2 + (int64_t)out_l * W2;  // low-rank: the formed w2, then dw2
+  float* dw2 = w2f + W2;
+  const float* w2 = p + pb;
+  if (low) {
+    hipLaunchKernelGGL(lokr_form_w2_kernel, dim3((W2 + 255) / 256), dim3(256), 0, st, p + pb, p + pc, out_k, in_n, r, w2f);
+    w2 = w2f;
+  }
+  hipLaunchKernelGGL(lokr_grad_partial_kernel, dim3(G, out_l), dim3(256), 0, st, dw, (int)K, out_k, in_n, in_m, p + pa, w2,
+                     p1, p2);
+  const int64_t nout = (int64_t)out_l * in_m + W2;
+  hipLaunchKernelGGL(lokr_grad_reduce_kernel, dim3((unsigned)((nout + 255) / 256)), dim3(256), 0, st, p1, p2, out_l, in_m,
+                     W2, G, scale, g + pa, low ? dw2 : g + pb, low ? 0 : 1);
+  if (low) {
+    const int64_t n2 = (int64_t)out_k * r + (int64_t)r * in_n;
+    hipLaunchKernelGGL(lokr_grad_lowrank_kernel, dim3((unsigned)((n2 + 255) / 256)), dim3(256), 0, st, dw2, p + pb, p + pc,
+                       out_k, in_n, r, g + pb, g + pc);
+  }
+  UWU_LAUNCH_CHECK("adapter_grad");
+  return UWU_OK;
+}

@@ -105,8 +105,8 @@ __global__ void __launch_bounds__(256) gn_sums_kernel(const T* __restrict__ x, c
       t2 += r2s[y * C + c];
     }
     if constexpr (MODE == 1) {
-      atomicAdd(dbeta + c, t1);
-      atomicAdd(dgamma + c, t2);
+      if (dbeta) atomicAdd(dbeta + c, t1);  // (null: a frozen norm, no parameter gradient)
+      if (dgamma) atomicAdd(dgamma + c, t2);
       const float gm = gamma[c];
       t1 *= gm;
       t2 *= gm;
@@ -264,7 +264,7 @@ extern "C" int uwu_groupnorm_fwd(const void* x, const float* gamma, const float*
 extern "C" int uwu_groupnorm_bwd(const void* dy, const void* x, const float* mean, const float* rstd,
                                  const float* gamma, const float* beta, void* dx, float* dgamma, float* dbeta,
                                  float* ws, int B, int HW, int C, int G, int silu, int dtype, void* stream) {
-  UWU_CHECK_ARG(dy && x && mean && rstd && gamma && beta && dx && dgamma && dbeta && ws, "groupnorm_bwd: null pointer");
+  UWU_CHECK_ARG(dy && x && mean && rstd && gamma && beta && dx && ws, "groupnorm_bwd: null pointer");  // dgamma / dbeta may be null
   UWU_CHECK_ARG(B > 0 && HW > 0 && C > 0 && G > 0 && G <= 256 && C % G == 0 && C % 8 == 0 && C <= 4096,
                 "groupnorm_bwd: bad shape C=%d G=%d", C, G);
   UWU_CHECK_ARG((((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dx) & 15) == 0, "groupnorm_bwd: tensors must be 16-byte aligned");

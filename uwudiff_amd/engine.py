@@ -123,8 +123,9 @@ def _dist_env():
 class Fitter:
     def __init__(self, max_steps=-1, precision="bf16-mixed", gradient_clip_val=None, fast_dev_run=False,
                  log_every_n_steps=10, accelerator="gpu", devices=1, strategy=None, callbacks=(), logger=(),
-                 max_epochs=None, **ignored):
+                 max_epochs=None, default_root_dir=None, **ignored):
         self.max_steps = max_steps
+        self.default_root_dir = os.fspath(default_root_dir) if default_root_dir is not None else os.getcwd()
         self.precision = str(precision)
         self.gradient_clip_val = gradient_clip_val
         self.fast_dev_run = fast_dev_run
@@ -228,7 +229,8 @@ class Fitter:
         sched = cfg["lr_scheduler"]["scheduler"] if isinstance(cfg, dict) and "lr_scheduler" in cfg else None
         fused = isinstance(opt, FusedAdamW)
         sync = FlatGradSync(self.world_size)
-        if fused:  # the early (inside-backward) reduction is consumed by FusedAdamW's per-chunk waits only; a foreign
+        lyc = getattr(module, "lycoris_model", None)  # adapter training: the UNet is frozen, the adapter buffer trains
+        if fused and lyc is None:  # the early (inside-backward) reduction is consumed by FusedAdamW's per-chunk waits only; a foreign
             sync.attach(module.unet)  # optimizer takes the plain whole-buffer exchange below
         elif hasattr(module.unet, "set_grad_ready_hook"):
             module.unet.set_grad_ready_hook(None)
@@ -238,6 +240,9 @@ class Fitter:
         if self.world_size > 1 and hasattr(module.unet, "flat"):
             # identical replicas (Lightning DDP broadcasts rank 0's module state): do not rely on per-rank seeding order
             dist.broadcast(module.unet.flat.data, src=0)
+            if lyc is not None:  # (the adapter gradient is exchanged whole-buffer below: it is small)
+                dist.broadcast(lyc.flat.data, src=0)
+                lyc.mark_dirty()
             if hasattr(module.unet, "refresh_shadow"):
                 module.unet.refresh_shadow()
         # Lightning's fast_dev_run disables checkpoint callbacks and loggers
@@ -299,7 +304,9 @@ class Fitter:
                     if self.gradient_clip_val:
                         torch.nn.utils.clip_grad_norm_(params, self.gradient_clip_val)
                     opt.step()
-                    if hasattr(module.unet, "refresh_shadow"):
+                    if lyc is not None:
+                        lyc.mark_dirty()  # (the adapters are merged again by the next forward; the base shadow is unchanged)
+                    elif hasattr(module.unet, "refresh_shadow"):
                         module.unet.refresh_shadow()
                 if sched is not None:
                     sched.step()
@@ -323,6 +330,8 @@ class Fitter:
                     break
             if not finished_epoch or (ran == 0 and resume_skip == 0 and done):
                 break  # cut short by max_steps: the epoch is partial -- no epoch-end hooks, no epoch count
+            if hasattr(module, "on_train_epoch_end"):
+                module.on_train_epoch_end()
             for cb in ckpt_cbs:
                 cb.on_epoch_end(self)
             epoch += 1

@@ -69,6 +69,9 @@ _SIGS = {
                                P, c_int, P]),
     "uwu_cast_f32_to_bf16": (c_int, [P, P, c_int64, P]),
     "uwu_cast_bf16_to_f32": (c_int, [P, P, c_int64, P]),
+    "uwu_adapter_merge": (c_int, [P, P, P, P, c_int, c_int64, P, P, P]),
+    "uwu_adapter_grad": (c_int, [P, c_int64, c_int64, c_int, P, P, c_int64, c_int64, c_int64, c_int, c_int, c_int, c_float,
+                                 P, c_int64, P]),
     "uwu_comm_unique_id": (c_int, [P]),
     "uwu_comm_init": (c_int, [P, c_int, c_int, ctypes.POINTER(c_void_p)]),
     "uwu_allreduce_flat": (c_int, [P, P, c_int64, P]),

@@ -66,6 +66,8 @@ class _Ctx:
         self.side = None
         self._join_queued = False
         self._held = collections.deque()
+        self.ad = None  # _Adapters while a LyCORIS network is attached (frozen base)
+        self._names = None
 
     # ---- weight gradients are off the backward's critical path: they run on a side stream, ordered after the kernels
     # that produced their operands; the main stream joins once, when the backward pass has finished
@@ -118,22 +120,191 @@ class _Ctx:
             o, sh = self.registry[nm]
             if sh != shape or len(sh) != 2 or o != off + i * math.prod(shape):
                 return None
+        if self.ad is not None:  # all adapted or none; adapted fp32 operands must sit back to back in the effective copy
+            flags = [nm in self.ad.seg for nm in names]
+            if any(flags) and not all(flags):
+                return None
+            if all(flags) and not self.bf16 and not self.ad.eff_contiguous(self, names):
+                return None
         return (names[0], len(names))
 
+    def base32(self, name):  # the (frozen) base weights, whether or not adapters are attached
+        return self._view(self.flat.data, name)
+
     def w32(self, name):
+        if self.ad is not None and self.adapted(name):
+            return self.ad.eff_view(self, name)
         return self._view(self.flat.data, name)
 
     def w(self, name):  # GEMM operand copy
-        return self._view(self.shadow if self.bf16 else self.flat.data, name)
+        if self.bf16:
+            return self._view(self.shadow, name)
+        return self.w32(name)
 
     def g(self, name):
+        if self.ad is not None:  # frozen base: gradients exist for the norm adapters only (None: a frozen tensor)
+            return self.ad.grad_view(self, name)
         if self.flat.grad is None:
             self.flat.grad = torch.zeros_like(self.flat.data)
         return self._view(self.flat.grad, name)
 
+    # ---- adapters
+    def adapted(self, name):
+        return self.ad is not None and (name[0] if isinstance(name, tuple) else name) in self.ad.seg
+
+    def anchor(self, name):
+        """the parameter an op on weight `name` is recorded against: the adapter buffer for an adapted weight, else the
+        flat parameter (which needs no gradient while the base is frozen: ops of the frozen prefix stay out of the graph)"""
+        return self.ad.net.flat if self.adapted(name) else self.flat
+
+    def members(self, name):
+        if not isinstance(name, tuple):
+            return [name]
+        if self._names is None:
+            self._names = list(self.registry)
+            self._index = {n: i for i, n in enumerate(self._names)}
+        i = self._index[name[0]]
+        return self._names[i:i + name[1]]
+
     @property
     def dtype(self):
         return torch.bfloat16 if self.bf16 else torch.float32
+
+
+def _memset_zero(t):
+    L.call("uwu_memset_zero", L.ptr(t), t.numel() * t.element_size(), L.stream())
+    return t
+
+
+class _Adapters:
+    """A LyCORIS network (adapters.LycorisNetwork) attached to one UNet.
+
+    ``seg``: registry name of every adapted tensor -> (spec, kind, pa, pb, pc) (offsets into the adapter buffer).  The
+    effective weights W + dW live in the bf16 shadow (GEMM operands in bf16 mode) and in ``eff``, an fp32 buffer covering
+    only the adapted tensors that are read in fp32: all of them in fp32 mode; norm vectors and the conditioning Linears
+    (fp32 matrix-vector kernels) in bf16 mode.  ``merge`` rewrites both in one uwu_adapter_merge launch."""
+
+    def __init__(self, net, P, fp32_names):
+        from .adapters import KIND_LOKR, KIND_LOKR_LOWRANK, KIND_LORA, KIND_NORM
+
+        self.net, self.fp32_names = net, fp32_names
+        self.seg = {}
+        off = lambda s, t: net.offsets[(s.name, t)][0]
+        for s in net.specs:
+            if s.algo == "norm":
+                self.seg[s.name + ".weight"] = (s, KIND_NORM, off(s, "w_norm"), 0, 0)
+                self.seg[s.name + ".bias"] = (s, KIND_NORM, off(s, "b_norm"), 0, 0)
+            elif s.algo == "lora":
+                self.seg[s.name + ".weight"] = (s, KIND_LORA, off(s, "lora_up.weight"), off(s, "lora_down.weight"), 0)
+            elif s.lowrank:
+                self.seg[s.name + ".weight"] = (s, KIND_LOKR_LOWRANK, off(s, "lokr_w1"), off(s, "lokr_w2_a"),
+                                                off(s, "lokr_w2_b"))
+            else:
+                self.seg[s.name + ".weight"] = (s, KIND_LOKR, off(s, "lokr_w1"), off(s, "lokr_w2"), 0)
+        order = {n: i for i, n in enumerate(P.registry)}
+        self.names = sorted(self.seg, key=order.__getitem__)
+        self.key = None
+        self.eff, self.eff_off = None, {}
+        self.version = None
+
+    def _table(self, P, eff_off, shadow):
+        rows, blk = [], [0]
+        for nm in self.names:
+            spec, kind, pa, pb, pc = self.seg[nm]
+            base, shape = P.registry[nm]
+            r_, c_ = (shape[0], shape[1]) if len(shape) == 2 else (1, shape[0])
+            sbits = int.from_bytes(torch.tensor([spec.scale], dtype=torch.float32).numpy().tobytes(), "little")
+            rows.append([kind, r_, c_, base, eff_off.get(nm, -1), base if shadow else -1, pa, pb, pc, spec.r, spec.out_k,
+                         spec.in_n, sbits])
+            blk.append(blk[-1] + -(-(r_ * c_) // 4096))
+        dev = P.flat.device
+        return (torch.tensor(rows, dtype=torch.int64).to(dev), torch.tensor(blk, dtype=torch.int64).to(dev),
+                len(rows), blk[-1])
+
+    def prepare(self, P):
+        key = (P.flat.device, P.bf16)
+        if key == self.key:
+            return
+        self.eff_off, n = {}, 0
+        for nm in self.names:
+            if not P.bf16 or self.seg[nm][1] == 0 or nm in self.fp32_names:
+                self.eff_off[nm] = n
+                n += _pad64(math.prod(P.registry[nm][1]))
+        self.eff = torch.empty(max(n, 64), device=P.flat.device, dtype=torch.float32)
+        self.tab = self._table(P, self.eff_off, P.bf16)
+        self.key, self.version = key, None
+
+    def needs_merge(self, P):
+        return self.key != (P.flat.device, P.bf16) or self.net._dirty or self.version != self.net.flat._version
+
+    def merge(self, P):
+        """W_eff = W + dW of every adapted tensor: one launch"""
+        self.prepare(P)
+        tab, blk, nseg, nblocks = self.tab
+        shadow = P.shadow if P.bf16 else None
+        L.call("uwu_adapter_merge", L.ptr(P.flat.data), L.ptr(self.net.flat.data), L.ptr(tab), L.ptr(blk), nseg, nblocks,
+               L.ptr(self.eff), L.ptr(shadow), L.stream())
+        self.net._dirty = False
+        self.version = self.net.flat._version
+
+    def fold(self, P):
+        """W += dW in the base fp32 weights themselves (in place: every element is read and written by one thread)"""
+        tab, blk, nseg, nblocks = self._table(P, {nm: P.registry[nm][0] for nm in self.names}, False)
+        L.call("uwu_adapter_merge", L.ptr(P.flat.data), L.ptr(self.net.flat.data), L.ptr(tab), L.ptr(blk), nseg, nblocks,
+               L.ptr(P.flat.data), None, L.stream())
+
+    def eff_view(self, P, name):
+        first, n = name if isinstance(name, tuple) else (name, 1)
+        if first not in self.eff_off:
+            raise L.UwuError(f"{first}: no fp32 effective copy of this adapted weight in bf16 mode")
+        shape = P.registry[first][1]
+        off = self.eff_off[first]
+        if n > 1:
+            return self.eff[off:off + n * math.prod(shape)].view(n * shape[0], shape[1])
+        return self.eff[off:off + math.prod(shape)].view(shape)
+
+    def eff_contiguous(self, P, names):
+        if any(nm not in self.eff_off for nm in names):
+            return False
+        step = math.prod(P.registry[names[0]][1])
+        return all(self.eff_off[nm] == self.eff_off[names[0]] + i * step for i, nm in enumerate(names))
+
+    def grad_view(self, P, name):
+        ent = self.seg.get(name)
+        if ent is None or ent[1] != 0:
+            return None
+        g = self.net.flat.grad
+        if g is None:
+            return None
+        shape = P.registry[name][1]
+        return g[ent[2]:ent[2] + math.prod(shape)].view(shape)
+
+    def linear_grad(self, P, wname, dy, x, skinny):
+        """fp32 dW of an adapted Linear (stacked span: every member), then the adapter gradients from it"""
+        names = P.members(wname)
+        K = P.registry[names[0]][1][1]
+        N = sum(P.registry[nm][1][0] for nm in names)
+        dW = _memset_zero(torch.empty(N, K, device=dy.device, dtype=torch.float32))
+        if skinny and dy.dtype == torch.float32:
+            ops.skinny_linear_wgrad(dy, x, dW, None)
+        else:
+            ops.gemm_wgrad_shared(dy, x, dW, blocks=_wgrad_blocks(x.shape[0], N, K))
+        self.grad_rows(P, names, dW)
+
+    def grad_rows(self, P, names, dW):
+        from .adapters import grad_ws_elems
+
+        p, g = self.net.flat.data, self.net.flat.grad
+        row = 0
+        for nm in names:
+            rows, K = P.registry[nm][1]
+            ent = self.seg.get(nm)
+            if ent is not None:
+                spec, kind, pa, pb, pc = ent
+                ws = torch.empty(max(grad_ws_elems(spec, rows, K), 1), device=dW.device, dtype=torch.float32)
+                L.call("uwu_adapter_grad", L.ptr(dW[row:row + rows]), rows, K, kind, L.ptr(p), L.ptr(g), pa, pb, pc, spec.r,
+                       spec.out_k, spec.in_n, float(spec.scale), L.ptr(ws), ws.numel(), L.stream())
+            row += rows
 
 
 def _wgrad_blocks(M, N, K):
@@ -173,6 +344,16 @@ class _LinearFn(torch.autograd.Function):
         W = P.w32(wname) if fp32 else P.w(wname)
         M, K = x.shape
         N = W.shape[0]
+        if P.ad is not None:  # frozen base: dX with W + dW; the adapter gradients of an adapted weight (no bias gradient)
+            dx = None
+            if ctx.needs_input_grad[0]:
+                if skinny and dy.dtype == torch.float32 and K <= 512:
+                    dx = ops.skinny_linear_dgrad(dy, W)
+                else:
+                    dx = ops.gemm(dy, W, trans_b=True)
+            if P.adapted(wname):
+                P.on_side(lambda: P.ad.linear_grad(P, wname, dy, x, skinny), dy, x)
+            return dx, None, None, None, None, None
         if skinny and dy.dtype == torch.float32:
             dx = None
             if ctx.needs_input_grad[0]:  # (the matrix-vector input gradient covers K <= 512: the DiT widths, not 1280)
@@ -209,6 +390,14 @@ class _Conv3x3Fn(torch.autograd.Function):
         dy = dy.contiguous()
         Wt = P.w(wname)
         dx = None
+        frozen = P.ad is not None  # (convolutions are never adapted: no weight gradient while the base is frozen)
+        if frozen and ctx.needs_input_grad[0]:
+            if implicit:
+                dx = ops.conv3x3_dgrad(dy, Wt, B, H, W_, C, Wt.shape[0], stride)
+            else:
+                dx = ops.col2im3x3(ops.gemm(dy, Wt, trans_b=True), B, H, W_, C, stride)
+        if frozen:
+            return (dx,) + (None,) * 8
         if implicit:
             Cout = Wt.shape[0]
             if ctx.needs_input_grad[0]:
@@ -226,7 +415,8 @@ class _Conv3x3Fn(torch.autograd.Function):
 
 class _GroupNormFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, P, prefix, B, HW, C, G, eps, silu):
+    def forward(ctx, x, P, prefix, B, HW, C, G, eps, silu, anchor):
+        # `anchor`: the parameter the gamma / beta gradients go to (P.anchor): records the op when x needs no gradient
         y, mean, rstd = ops.groupnorm_fwd(x, P.w32(prefix + ".weight"), P.w32(prefix + ".bias"), B, HW, C, G, eps, silu)
         ctx.save_for_backward(x, mean, rstd)
         ctx.meta = (P, prefix, B, HW, C, G, silu)
@@ -238,12 +428,12 @@ class _GroupNormFn(torch.autograd.Function):
         P, prefix, B, HW, C, G, silu = ctx.meta
         dx = ops.groupnorm_bwd(dy.contiguous(), x, mean, rstd, P.w32(prefix + ".weight"), P.w32(prefix + ".bias"),
                                P.g(prefix + ".weight"), P.g(prefix + ".bias"), B, HW, C, G, silu)
-        return (dx,) + (None,) * 8
+        return (dx,) + (None,) * 9
 
 
 class _LayerNormFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, P, prefix, eps):
+    def forward(ctx, x, P, prefix, eps, anchor):
         M, D = x.shape
         _, h, mean, rstd = ops.add_ln_modulate_fwd(x, 1, M, shift=P.w32(prefix + ".bias"), scale=P.w32(prefix + ".weight"),
                                                    mod_ld=0, eps=eps, affine=True)
@@ -258,7 +448,7 @@ class _LayerNormFn(torch.autograd.Function):
         M, D = x.shape
         dx, _ = ops.add_ln_modulate_bwd(dh.contiguous(), x, mean, rstd, 1, M, scale=P.w32(prefix + ".weight"), mod_ld=0,
                                         dshift=P.g(prefix + ".bias"), dscale=P.g(prefix + ".weight"), affine=True)
-        return dx, None, None, None
+        return dx, None, None, None, None
 
 
 class _AddLayerNormFn(torch.autograd.Function):
@@ -266,7 +456,7 @@ class _AddLayerNormFn(torch.autograd.Function):
     (dx = dx_res + LN_bwd(dn)), so neither direction runs a separate add."""
 
     @staticmethod
-    def forward(ctx, h, a, P, prefix, eps, ones):
+    def forward(ctx, h, a, P, prefix, eps, ones, anchor):
         M, D = h.shape
         x, n, mean, rstd = ops.add_ln_modulate_fwd(h, 1, M, y=a.contiguous(), gate=ones, shift=P.w32(prefix + ".bias"),
                                                    scale=P.w32(prefix + ".weight"), mod_ld=0, eps=eps, affine=True)
@@ -282,7 +472,7 @@ class _AddLayerNormFn(torch.autograd.Function):
         dx, _ = ops.add_ln_modulate_bwd(dn.contiguous(), x, mean, rstd, 1, M, scale=P.w32(prefix + ".weight"),
                                         dx_in=dx_res.contiguous(), mod_ld=0, dshift=P.g(prefix + ".bias"),
                                         dscale=P.g(prefix + ".weight"), affine=True)
-        return dx, dx, None, None, None, None
+        return dx, dx, None, None, None, None, None
 
 
 class _AttentionFn(torch.autograd.Function):
@@ -398,6 +588,8 @@ class _AddRowvecFn(torch.autograd.Function):
     def backward(ctx, d):
         B, HW, C, vdt = ctx.meta
         d = d.contiguous()
+        if not ctx.needs_input_grad[1]:  # (a time embedding of the frozen base)
+            return d, None, None, None, None
         dv = ops.colsum_batched(d, B, HW, C)
         return d, dv.to(vdt), None, None, None
 
@@ -481,7 +673,11 @@ class UNet2DConditionModel(nn.Module):
         self.cin_pad, self.cout_pad = _pad8(cfg["in_channels"]), _pad8(cfg["out_channels"])
         self._conv_meta = {}
 
+        # module name -> layer class (Linear / Conv2d / GroupNorm / LayerNorm): the LyCORIS preset matching (adapters.py)
+        self.module_kinds = {}
+
         def lin(name, cin, cout, bias=True):
+            self.module_kinds[name] = "Linear"
             P.add(name + ".weight", (cout, cin))
             if bias:
                 P.add(name + ".bias", (cout,))
@@ -489,10 +685,12 @@ class UNet2DConditionModel(nn.Module):
         def conv(name, cin, cout, cin_store=None, cout_store=None):
             ci, co = cin_store or cin, cout_store or cout
             self._conv_meta[name] = (cin, cout, ci, co)
+            self.module_kinds[name] = "Conv2d"
             P.add(name + ".weight", (co, 9 * ci))
             P.add(name + ".bias", (co,))
 
-        def norm(name, c):
+        def norm(name, c, kind="GroupNorm"):
+            self.module_kinds[name] = kind
             P.add(name + ".weight", (c,))
             P.add(name + ".bias", (c,))
 
@@ -514,7 +712,7 @@ class UNet2DConditionModel(nn.Module):
             ctx_dim = cfg["cross_attention_dim"]
             for i in range(depth):
                 b = f"{name}.transformer_blocks.{i}"
-                norm(b + ".norm1", dim)
+                norm(b + ".norm1", dim, "LayerNorm")
                 for a, kd in (("attn1", dim), ("attn2", ctx_dim)):
                     lin(f"{b}.{a}.to_q", dim, dim, bias=False)
                     lin(f"{b}.{a}.to_k", kd, dim, bias=False)
@@ -525,8 +723,8 @@ class UNet2DConditionModel(nn.Module):
                         P.add(f"{b}.{a}.axial_rope.freqs_h", (nh, dim // nh // 4))
                         P.add(f"{b}.{a}.axial_rope.freqs_w", (nh, dim // nh // 4))
                     if a == "attn1":
-                        norm(b + ".norm2", dim)
-                norm(b + ".norm3", dim)
+                        norm(b + ".norm2", dim, "LayerNorm")
+                norm(b + ".norm3", dim, "LayerNorm")
                 lin(b + ".ff.net.0.proj", dim, dim * 8)
                 lin(b + ".ff.net.2", dim * 4, dim)
             lin(name + ".proj_out", dim, dim)
@@ -604,7 +802,7 @@ class UNet2DConditionModel(nn.Module):
         g = torch.Generator(device=dev).manual_seed(torch.initial_seed() % (2 ** 31))
         zero = self.cfg_dict["zero_init"]
         for name, (off, shape) in self.P.registry.items():
-            v = self.P.w32(name)
+            v = self.P.base32(name)
             if ".axial_rope." in name:  # rope.py:74-81 freqs_pixel_log(max_freq = 10): linspace(log pi, log 5 pi) per head
                 v.copy_(torch.linspace(math.log(math.pi), math.log(10.0 * math.pi / 2), shape[-1]).expand(shape))
             elif name.endswith(".bias"):
@@ -629,17 +827,17 @@ class UNet2DConditionModel(nn.Module):
     @torch.no_grad()
     def _zero_padding(self):
         for cname, (cin, cout, ci, co) in self._conv_meta.items():
-            w = self.P.w32(cname + ".weight").view(co, 9, ci)
+            w = self.P.base32(cname + ".weight").view(co, 9, ci)
             if ci != cin:
                 w[:, :, cin:] = 0
             if co != cout:
                 w[cout:] = 0
-                self.P.w32(cname + ".bias")[cout:] = 0
+                self.P.base32(cname + ".bias")[cout:] = 0
 
     def named_tensors(self):
         """(diffusers name, tensor in diffusers layout) pairs; conv weights are returned as [Cout, Cin, 3, 3]."""
         for name in self.P.registry:
-            v = self.P.w32(name)
+            v = self.P.base32(name)
             base = name[:-7] if name.endswith(".weight") else name[:-5]
             if base in self._conv_meta:
                 cin, cout, ci, co = self._conv_meta[base]
@@ -665,7 +863,7 @@ class UNet2DConditionModel(nn.Module):
                 missing.append(name)
                 continue
             src = state_dict[name].float()
-            dst = self.P.w32(name)
+            dst = self.P.base32(name)
             base = name[:-7] if name.endswith(".weight") else name[:-5]
             if base in self._conv_meta:
                 cin, cout, ci, co = self._conv_meta[base]
@@ -694,6 +892,8 @@ class UNet2DConditionModel(nn.Module):
 
     @torch.no_grad()
     def refresh_shadow(self):
+        if self.P.ad is not None:  # the effective weights of the adapted tensors are merged again before the next forward
+            self.P.ad.net.mark_dirty()
         if not self.P.bf16 or not self.flat.is_cuda:
             return
         if self.shadow.numel() != self.P.n or self.shadow.device != self.flat.device:
@@ -707,6 +907,40 @@ class UNet2DConditionModel(nn.Module):
         self.P.flat = self.flat
         self.refresh_shadow()
         return r
+
+    # ------------------------------------------------------------------ LyCORIS adapters (adapters.py)
+    def _fp32_weight_names(self):
+        """weights read in fp32 in bf16 mode too: the conditioning path's Linears (matrix-vector kernels)"""
+        return {n for n in self.P.registry if n.endswith(".weight") and (
+            n.startswith(("time_embedding.", "add_embedding.")) or ".time_emb_proj." in n)}
+
+    def attach_adapters(self, net):
+        """Run with W + dW of `net` (an adapters.LycorisNetwork).  The base stays frozen: ``flat`` is never written and
+        gets no gradient; ops that touch no adapted tensor and see no differentiable input are not recorded."""
+        self.P.ad = _Adapters(net, self.P, self._fp32_weight_names())
+        net.mark_dirty()
+
+    def detach_adapters(self):
+        self.P.ad = None
+        self.refresh_shadow()
+
+    @torch.no_grad()
+    def fold_adapters(self, net):
+        """W += dW of `net` in the base weights (one merge launch) and detach: a plain UNet with the adapted weights."""
+        if not self.flat.is_cuda:
+            raise L.UwuError("fold_adapters runs on the HIP device only (no CPU fallback)")
+        _Adapters(net, self.P, set()).fold(self.P)
+        self.detach_adapters()
+
+    def _sync_adapters(self):
+        ad = self.P.ad
+        if ad.net.flat.device != self.flat.device:
+            raise L.UwuError("the adapter network and the UNet are on different devices")
+        if ad.needs_merge(self.P):
+            ad.merge(self.P)
+        g = ad.net.flat
+        if torch.is_grad_enabled() and g.requires_grad and g.grad is None:
+            g.grad = _memset_zero(torch.empty_like(g.data))
 
     def enable_gradient_checkpointing(self, enable=True):
         """test_scripts/test_train.py:38-39.  Every resnet and every Transformer2D stack becomes one recomputed segment: only
@@ -729,18 +963,18 @@ class UNet2DConditionModel(nn.Module):
         return c[(n, dev)]
 
     def _linear(self, x, name, bias=True, fp32=False):
-        return _LinearFn.apply(x, self.P, name + ".weight", name + ".bias" if bias else None, fp32, self.flat)
+        return _LinearFn.apply(x, self.P, name + ".weight", name + ".bias" if bias else None, fp32, self.P.anchor(name + ".weight"))
 
     def _conv(self, x, name, B, H, W, C, stride=1):
         return _Conv3x3Fn.apply(x, self.P, name + ".weight", name + ".bias", B, H, W, C, stride)
 
     def _resnet(self, x, emb_act, name, cin, cout, B, H, W):
         HW = H * W
-        h = _GroupNormFn.apply(x, self.P, name + ".norm1", B, HW, cin, self.G, 1e-5, True)
+        h = _GroupNormFn.apply(x, self.P, name + ".norm1", B, HW, cin, self.G, 1e-5, True, self.P.anchor(name + ".norm1.weight"))
         h = self._conv(h, name + ".conv1", B, H, W, cin)
         t = self._linear(emb_act, name + ".time_emb_proj", fp32=True)  # [B, cout] fp32
         h = _AddRowvecFn.apply(h, t, B, HW, cout)
-        h = _GroupNormFn.apply(h, self.P, name + ".norm2", B, HW, cout, self.G, 1e-5, True)
+        h = _GroupNormFn.apply(h, self.P, name + ".norm2", B, HW, cout, self.G, 1e-5, True, self.P.anchor(name + ".norm2.weight"))
         h = self._conv(h, name + ".conv2", B, H, W, cout)
         if cin != cout:
             x = self._linear(x, name + ".conv_shortcut")
@@ -769,7 +1003,7 @@ class UNet2DConditionModel(nn.Module):
                 # self-attention up to 256 tokens (every one at 4x32x32 latents): ONE stacked projection and the rotation applied
                 # inside the attention kernels' q / k staging (attn_*_mfma<..., ROPE>, reference rope_unet.py:143-147 rotates
                 # between projection and SDPA) -- no rotated copies of q / k, no standalone rotation kernels in the forward
-                qkv = _LinearFn.apply(x, self.P, span, None, False, self.flat)
+                qkv = _LinearFn.apply(x, self.P, span, None, False, self.P.anchor(span))
                 o = ops.rope_attention(qkv, pos[:T], fh, fw, B, T, heads, d)
                 return self._linear(o, name + ".to_out.0")
             # longer sequences / cross-attention: separate projections (the rotation needs q / k as tensors of their own), q
@@ -788,14 +1022,14 @@ class UNet2DConditionModel(nn.Module):
         if ctx is None:
             span = self.P.span([f"{name}.to_{c}.weight" for c in "qkv"])
             if span is not None:
-                qkv = _LinearFn.apply(x, self.P, span, None, False, self.flat)
+                qkv = _LinearFn.apply(x, self.P, span, None, False, self.P.anchor(span))
                 o = _PackedAttentionFn.apply(None, qkv, B, T, Tk, heads, D // heads, key_bias)
                 return self._linear(o, name + ".to_out.0")
         else:
             span = self.P.span([f"{name}.to_{c}.weight" for c in "kv"])
             if span is not None:
                 q = self._linear(x, name + ".to_q", bias=False)
-                kv = _LinearFn.apply(ctx, self.P, span, None, False, self.flat)
+                kv = _LinearFn.apply(ctx, self.P, span, None, False, self.P.anchor(span))
                 o = _PackedAttentionFn.apply(q, kv, B, T, Tk, heads, D // heads, key_bias)
                 return self._linear(o, name + ".to_out.0")
         q = self._linear(x, name + ".to_q", bias=False)
@@ -807,20 +1041,20 @@ class UNet2DConditionModel(nn.Module):
 
     def _t2d(self, x, ctx, name, depth, heads, B, HW, C, Tk):
         self._hw = self._hw_of[HW]
-        h = _GroupNormFn.apply(x, self.P, name + ".norm", B, HW, C, self.G, 1e-6, False)
+        h = _GroupNormFn.apply(x, self.P, name + ".norm", B, HW, C, self.G, 1e-6, False, self.P.anchor(name + ".norm.weight"))
         h = self._linear(h, name + ".proj_in")
         ones = self._ones(C, h.device)
         f = None  # branch output still to be added to the residual stream: folded into the next LayerNorm pass
         for i in range(depth):
             b = f"{name}.transformer_blocks.{i}"
             if f is None:
-                n = _LayerNormFn.apply(h, self.P, b + ".norm1", 1e-5)
+                n = _LayerNormFn.apply(h, self.P, b + ".norm1", 1e-5, self.P.anchor(b + ".norm1.weight"))
             else:
-                h, n = _AddLayerNormFn.apply(h, f, self.P, b + ".norm1", 1e-5, ones)
+                h, n = _AddLayerNormFn.apply(h, f, self.P, b + ".norm1", 1e-5, ones, self.P.anchor(b + ".norm1.weight"))
             a = self._attn(n, None, b + ".attn1", B, HW, HW, heads)
-            h, n = _AddLayerNormFn.apply(h, a, self.P, b + ".norm2", 1e-5, ones)
+            h, n = _AddLayerNormFn.apply(h, a, self.P, b + ".norm2", 1e-5, ones, self.P.anchor(b + ".norm2.weight"))
             a = self._attn(n, ctx, b + ".attn2", B, HW, Tk, heads, self._key_bias)
-            h, n = _AddLayerNormFn.apply(h, a, self.P, b + ".norm3", 1e-5, ones)
+            h, n = _AddLayerNormFn.apply(h, a, self.P, b + ".norm3", 1e-5, ones, self.P.anchor(b + ".norm3.weight"))
             f = self._linear(_GegluFn.apply(self._linear(n, b + ".ff.net.0.proj")), b + ".ff.net.2")
         h = _AddFn.apply(h, f)
         h = self._linear(h, name + ".proj_out")
@@ -837,7 +1071,9 @@ class UNet2DConditionModel(nn.Module):
         dev = sample.device
         if P.bf16 and self.shadow.numel() != P.n:
             self.refresh_shadow()
-        if self.flat.grad is None and torch.is_grad_enabled():
+        if P.ad is not None:
+            self._sync_adapters()
+        elif self.flat.grad is None and torch.is_grad_enabled():
             self.flat.grad = torch.zeros_like(self.flat.data)
         if P.side is None and os.environ.get("UWU_UNET_FORK", "1") != "0":
             P.side = torch.cuda.Stream(device=dev)
@@ -871,9 +1107,10 @@ class UNet2DConditionModel(nn.Module):
                     raise ValueError(f"encoder_attention_mask must be [B, S] = [{B}, {Tk}]")
                 keep = encoder_attention_mask.to(device=dev, dtype=torch.float32)
                 self._key_bias = ((1.0 - keep) * -10000.0).contiguous()
-        # the input needs no gradient, but every op must see a differentiable input to be recorded
+        # the input needs no gradient, but every op must see a differentiable input to be recorded (with adapters attached
+        # the ops before the first adapted tensor are not: they are anchored to the frozen flat parameter)
         x = sample.float()
-        if torch.is_grad_enabled() and not x.requires_grad:
+        if torch.is_grad_enabled() and not x.requires_grad and P.ad is None:
             x = x.detach().requires_grad_(True)
         x = _ToCL.apply(x, self.cin_pad, dt)
         x = self._conv(x, "conv_in", B, H, W, self.cin_pad)
@@ -911,7 +1148,7 @@ class UNet2DConditionModel(nn.Module):
                 x = _UpsampleFn.apply(x, B, h, w, blk["ch"])
                 h, w = 2 * h, 2 * w
                 x = self._conv(x, blk["up"], B, h, w, blk["ch"])
-        x = _GroupNormFn.apply(x, P, "conv_norm_out", B, h * w, boc[0], self.G, 1e-5, True)
+        x = _GroupNormFn.apply(x, P, "conv_norm_out", B, h * w, boc[0], self.G, 1e-5, True, P.anchor("conv_norm_out.weight"))
         x = self._conv(x, "conv_out", B, h, w, boc[0])
         return (_FromCL.apply(x, B, cfg.out_channels, h, w, self.cout_pad),)
 
