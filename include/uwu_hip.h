@@ -260,7 +260,7 @@ int uwu_gemm_fp8_emit(const void* A, const void* B, void* C, float* colsum, cons
  * im2col matrix exists in HBM (reference: the resblock / down / up-sample Conv2d of diffusers' UNet2DConditionModel,
  * src/duwu/modules/unet_patch.py:13-57).  x [B,H,W,C], w [Cout][3][3][C] (the layout of this build's flat parameter
  * blob), y / dy [B,Ho,Wo,Cout].  uwu_conv3x3_implicit_ok tells whether a shape is covered (bf16, C and Cout multiples
- * of 32, B*Ho*Wo a multiple of 32); other shapes use uwu_im2col3x3 + uwu_gemm.  wgrad accumulates into fp32 dw / db. */
+ * of 32, B, H, W > 0, B*Ho*Wo a multiple of 32); other shapes use uwu_im2col3x3 + uwu_gemm.  wgrad accumulates into fp32 dw / db. */
 int uwu_conv3x3_implicit_ok(int B, int H, int W, int C, int Cout, int stride, int dtype);
 int uwu_conv3x3_fwd(const void* x, const void* w, const float* bias, void* y, int B, int H, int W, int C, int Cout,
                     int stride, int dtype, void* stream);

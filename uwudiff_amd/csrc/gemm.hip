@@ -2150,6 +2150,7 @@ static const void* conv_zero_page() {
 
 extern "C" int uwu_conv3x3_implicit_ok(int B, int H, int W, int C, int Cout, int stride, int dtype) {
   if (dtype != UWU_BF16 || C % 32 || Cout % 32 || C < 32 || Cout < 32 || (stride != 1 && stride != 2)) return 0;
+  if (B <= 0 || H <= 0 || W <= 0) return 0;  // an empty image has Mo = 0, a multiple of 32: not a shape to launch
   const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
   const int64_t Mi = (int64_t)B * H * W, Mo = (int64_t)B * Ho * Wo;
   if (Mi >= (1 << 24) || Mo >= (1 << 24) || Mo % 32 || 9 * (int64_t)C >= (1 << 24)) return 0;
