@@ -1,6 +1,6 @@
 // Weight gradients on the 8-phase schedule of gemm_p8.hip:  dW[M, N] (fp32) += A[K, M]^T . B[K, N],  A = dY, B = X, both
 // K-major bf16 (reference: the weight gradient autograd forms for every nn.Linear of the blocks, src/duwu/modules/rope_unet.py:
-// 122-166, 393-411).  gemm_trw_kernel (gemm.hip) runs 192 x 384 tiles with one barrier per 32-deep K step and all eight waves in
+// 122-166, 393-411).  gemm_trw_kernel (gemm_wgrad.hip) runs 192 x 384 tiles with one barrier per 32-deep K step and all eight waves in
 // step (0.8 - 1.0 PFLOP/s on the DiT-B/2 and DiT-XL/2 shapes); this kernel:
 //
 //   * 256 x 256 tiles, K step 64, the half-tile ring of gemm_p8.hip with BOTH operands as [32 k][128 x] sub-images filled untouched
@@ -22,9 +22,6 @@ namespace {
 
 constexpr int W8_HT = 128 * ROW_BYTES;  // half-tile: 128 columns x 64 k = two [32 k][128 x] sub-images of 8 KB
 constexpr int W8_LDS = 8 * W8_HT;
-
-template <int H>
-using IC = std::integral_constant<int, H>;
 
 // LDS-DMA with a wave-uniform 64-bit base in SGPRs and a 32-bit per-lane byte offset: one address register per source instead of
 // a pair (this kernel lives at the 256-register limit).  Inline asm: m0 is saved / set / restored inside the statement; hipcc does

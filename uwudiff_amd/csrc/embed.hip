@@ -161,7 +161,7 @@ extern "C" int uwu_add(const void* a, const void* b, void* out, int64_t n, int d
 }
 
 // dst[c][r] = src[r][c] for a bf16 matrix (weights only: the input-gradient GEMM of a store-heavy Linear wants its weight
-// contraction-contiguous, csrc/gemm.hip gemm_as_kernel).  32 x 32 tiles through LDS, coalesced on both sides.
+// contraction-contiguous, csrc/gemm_as.hip gemm_as_kernel).  32 x 32 tiles through LDS, coalesced on both sides.
 namespace {
 __global__ void __launch_bounds__(256) transpose_bf16_kernel(const bf16_t* __restrict__ src, bf16_t* __restrict__ dst, int rows,
                                                              int cols, int lds, int ldd) {

@@ -26,7 +26,7 @@
 //        other three slots are refilled two phases after their reads, which a later barrier of the reading group separates.
 //
 // TB = 1 (input gradients, W stored [K][N]): the B half-tiles are two [32 k][128 n] sub-images filled untouched and read by
-// ds_read_b64_tr_b16, exactly as in gemm_big_kernel / gemm_r3_kernel.
+// ds_read_b64_tr_b16, exactly as in gemm_big_kernel / gemm_r3_kernel (gemm.hip).
 #include "gemm_shared.h"
 
 namespace {
@@ -36,14 +36,6 @@ constexpr int P8_RING = 8 * P8_HT;     // ring of eight half-tile slots (128 KB)
 constexpr int P8_BIAS = P8_RING + 2048;  // behind the dGELU column sums of a tile (2 x 256 floats): 8 waves x 64 bias floats
 constexpr int P8_LDS = P8_BIAS + 2048;
 
-template <int H>
-using IC = std::integral_constant<int, H>;
-
-// LDS image of a K-contiguous half-tile: [128 rows][128 B], 16-byte chunk c of row r at position c ^ ((r >> 1) & 7).  The
-// ds_read_b128 lane groups (16 lanes: rows fr of one parity pair set, chunk 4 kk + fq) then cover all 64 banks once, and -- unlike
-// swz() of gemm_shared.h, whose (r >> 4) term serves register-staged transposed writes -- the address of fragment i is the
-// address of fragment 0 plus 2048 i: one address register per operand and k half instead of one per fragment.
-__device__ __forceinline__ int p8_swz(int row, int chunk) { return row * ROW_BYTES + (((chunk ^ (row >> 1)) & 7) << 4); }
 
 // PERSISTENT: grid = one workgroup per CU; a workgroup walks tiles L = blockIdx.x, + gridDim.x, ... (same XCD-chunked order as
 // the one-tile-per-workgroup kernels).  After the K loop of a tile the first seven half-tiles of the NEXT tile are requested
@@ -62,7 +54,7 @@ __global__ void __launch_bounds__(512, 2) gemm_p8_kernel(const GemmArgs g) {
   const int fr = lane & 15, fq = lane >> 4;
   const int nblk = g.tiles_m * g.tiles_n;
   const int nk = g.K >> 6;
-  auto tile_of = [&](int L) __attribute__((always_inline)) {  // XCD-aware tile order as in gemm_kernel
+  auto tile_of = [&](int L) __attribute__((always_inline)) {  // XCD-aware tile order as in gemm_kernel (gemm.hip)
     const int xcd = L & 7, loc = L >> 3;
     const int q = nblk >> 3, rm = nblk & 7;
     return (xcd < rm ? xcd * (q + 1) : rm * (q + 1) + (xcd - rm) * q) + loc;
@@ -407,20 +399,11 @@ int p8_cus_impl() {
 
 template <typename TC, int EPI, bool TB>
 int launch_p8(GemmArgs g, hipStream_t st) {
-  auto kern = gemm_p8_kernel<TC, EPI, TB>;
-  static unsigned char done[UWU_MAX_DEV];
-  if (!uwu_func_lds(reinterpret_cast<const void*>(kern), P8_LDS, done)) {
-    uwu_set_error("gemm_p8: the device cannot give a workgroup %d bytes of LDS", P8_LDS);
-    return UWU_ELAUNCH;
-  }
   g.tiles_m = (g.M + 255) / 256;
   g.tiles_n = (g.N + 255) / 256;
   const int nblk = g.tiles_m * g.tiles_n, ncu = p8_cus_impl();
-  UwuProfScope prof(st);
-  hipLaunchKernelGGL(kern, dim3(nblk < ncu ? nblk : ncu), dim3(512), P8_LDS, st, g);
-  prof.done(gemm_tag(g, TB, false), 0, 2.0 * g.M * g.N * g.K, gemm_bytes(g, 2, sizeof(TC)));
-  UWU_LAUNCH_CHECK("gemm_p8");
-  return UWU_OK;
+  return gemm_launch<gemm_p8_kernel<TC, EPI, TB>>("gemm_p8", P8_LDS, dim3(nblk < ncu ? nblk : ncu), 512, st,
+                                                 gemm_prof(g, TB, sizeof(TC)), g);
 }
 
 }  // namespace

@@ -1,6 +1,6 @@
 // 256 x 256 fp8 (block-scaled MFMA, unit block scales) GEMM for the fp8 Linears of DiT-XL/2 (BASELINE config 5; reference: the
 // nn.Linear fwd / bwd inside the transformer blocks, src/duwu/modules/rope_unet.py:122-166, 393-411, under the reference's fp8
-// autocast): the 8-phase schedule of gemm_p8.hip on fp8 operands.  gemm_f8_kernel (gemm.hip) runs the same tile as a two-stage
+// autocast): the 8-phase schedule of gemm_p8.hip on fp8 operands.  gemm_f8_kernel (gemm_f8.hip) runs the same tile as a two-stage
 // loop with one vmcnt(0) + barrier per K step -- at twice the MFMA rate of bf16 a K step is half as long and the exposed latency
 // per step weighs twice as much (0.22 - 0.40 of the 5 PFLOP/s fp8 peak at the DiT-XL/2 shapes).
 //
@@ -18,8 +18,6 @@
 // of units an XCD walks stays inside one or two slices (their operand ranges share that XCD's L2).
 #include "gemm_shared.h"
 
-int uwu_p8_cus();  // gemm_p8.hip
-
 namespace {
 
 constexpr int P8_HT = 128 * ROW_BYTES;  // half-tile: 128 rows x 128 B
@@ -28,14 +26,6 @@ constexpr int P8_BIAS = P8_RING;       // 8 waves x 64 bias floats
 constexpr int P8_LDS = P8_BIAS + 2048;
 typedef int fi32x8 __attribute__((ext_vector_type(8)));
 
-template <int H>
-using IC = std::integral_constant<int, H>;
-
-// LDS image of a K-contiguous half-tile: [128 rows][128 B], 16-byte chunk c of row r at position c ^ ((r >> 1) & 7).  The
-// ds_read_b128 lane groups (16 lanes: rows fr of one parity pair set, chunk 4 kk + fq) then cover all 64 banks once, and -- unlike
-// swz() of gemm_shared.h, whose (r >> 4) term serves register-staged transposed writes -- the address of fragment i is the
-// address of fragment 0 plus 2048 i: one address register per operand and k half instead of one per fragment.
-__device__ __forceinline__ int p8_swz(int row, int chunk) { return row * ROW_BYTES + (((chunk ^ (row >> 1)) & 7) << 4); }
 
 // PERSISTENT: grid = one workgroup per CU; a workgroup walks units L = blockIdx.x, + gridDim.x, ... exactly as gemm_p8_kernel
 // (see there for the tile-boundary argument: the next tile's first seven half-tiles are requested before this tile's results
@@ -54,7 +44,7 @@ __global__ void __launch_bounds__(512, 2) gemm_p8f_kernel(const GemmArgs g, cons
   const int nblk = PART ? ntile * g.wide : ntile;   // units of work (PART: g.wide K slices per tile, slice-major)
   const int nk = PART ? g.k_tiles_per_split : g.K >> 7;  // K steps of 128 fp8 per unit
   const float alpha = 1.f / (scale_a[0] * scale_b[0]);
-  auto tile_of = [&](int L) __attribute__((always_inline)) {  // XCD-aware tile order as in gemm_kernel
+  auto tile_of = [&](int L) __attribute__((always_inline)) {  // XCD-aware tile order as in gemm_kernel (gemm.hip)
     const int xcd = L & 7, loc = L >> 3;
     const int q = nblk >> 3, rm = nblk & 7;
     return (xcd < rm ? xcd * (q + 1) : rm * (q + 1) + (xcd - rm) * q) + loc;
@@ -382,12 +372,8 @@ __global__ void __launch_bounds__(512, 2) gemm_p8f_kernel(const GemmArgs g, cons
 
 template <typename TC, int EPI, int FA, bool PART>
 int launch_p8f(GemmArgs g, const float* sa, const float* sb, hipStream_t st) {
-  auto kern = gemm_p8f_kernel<TC, EPI, FA, PART>;
-  static unsigned char done[UWU_MAX_DEV];
-  if (!uwu_func_lds(reinterpret_cast<const void*>(kern), P8_LDS, done)) {
-    uwu_set_error("gemm_p8f: the device cannot give a workgroup %d bytes of LDS", P8_LDS);
-    return UWU_ELAUNCH;
-  }
+  constexpr auto kern = gemm_p8f_kernel<TC, EPI, FA, PART>;
+  RETURN_IF(gemm_lds_optin<kern>("gemm_p8f", P8_LDS));  // (the profiler scope is the caller's: uwu_gemm_fp8, gemm_f8.hip)
   const int units = g.tiles_m * g.tiles_n * (PART ? g.wide : 1), ncu = uwu_p8_cus();
   hipLaunchKernelGGL(kern, dim3(units < ncu ? units : ncu), dim3(512), P8_LDS, st, g, sa, sb);
   UWU_LAUNCH_CHECK("gemm_p8f");
@@ -449,7 +435,7 @@ bool uwu_gemm_p8f_part_ok(const GemmArgs& g) {
   return uwu_gemm_p8f_split(tiles, g.K / 128) > 0;
 }
 
-// partial sums into `scratch` ([split][M][N] fp32); the caller adds them into C (launch_splitk_reduce).  Returns the slice count
+// partial sums into `scratch` ([split][M][N] fp32); the caller adds them into C (uwu_launch_splitk_reduce).  Returns the slice count
 // through g.wide.
 int uwu_launch_gemm_p8f_part(GemmArgs& g, int fmt_a, const float* sa, const float* sb, void* scratch, hipStream_t st) {
   g.tiles_m = (g.M + 255) / 256;

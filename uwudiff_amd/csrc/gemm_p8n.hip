@@ -21,8 +21,6 @@
 //     loads (plain / bias / bias + GELU; K-major W: plain) -- other cases stay on the older kernels.
 #include "gemm_shared.h"
 
-int uwu_p8_cus();  // gemm_p8.hip
-
 namespace {
 
 constexpr int N8_HT = 128 * ROW_BYTES;  // a third of W: 128 rows x 128 B = 16 KB
@@ -35,16 +33,6 @@ template <int FI> struct N8 {
   static constexpr int VM = 2 * 4 + APIECES;               // DMA instructions of the five youngest requests (always one A among them)
 };
 
-template <int H>
-using IC = std::integral_constant<int, H>;
-
-__device__ __forceinline__ int n8_swz(int row, int chunk) { return row * ROW_BYTES + (((chunk ^ (row >> 1)) & 7) << 4); }  // = p8_swz
-
-template <int N>
-__device__ __forceinline__ void n8_wait_vm() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
 template <typename TC, int EPI, bool TB, int FI>
 __global__ void __launch_bounds__(512, 2) gemm_p8n_kernel(const GemmArgs g) {
   typedef N8<FI> G;
@@ -56,7 +44,7 @@ __global__ void __launch_bounds__(512, 2) gemm_p8n_kernel(const GemmArgs g) {
   const int fr = lane & 15, fq = lane >> 4;
   const int nblk = g.tiles_m * g.tiles_n;
   const int nk = g.K >> 6;  // even, >= 4 (checked on the host)
-  auto tile_of = [&](int L) __attribute__((always_inline)) {  // XCD-aware tile order as in gemm_kernel
+  auto tile_of = [&](int L) __attribute__((always_inline)) {  // XCD-aware tile order as in gemm_kernel (gemm.hip)
     const int xcd = L & 7, loc = L >> 3;
     const int q = nblk >> 3, rm = nblk & 7;
     return (xcd < rm ? xcd * (q + 1) : rm * (q + 1) + (xcd - rm) * q) + loc;
@@ -83,7 +71,7 @@ __global__ void __launch_bounds__(512, 2) gemm_p8n_kernel(const GemmArgs g) {
 #pragma unroll
     for (int q = 0; q < NOA; ++q) {
       const int row = 8 * (wave + 8 * q) + (lane_ >> 3);
-      const int c = ((lane_ & 7) ^ (row >> 1)) & 7;  // logical chunk that must land at position lane & 7 (n8_swz)
+      const int c = ((lane_ & 7) ^ (row >> 1)) & 7;  // logical chunk that must land at position lane & 7 (p8_swz)
       int ga = row;
       if (ga >= g.M - m0) ga = g.M - m0 - 1;  // (clamped rows / columns: their products are never stored)
       oa[q] = (unsigned)(ga * g.lda + 8 * c) * 2u;
@@ -128,8 +116,8 @@ __global__ void __launch_bounds__(512, 2) gemm_p8n_kernel(const GemmArgs g) {
   unsigned a_ad[2], b_ad[2];  // [kk]: fragment 0 (A rows 16 FI grp + fr of the A element, B rows 32 wc + fr of third 0); fragment i: + 2048 i
 #pragma unroll
   for (int kk = 0; kk < 2; ++kk) {
-    a_ad[kk] = smem_base + 3 * N8_HT + (unsigned)n8_swz(16 * FI * grp + fr, 4 * kk + fq);
-    b_ad[kk] = smem_base + (unsigned)n8_swz(32 * wc + fr, 4 * kk + fq);
+    a_ad[kk] = smem_base + 3 * N8_HT + (unsigned)p8_swz(16 * FI * grp + fr, 4 * kk + fq);
+    b_ad[kk] = smem_base + (unsigned)p8_swz(32 * wc + fr, 4 * kk + fq);
   }
   unsigned bt_ad[2][2];  // TB: [fragment j][transposed read t] inside a [32 k][128 n] sub-image
 #pragma unroll
@@ -232,11 +220,11 @@ __global__ void __launch_bounds__(512, 2) gemm_p8n_kernel(const GemmArgs g) {
   // instructions (+ `st` stores of the previous tile that were issued behind it) may stay in flight; `all` = every one of the five
   // younger requests exists (else: the tail of the workgroup's last tile -- drain)
   auto wait_next = [&](bool all, int st) __attribute__((always_inline)) {
-    if (!all) n8_wait_vm<0>();
-    else if (st == 0) n8_wait_vm<G::VM>();
-    else if (st == 1) n8_wait_vm<G::VM + SPT>();
-    else if (st == 2) n8_wait_vm<G::VM + 2 * SPT>();
-    else n8_wait_vm<G::VM + 3 * SPT>();
+    if (!all) r_wait_vm<0>();
+    else if (st == 0) r_wait_vm<G::VM>();
+    else if (st == 1) r_wait_vm<G::VM + SPT>();
+    else if (st == 2) r_wait_vm<G::VM + 2 * SPT>();
+    else r_wait_vm<G::VM + 3 * SPT>();
   };
 
   // One K step (parity PAR static); kt: K step inside the tile.
@@ -308,7 +296,7 @@ __global__ void __launch_bounds__(512, 2) gemm_p8n_kernel(const GemmArgs g) {
   issue(IC<0>{}, IC<1>{}, 1);
   issue(IC<1>{}, IC<1>{}, 1);
   issue(IC<2>{}, IC<1>{}, 1);
-  n8_wait_vm<G::VM>();  // (0, B0) and (0, A) have landed: the five requests behind them may fly
+  r_wait_vm<G::VM>();  // (0, B0) and (0, A) have landed: the five requests behind them may fly
   bar();
   if (grp == 1) bar();  // waves 4-7 run one barrier behind their SIMD partners
   for (;;) {
@@ -334,20 +322,11 @@ __global__ void __launch_bounds__(512, 2) gemm_p8n_kernel(const GemmArgs g) {
 
 template <typename TC, int EPI, bool TB, int FI>
 int launch_p8n_fi(GemmArgs g, hipStream_t st) {
-  auto kern = gemm_p8n_kernel<TC, EPI, TB, FI>;
-  static unsigned char done[UWU_MAX_DEV];
-  if (!uwu_func_lds(reinterpret_cast<const void*>(kern), N8<FI>::LDS, done)) {
-    uwu_set_error("gemm_p8n: the device cannot give a workgroup %d bytes of LDS", N8<FI>::LDS);
-    return UWU_ELAUNCH;
-  }
   g.tiles_m = (g.M + 32 * FI - 1) / (32 * FI);
   g.tiles_n = g.N / 384;
   const int nblk = g.tiles_m * g.tiles_n, ncu = uwu_p8_cus();
-  UwuProfScope prof(st);
-  hipLaunchKernelGGL(kern, dim3(nblk < ncu ? nblk : ncu), dim3(512), N8<FI>::LDS, st, g);
-  prof.done(gemm_tag(g, TB, false), 0, 2.0 * g.M * g.N * g.K, gemm_bytes(g, 2, sizeof(TC)));
-  UWU_LAUNCH_CHECK("gemm_p8n");
-  return UWU_OK;
+  return gemm_launch<gemm_p8n_kernel<TC, EPI, TB, FI>>("gemm_p8n", N8<FI>::LDS, dim3(nblk < ncu ? nblk : ncu), 512, st,
+                                                      gemm_prof(g, TB, sizeof(TC)), g);
 }
 
 // 192-row tiles unless the 128-row grid fills the chip and the 192-row one does not

@@ -1,6 +1,7 @@
-// Shared pieces of the MFMA GEMM kernels (gemm.hip, gemm_p8.hip): argument block, LDS images + LDS-DMA staging,
-// fragment reads and the epilogue of one wave tile.  Everything but GemmArgs lives in an anonymous namespace:
-// each translation unit gets its own copy.
+// Shared pieces of the MFMA GEMM kernels (gemm.hip, gemm_as.hip, gemm_wgrad.hip, gemm_f8.hip, gemm_p8*.hip): argument block,
+// LDS images + LDS-DMA staging, fragment reads, the epilogue of one wave tile and the host-side launch helper.  Everything but
+// GemmArgs and the cross-file host functions declared at the end lives in an anonymous namespace: each translation unit gets
+// its own copy.
 #pragma once
 #include <stdlib.h>
 
@@ -8,9 +9,9 @@
 
 #include "common.h"
 
-#define RETURN_IF(expr)            \
+#define RETURN_IF(...)             \
   do {                             \
-    const int rc_ = (expr);        \
+    const int rc_ = (__VA_ARGS__); \
     if (rc_ != UWU_OK) return rc_; \
   } while (0)
 
@@ -417,6 +418,26 @@ template <int N>
 __device__ __forceinline__ void r_wait_vm() {
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
+// One LDS-DMA wave-instruction (64 lanes x 16 bytes to lds_dst .. + 1023) as inline asm, m0 set and restored inside the statement:
+// invisible to hipcc, which then neither waits vmcnt(0) in front of visible LDS reads nor drains the ring at a barrier; the
+// caller counts vmcnt by hand (gemm_trw_kernel, gemm_as_kernel).
+__device__ __forceinline__ void glds16_asm(const void* gsrc, unsigned lds_dst /* wave-uniform */) {
+  unsigned keep;
+  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+               : "=&s"(keep)
+               : "v"(gsrc), "s"(lds_dst)
+               : "memory");
+}
+// ---- the 8-phase kernels (gemm_p8.hip, gemm_p8n.hip, gemm_p8f.hip) -------------------------------------------------------------
+// compile-time index that a lambda can take as an argument
+template <int H>
+using IC = std::integral_constant<int, H>;
+// LDS image of a K-contiguous half-tile: [128 rows][128 B], 16-byte chunk c of row r at position c ^ ((r >> 1) & 7).  The
+// ds_read_b128 lane groups (16 lanes: rows fr of one parity pair set, chunk 4 kk + fq) then cover all 64 banks once, and -- unlike
+// swz() above, whose (r >> 4) term serves register-staged transposed writes -- the address of fragment i is the
+// address of fragment 0 plus 2048 i: one address register per operand and k half instead of one per fragment.
+__device__ __forceinline__ int p8_swz(int row, int chunk) { return row * ROW_BYTES + (((chunk ^ (row >> 1)) & 7) << 4); }
+
 // transposing LDS read (4 x 16 block of b16 per 16 lanes, delivered column-major); EXEC must be all ones
 template <int OFF>
 __device__ __forceinline__ uint2 t_read_tr(unsigned addr) {
@@ -452,10 +473,55 @@ static double gemm_bytes(const GemmArgs& g, int es, int esc) {
   return b;
 }
 
+// ---- launching (host) -----------------------------------------------------------------------------------------------------
+// Opt-in to `lds` bytes of dynamic LDS for KERN, once per device.  `name` is the kernel family in the error text.
+template <auto KERN>
+int gemm_lds_optin(const char* name, int lds) {
+  static unsigned char done[UWU_MAX_DEV];
+  if (uwu_func_lds(reinterpret_cast<const void*>(KERN), lds, done)) return UWU_OK;
+  uwu_set_error("%s: the device cannot give a workgroup %d bytes of LDS", name, lds);
+  return UWU_ELAUNCH;
+}
+// what the live profiler records for a launch
+struct GemmProf {
+  int tag, kind;  // UWU_PROF_*; operand kind 0 = bf16 / fp8, 1 = fp32
+  double flops, bytes;
+};
+// the record of a bf16 Linear launch, forward or (tb) input gradient; esc = bytes per output element
+static GemmProf gemm_prof(const GemmArgs& g, bool tb, int esc) {
+  return {gemm_tag(g, tb, false), 0, 2.0 * g.M * g.N * g.K, gemm_bytes(g, 2, esc)};
+}
+// One kernel launch: LDS opt-in, profiler scope around the launch, launch check.  A launcher that puts more than one kernel
+// into its profiler scope (split-K + reduce) calls gemm_lds_optin and writes the rest itself.
+template <auto KERN, typename... Args>
+int gemm_launch(const char* name, int lds, dim3 grid, int block, hipStream_t st, const GemmProf& p, const Args&... args) {
+  RETURN_IF(gemm_lds_optin<KERN>(name, lds));
+  UwuProfScope prof(st);
+  hipLaunchKernelGGL(KERN, grid, dim3(block), lds, st, args...);
+  prof.done(p.tag, p.kind, p.flops, p.bytes);
+  UWU_LAUNCH_CHECK(name);
+  return UWU_OK;
+}
 
 }  // namespace
+
+// ---- host functions that cross translation units (C++ linkage; the kernels themselves stay file-local) -----------------------
+// A launcher that is a template is DECLARED here and explicitly instantiated in its kernel's file: the caller names the
+// instantiation it wants, the kernel is compiled once, and a combination nobody instantiated fails at link time.
+// gemm_as.hip: the A-stationary K = 384 kernel and its rules (out_bytes: size of an output element)
+bool uwu_gemm_use_as(const GemmArgs& g, int out_bytes);
+bool uwu_gemm_use_as_bias();
+template <typename TC, int EPI> int uwu_launch_gemm_as(GemmArgs g, hipStream_t st);
+// gemm.hip: geometry of a 3x3 convolution (padding 1) and the zero page of its padded pixels, for the CONV / CONVW kernels
+int uwu_conv3x3_args(GemmArgs& g, int B, int H, int W, int C, int stride);
+// gemm_wgrad.hip: the streaming weight-gradient kernel (0 = not taken, 1 = <8, 4>: 256x128 tiles, 2 = <4, 8>: 128x256) and the
+// sum of split-K slices `part` [split][M][N] into C
+int uwu_gemm_pick_tr(const GemmArgs& g);
+template <int FI, int FJ, bool CONVW = false> int uwu_launch_gemm_tr(GemmArgs g, void* scratch, size_t scratch_bytes, hipStream_t st);
+void uwu_launch_splitk_reduce(const float* part, float* C, int M, int N, int ldc, int split, hipStream_t st);
 // the 8-phase 256 x 256 kernel (gemm_p8.hip): returns UWU_OK / error; `tb` = B is [K][N] (input gradients)
 int uwu_launch_gemm_p8(const GemmArgs& g, bool tb, hipStream_t st);
+int uwu_p8_cus();  // workgroups of a persistent grid: one per CU, a multiple of 8
 bool uwu_gemm_p8_ok(const GemmArgs& g, bool tb);
 // its 128 x 384 sibling (gemm_p8n.hip): N a multiple of 384
 int uwu_launch_gemm_p8n(const GemmArgs& g, bool tb, hipStream_t st);

@@ -1,4 +1,4 @@
-// fp8 quantisation for the block-scaled-MFMA GEMM path (gemm.hip: gemm_f8_kernel; BASELINE config 5).
+// fp8 quantisation for the block-scaled-MFMA GEMM path (gemm_f8.hip: gemm_f8_kernel; BASELINE config 5).
 //
 // Per-tensor scaling: x_fp8 = sat(x * scale), scale = FMT_MAX / amax.  Two policies share the kernels:
 //   * just-in-time: uwu_fp8_amax -> uwu_fp8_update_scales -> uwu_fp8_quantize   (two passes over x; parity tests, step 0)
