@@ -64,9 +64,10 @@ class DMTrainer(BaseTrainer):
                          warm_up_period=warm_up_period)
         self.unet = load_any(model_config["unet"])
         self.te = load_any(model_config["te"]) if model_config.get("te") is not None else None
-        # trainer.py:136,241-244: any frozen module with `.encode(x).latent_dist.sample()` (diffusers.AutoencoderKL needs
-        # hub weights; `uwudiff_amd.conditioning.SyntheticVAE` is the offline stand-in).  The (x - mean) / std step that
-        # follows the encoder is folded into the loss's q-sample kernel.
+        # trainer.py:136,241-244: any frozen module with `.encode(x).latent_dist.sample()`: `diffusers.AutoencoderKL` resolves to
+        # `uwudiff_amd.vae.AutoencoderKL` (the SDXL VAE on the HIP kernels; hub names give seeded random weights), and
+        # `uwudiff_amd.conditioning.SyntheticVAE` is the 8x-pooling stand-in.  The (x - mean) / std step that follows the
+        # encoder is folded into the loss's q-sample kernel.
         self.vae = load_any(model_config["vae"]) if model_config.get("vae") is not None else None
         if self.vae is not None:
             self.vae.requires_grad_(False).eval()

@@ -99,6 +99,12 @@ int uwu_draw_timesteps(int64_t* timesteps, int n_train, int B, uint64_t seed, ui
 int uwu_draw_u01(float* u01, int B, uint64_t seed, uint64_t offset, void* stream);
 int uwu_qsample_draw(const float* x, const float* coef, int B, int64_t n, int use_norm, float vae_mean, float vae_std,
                      float* x_norm, float* noise, float* noisy, uint64_t seed, uint64_t offset, void* stream);
+/* AutoencoderKL posterior: moments fp32 channels-last [B*HW][ldm] (mean in channels 0 .. latent-1, logvar in latent .. 2 latent-1)
+ * -> fp32 NCHW [B, latent, HW]:  z = mean + exp(0.5 clamp(logvar, -30, 20)) * eps, element i of z taking element i of
+ * uwu_philox_normal(B*latent*HW, seed, offset);  mean_out / logvar_out (clamped) are the same moments as NCHW.  Each of the three
+ * outputs may be null (at least one is not); nothing is drawn when z is null.  B*latent*HW must be a multiple of 4. */
+int uwu_posterior_draw(const float* moments, int ldm, int B, int latent, int64_t HW, float* z, float* mean_out, float* logvar_out,
+                       uint64_t seed, uint64_t offset, void* stream);
 
 /* Conditioning front-end, text_encoders.py:196-262: place one text encoder's hidden states src [B,S,F] (fp32 / bf16),
  * times its attention mask [B,S] (int64, may be NULL: zero_for_padding off or no mask), into the zero-filled context
@@ -264,6 +270,15 @@ int uwu_gemm_fp8_emit(const void* A, const void* B, void* C, float* colsum, cons
 int uwu_conv3x3_implicit_ok(int B, int H, int W, int C, int Cout, int stride, int dtype);
 int uwu_conv3x3_fwd(const void* x, const void* w, const float* bias, void* y, int B, int H, int W, int C, int Cout,
                     int stride, int dtype, void* stream);
+/* 3x3 / stride 2 convolution padded RIGHT AND BOTTOM only, forward (the AutoencoderKL encoder's downsampler: F.pad(x, (0,1,0,1)),
+ * then stride 2 / padding 0):  y[b,oy,ox,:] = bias + sum_{ky,kx} w[:,ky,kx,:] . x[b, 2 oy + ky, 2 ox + kx, :], zero where the index
+ * reaches H or W;  Ho = (H - 2) / 2 + 1, Wo likewise (H, W >= 2).  Same layouts as uwu_conv3x3_fwd.  bf16 shapes with C and Cout
+ * multiples of 32 and B*Ho*Wo a multiple of 32 run as an implicit GEMM and need no workspace; every other shape (bf16 with
+ * C % 8 == 0, fp32 with C % 4 == 0) gathers a [B*Ho*Wo, 9*C] column matrix into ws and runs uwu_gemm on it.
+ * uwu_conv3x3_s2br_ws_bytes: the workspace that shape needs (0: none, or a shape the entry point refuses). */
+size_t uwu_conv3x3_s2br_ws_bytes(int B, int H, int W, int C, int Cout, int dtype);
+int uwu_conv3x3_s2br_fwd(const void* x, const void* w, const float* bias, void* y, int B, int H, int W, int C, int Cout, int dtype,
+                         void* ws, size_t ws_bytes, void* stream);
 int uwu_conv3x3_dgrad(const void* dy, const void* w, void* dx, int B, int H, int W, int C, int Cout, int stride, int dtype,
                       void* stream);
 size_t uwu_conv3x3_wgrad_scratch_bytes(int C, int Cout, int64_t Mo);
@@ -370,6 +385,11 @@ int uwu_add_ln_modulate_bwd(const void* dh, const void* x, const float* mean, co
  * lse: fp32 [B,H,Tq] log-sum-exp of the scaled scores (saved for backward). */
 int uwu_attention_fwd(const void* q, const void* k, const void* v, void* o, float* lse, int B, int Tq, int Tk,
                       int H, int d, int ldq, int ldk, int ldv, int ldo, float scale, int dtype, void* stream);
+/* One head of width 512, Tq = Tk = T >= 1, forward only, no lse (the AutoencoderKL mid-block attention): q/k/v/o [B*T, >= 512]
+ * with row strides ld* (multiples of 8 for bf16, 4 for fp32; 16-byte aligned bases).  bf16: MFMA flash kernel with online
+ * softmax, no T x T tensor in memory; fp32: exact-fp32 VALU kernel. */
+int uwu_attention_d512_fwd(const void* q, const void* k, const void* v, void* o, int B, int T, int ldq, int ldk, int ldv, int ldo,
+                           float scale, int dtype, void* stream);
 /* dq/dk/dv use the strides of q/k/v; dO uses ldo.  delta: fp32 workspace [B,H,Tq] (rowsum(dO*O)). */
 int uwu_attention_bwd(const void* q, const void* k, const void* v, const void* o, const void* dO,
                       const float* lse, float* delta, void* dq, void* dk, void* dv, int B, int Tq, int Tk, int H,
@@ -441,6 +461,13 @@ int uwu_groupnorm_fwd(const void* x, const float* gamma, const float* beta, void
                       int B, int HW, int C, int G, float eps, int silu, int dtype, void* stream);
 /* dgamma/dbeta are accumulated (fp32 atomics); either may be NULL (a frozen norm).  ws: fp32 scratch of 2*B*G floats.
  * Both directions: C % 8 == 0, C <= 4096, 16-byte aligned tensors (whole-row vector accesses). */
+/* uwu_groupnorm_fwd with a fixed summation order: per-workgroup partial sums in ws (uwu_groupnorm_fwd_det_ws_bytes), added in
+ * ascending order, the row partition a function of the image alone.  The statistics of a sample, and so y, are the same bits
+ * between launches and between batch sizes (the atomics of uwu_groupnorm_fwd give agreement to fp32 rounding only).  Same
+ * shapes and refusals as uwu_groupnorm_fwd. */
+size_t uwu_groupnorm_fwd_det_ws_bytes(int B, int HW, int C, int G);
+int uwu_groupnorm_fwd_det(const void* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd, void* ws,
+                          size_t ws_bytes, int B, int HW, int C, int G, float eps, int silu, int dtype, void* stream);
 int uwu_groupnorm_bwd(const void* dy, const void* x, const float* mean, const float* rstd, const float* gamma,
                       const float* beta, void* dx, float* dgamma, float* dbeta, float* ws, int B, int HW, int C, int G,
                       int silu, int dtype, void* stream);

@@ -207,6 +207,8 @@ __global__ void __launch_bounds__(256, 2) gemm_kernel(const GemmArgs g) {
 //   CONV = 1 forward:  Y[(b,oy,ox), co] = sum_{tap,c} X[b, oy s + ky - 1, ox s + kx - 1, c] W[co][tap][c]   (TB = 0)
 //   CONV = 2 dgrad:    dX[(b,iy,ix), c] = sum_{tap,co} dY[b, (iy + 1 - ky) / s, (ix + 1 - kx) / s, co] W[co][tap][c]
 //                      (TB = 1: for a fixed tap the weight is a [co][c] matrix with row stride 9 C)
+//   CONV = 3 forward, stride 2, padded right and bottom only (the AutoencoderKL encoder's downsampler):
+//                      Y[(b,oy,ox), co] = sum_{tap,c} X[b, 2 oy + ky, 2 ox + kx, c] W[co][tap][c], zero where the index reaches H or W
 template <typename TC, int EPI, bool TB, int FI, int CONV = 0>
 __global__ void __launch_bounds__(256, 2) gemm_r3_kernel(const GemmArgs g) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -245,8 +247,8 @@ __global__ void __launch_bounds__(256, 2) gemm_r3_kernel(const GemmArgs g) {
       pa[q] = static_cast<const T*>(g.A) + (int64_t)row * g.lda + 8 * csrc;
     } else {
       // rows of this GEMM = pixels of the (CONV 1: output, CONV 2: input) image; the gathered tensor is the other one
-      const int RH = CONV == 1 ? g.cHo : g.cH, RW = CONV == 1 ? g.cWo : g.cW;  // row image
-      const int GH = CONV == 1 ? g.cH : g.cHo, GW = CONV == 1 ? g.cW : g.cWo;  // gathered image
+      const int RH = CONV != 2 ? g.cHo : g.cH, RW = CONV != 2 ? g.cWo : g.cW;  // row image
+      const int GH = CONV != 2 ? g.cH : g.cHo, GW = CONV != 2 ? g.cW : g.cWo;  // gathered image
       int b, rem, y, x;
       divmod24(row < g.M ? row : 0, RH * RW, 1.f / (float)(RH * RW), b, rem);
       divmod24(rem, RW, 1.f / (float)RW, y, x);
@@ -287,6 +289,10 @@ __global__ void __launch_bounds__(256, 2) gemm_r3_kernel(const GemmArgs g) {
           gy = cy[q] * g.cS + ky - 1;
           gx = cx[q] * g.cS + kx - 1;
           ok = gy >= 0 && gy < g.cH && gx >= 0 && gx < g.cW;
+        } else if constexpr (CONV == 3) {
+          gy = cy[q] * 2 + ky;
+          gx = cx[q] * 2 + kx;
+          ok = gy >= 0 && gy < g.cH && gx < g.cW;  // (gy < 0: a row past M)
         } else {
           const int ty = cy[q] + 1 - ky, tx = cx[q] + 1 - kx;
           ok = ty >= 0 && tx >= 0;
@@ -300,7 +306,7 @@ __global__ void __launch_bounds__(256, 2) gemm_r3_kernel(const GemmArgs g) {
           }
           ok = ok && gy < g.cHo && gx < g.cWo;
         }
-        const int GW = CONV == 1 ? g.cW : g.cWo;
+        const int GW = CONV != 2 ? g.cW : g.cWo;
         const T* src = ok ? pa[q] + (int64_t)(gy * GW + gx) * g.lda + 32 * ch : zsrc;
         __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
                                          (__attribute__((address_space(3))) void*)(st + q * 4096), 16, 0, 0);
@@ -1006,6 +1012,61 @@ extern "C" int uwu_conv3x3_dgrad(const void* dy, const void* w, void* dx, int B,
   g.epi = UWU_EPI_NONE;
   g.wide = (C % 8 == 0) ? 1 : 0;
   return launch_r3<bf16_t, UWU_EPI_NONE, true, 8, 2>(g, (hipStream_t)stream);
+}
+
+// ---- 3x3 / stride 2 convolution padded right and bottom only: F.pad(x, (0, 1, 0, 1)) + conv2d(stride 2, padding 0) -------------
+// (forward only; the AutoencoderKL encoder's downsamplers.)  Ho = (H - 2) / 2 + 1.  bf16 shapes that meet the ring kernel's
+// conditions run as the implicit GEMM above with the CONV = 3 pixel map; every other shape gathers the column matrix into the
+// caller's workspace (uwu_conv3x3_s2br_ws_bytes) and runs uwu_gemm on it (bf16 or fp32).
+int uwu_im2col3x3_s2br(const void* x, void* col, int B, int H, int W, int C, int dtype, hipStream_t st);  // unet_ops.hip
+
+static bool conv_s2br_implicit(int B, int H, int W, int C, int Cout, int dtype) {
+  if (dtype != UWU_BF16 || C % 32 || Cout % 32 || C < 32 || Cout < 32) return false;
+  const int Ho = (H - 2) / 2 + 1, Wo = (W - 2) / 2 + 1;
+  const int64_t Mi = (int64_t)B * H * W, Mo = (int64_t)B * Ho * Wo;
+  return Mi < (1 << 24) && Mo % 32 == 0 && 9 * (int64_t)C < (1 << 24);
+}
+
+static bool conv_s2br_shape_ok(int B, int H, int W, int C, int Cout, int dtype) {
+  if (dtype != UWU_BF16 && dtype != UWU_F32) return false;
+  const int epc = dtype == UWU_BF16 ? 8 : 4;
+  if (B <= 0 || H < 2 || W < 2 || C <= 0 || Cout <= 0 || C % epc) return false;
+  return (int64_t)B * H * W < ((int64_t)1 << 31) / 9 && (int64_t)B * H * W * C < ((int64_t)1 << 40);
+}
+
+extern "C" size_t uwu_conv3x3_s2br_ws_bytes(int B, int H, int W, int C, int Cout, int dtype) {
+  if (!conv_s2br_shape_ok(B, H, W, C, Cout, dtype) || conv_s2br_implicit(B, H, W, C, Cout, dtype)) return 0;
+  const int Ho = (H - 2) / 2 + 1, Wo = (W - 2) / 2 + 1;
+  return (size_t)B * Ho * Wo * 9 * C * (dtype == UWU_BF16 ? 2 : 4);
+}
+
+extern "C" int uwu_conv3x3_s2br_fwd(const void* x, const void* w, const float* bias, void* y, int B, int H, int W, int C, int Cout,
+                                    int dtype, void* ws, size_t ws_bytes, void* stream) {
+  UWU_CHECK_ARG(x && w && y, "conv3x3_s2br_fwd: null pointer");
+  UWU_CHECK_ARG(conv_s2br_shape_ok(B, H, W, C, Cout, dtype),
+                "conv3x3_s2br_fwd: bad shape B=%d H=%d W=%d C=%d Cout=%d dtype=%d (H, W >= 2; C a multiple of 8 (bf16) / 4 (fp32))", B, H, W, C,
+                Cout, dtype);
+  UWU_CHECK_ARG((((uintptr_t)x | (uintptr_t)w | (uintptr_t)y) & 15) == 0 && (!bias || ((uintptr_t)bias & 15) == 0),
+                "conv3x3_s2br_fwd: misaligned tensor");
+  const int Ho = (H - 2) / 2 + 1, Wo = (W - 2) / 2 + 1;
+  hipStream_t st = (hipStream_t)stream;
+  if (conv_s2br_implicit(B, H, W, C, Cout, dtype)) {
+    GemmArgs g{};
+    RETURN_IF(uwu_conv3x3_args(g, B, H, W, C, 2));
+    g.cHo = Ho; g.cWo = Wo;
+    g.A = x; g.B = w; g.C = y; g.bias = bias;
+    g.M = B * Ho * Wo; g.N = Cout; g.K = 9 * C; g.lda = C; g.ldb = 9 * C; g.ldc = Cout;
+    g.epi = bias ? UWU_EPI_BIAS : UWU_EPI_NONE;
+    g.wide = (Cout % 8 == 0) ? 1 : 0;
+    if (bias) return launch_r3<bf16_t, UWU_EPI_BIAS, false, 8, 3>(g, st);
+    return launch_r3<bf16_t, UWU_EPI_NONE, false, 8, 3>(g, st);
+  }
+  const size_t need = (size_t)B * Ho * Wo * 9 * C * (dtype == UWU_BF16 ? 2 : 4);
+  UWU_CHECK_ARG(ws && ws_bytes >= need && ((uintptr_t)ws & 15) == 0,
+                "conv3x3_s2br_fwd: this shape needs a 16-byte aligned workspace of %zu bytes (uwu_conv3x3_s2br_ws_bytes)", need);
+  RETURN_IF(uwu_im2col3x3_s2br(x, ws, B, H, W, C, dtype, st));
+  return uwu_gemm(ws, w, y, nullptr, bias, nullptr, B * Ho * Wo, Cout, 9 * C, 9 * C, 9 * C, Cout, 0, 0, 0, dtype, dtype,
+                  bias ? UWU_EPI_BIAS : UWU_EPI_NONE, 1, stream);
 }
 
 extern "C" int uwu_gemm(const void* A, const void* B, void* C, void* C2, const float* bias, const void* aux, int M,

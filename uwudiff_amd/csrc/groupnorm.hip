@@ -31,7 +31,9 @@ constexpr int GN_MAXNS = 2;       // C <= 4096
 constexpr int GN_RED = 2 * 4096;  // floats: RY * C <= 4096 channels-rows, two sums
 
 // MODE 0: v1 = x - p, v2 = (x - p)^2 (p: the group's pivot).  MODE 1: go = dy * silu'(xhat gamma + beta): v1 = go, v2 = go * xhat.
-template <typename T, int MODE>
+// DET (MODE 0, uwu_groupnorm_fwd_det): no atomics -- every workgroup stores its two group sums at [b][row chunk][group] and
+// gn_finalize_det_kernel adds the chunks in ascending order, so two launches give the same bits.
+template <typename T, int MODE, bool DET = false>
 __global__ void __launch_bounds__(256) gn_sums_kernel(const T* __restrict__ x, const T* __restrict__ dy,
                                                       const float* __restrict__ mean, const float* __restrict__ rstd,
                                                       const float* __restrict__ gamma, const float* __restrict__ beta,
@@ -133,8 +135,13 @@ __global__ void __launch_bounds__(256) gn_sums_kernel(const T* __restrict__ x, c
       t1 += r1s[c];
       t2 += r2s[c];
     }
-    atomicAdd(acc1 + b * G + tid, t1);
-    atomicAdd(acc2 + b * G + tid, t2);
+    if constexpr (DET) {
+      acc1[((int64_t)b * gridDim.x + blockIdx.x) * G + tid] = t1;
+      acc2[((int64_t)b * gridDim.x + blockIdx.x) * G + tid] = t2;
+    } else {
+      atomicAdd(acc1 + b * G + tid, t1);
+      atomicAdd(acc2 + b * G + tid, t2);
+    }
   }
 }
 
@@ -148,6 +155,27 @@ __global__ void gn_finalize_kernel(const T* __restrict__ x, float* __restrict__ 
   const float p = to_f32(x[(int64_t)b * HW * C + g * (C / G)]);
   const float md = mean[i] * inv_n;
   float var = rstd[i] * inv_n - md * md;
+  if (var < 0.f) var = 0.f;
+  mean[i] = p + md;
+  rstd[i] = 1.f / sqrtf(var + eps);
+}
+
+// part1 / part2 [b][chunk][g]: the per-workgroup sums of gn_sums_kernel<T, 0, true>, added here in a fixed order
+template <typename T>
+__global__ void gn_finalize_det_kernel(const T* __restrict__ x, const float* __restrict__ part1, const float* __restrict__ part2,
+                                       int chunks, float* __restrict__ mean, float* __restrict__ rstd, int BG, int G, int HW, int C,
+                                       float inv_n, float eps) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= BG) return;
+  const int b = i / G, g = i - b * G;
+  float s1 = 0.f, s2 = 0.f;
+  for (int k = 0; k < chunks; ++k) {
+    s1 += part1[((int64_t)b * chunks + k) * G + g];
+    s2 += part2[((int64_t)b * chunks + k) * G + g];
+  }
+  const float p = to_f32(x[(int64_t)b * HW * C + g * (C / G)]);
+  const float md = s1 * inv_n;
+  float var = s2 * inv_n - md * md;
   if (var < 0.f) var = 0.f;
   mean[i] = p + md;
   rstd[i] = 1.f / sqrtf(var + eps);
@@ -244,6 +272,31 @@ int gn_fwd(const void* x, const float* gamma, const float* beta, void* y, float*
   return UWU_OK;
 }
 
+// rows per workgroup of the deterministic forward: a function of the image alone (never of B), so a sample's statistics are
+// the same bits whatever batch it sits in; ~512 chunks per image, at least 4 iterations of RY rows each
+int gn_det_rows(int HW, int RY) {
+  int rows = (HW + 511) / 512;
+  if (rows < 4 * RY) rows = 4 * RY;
+  return rows;
+}
+
+template <typename T>
+int gn_fwd_det(const void* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd, float* ws, int B, int HW,
+               int C, int G, float eps, int silu, hipStream_t st) {
+  const GnMap m = gn_map(C);
+  const int rows = gn_det_rows(HW, m.RY), chunks = (HW + rows - 1) / rows;
+  const dim3 grid(chunks, B);
+  float* p1 = ws;
+  float* p2 = ws + (size_t)B * chunks * G;
+  hipLaunchKernelGGL((gn_sums_kernel<T, 0, true>), grid, dim3(256), 0, st, (const T*)x, (const T*)nullptr, nullptr, nullptr, gamma,
+                     beta, p1, p2, nullptr, nullptr, HW, C, G, rows, 0);
+  hipLaunchKernelGGL(gn_finalize_det_kernel<T>, dim3((B * G + 255) / 256), dim3(256), 0, st, (const T*)x, p1, p2, chunks, mean, rstd,
+                     B * G, G, HW, C, 1.f / ((float)HW * (float)(C / G)), eps);
+  hipLaunchKernelGGL((gn_apply_kernel<T, 0>), grid, dim3(256), 0, st, (const T*)x, (const T*)nullptr, mean, rstd, gamma, beta, nullptr,
+                     nullptr, (T*)y, HW, C, G, rows, silu, 0.f);
+  return UWU_OK;
+}
+
 template <typename T>
 int gn_bwd(const void* dy, const void* x, const float* mean, const float* rstd, const float* gamma, const float* beta,
            void* dx, float* dgamma, float* dbeta, float* ws, int B, int HW, int C, int G, int silu, hipStream_t st) {
@@ -275,6 +328,31 @@ extern "C" int uwu_groupnorm_fwd(const void* x, const float* gamma, const float*
   else if (dtype == UWU_BF16) rc = gn_fwd<bf16_t>(x, gamma, beta, y, mean, rstd, B, HW, C, G, eps, silu, st);
   else { uwu_set_error("groupnorm_fwd: bad dtype %d", dtype); return UWU_EINVAL; }
   UWU_LAUNCH_CHECK("groupnorm_fwd");
+  return rc;
+}
+
+// The forward with a fixed summation order (no float atomics): the statistics of a sample are bit-identical between launches and
+// between batch sizes.  ws: uwu_groupnorm_fwd_det_ws_bytes(B, HW, C, G) bytes of per-workgroup partial sums.
+extern "C" size_t uwu_groupnorm_fwd_det_ws_bytes(int B, int HW, int C, int G) {
+  if (B <= 0 || HW <= 0 || C <= 0 || G <= 0 || C % 8) return 0;
+  const int rows = gn_det_rows(HW, gn_map(C).RY);
+  return sizeof(float) * 2 * (size_t)B * ((HW + rows - 1) / rows) * G;
+}
+
+extern "C" int uwu_groupnorm_fwd_det(const void* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd, void* ws,
+                                     size_t ws_bytes, int B, int HW, int C, int G, float eps, int silu, int dtype, void* stream) {
+  UWU_CHECK_ARG(x && gamma && beta && y && mean && rstd && ws, "groupnorm_fwd_det: null pointer");
+  UWU_CHECK_ARG(B > 0 && B <= 65535 && HW > 0 && C > 0 && G > 0 && G <= 256 && C % G == 0 && C % 8 == 0 && C <= 4096,
+                "groupnorm_fwd_det: bad shape C=%d G=%d (C %% 8 == 0, C <= 4096)", C, G);
+  UWU_CHECK_ARG((((uintptr_t)x | (uintptr_t)y) & 15) == 0 && ((uintptr_t)ws & 3) == 0, "groupnorm_fwd_det: x / y must be 16-byte aligned");
+  UWU_CHECK_ARG(ws_bytes >= uwu_groupnorm_fwd_det_ws_bytes(B, HW, C, G), "groupnorm_fwd_det: workspace of %zu bytes is too small",
+                ws_bytes);
+  hipStream_t st = (hipStream_t)stream;
+  int rc;
+  if (dtype == UWU_F32) rc = gn_fwd_det<float>(x, gamma, beta, y, mean, rstd, (float*)ws, B, HW, C, G, eps, silu, st);
+  else if (dtype == UWU_BF16) rc = gn_fwd_det<bf16_t>(x, gamma, beta, y, mean, rstd, (float*)ws, B, HW, C, G, eps, silu, st);
+  else { uwu_set_error("groupnorm_fwd_det: bad dtype %d", dtype); return UWU_EINVAL; }
+  UWU_LAUNCH_CHECK("groupnorm_fwd_det");
   return rc;
 }
 

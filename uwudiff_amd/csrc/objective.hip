@@ -153,6 +153,38 @@ __global__ void qsample_draw_kernel(const float* __restrict__ x, const float* __
   }
 }
 
+// AutoencoderKL posterior (DiagonalGaussianDistribution): the encoder's moments are channels-last fp32 rows [B*HW][ldm] holding
+// mean (channels 0 .. L-1) and logvar (L .. 2L-1); the latent is fp32 NCHW [B, L, HW].  Element i of the NCHW tensor takes
+// element i of the Philox normal stream (counter offset + i / 4), the convention of qsample_draw_kernel, so
+// z = mean + exp(0.5 clamp(logvar, -30, 20)) * uwu_philox_normal(n, seed, offset).  z / mean_out / logvar_out are each optional:
+// without z nothing is drawn (the latent_dist attributes alone).
+__global__ void posterior_draw_kernel(const float* __restrict__ mom, int ldm, int Lc, int64_t HW, int64_t total4, float* __restrict__ z,
+                                      float* __restrict__ mean_out, float* __restrict__ logvar_out, unsigned long long seed,
+                                      unsigned long long offset) {
+  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (; i < total4; i += stride) {
+    f32x4 mu, lv, zv;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int64_t e = 4 * i + j, r = e / HW, p = e - r * HW;
+      const int64_t b = r / Lc;
+      const int c = (int)(r - b * Lc);
+      const float* row = mom + (b * HW + p) * ldm;
+      mu[j] = row[c];
+      lv[j] = fminf(fmaxf(row[Lc + c], -30.f), 20.f);
+    }
+    if (z) {
+      const f32x4 nv = philox_normal4(offset + (unsigned long long)i, seed);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) zv[j] = mu[j] + expf(0.5f * lv[j]) * nv[j];
+      store4(z + 4 * i, zv);
+    }
+    if (mean_out) store4(mean_out + 4 * i, mu);
+    if (logvar_out) store4(logvar_out + 4 * i, lv);
+  }
+}
+
 // diffusion.py:77-82 ; rectified_flow.py:67-71
 __global__ void qsample_kernel(const float* __restrict__ x, const float* __restrict__ noise,
                                const float* __restrict__ coef, int64_t n4, int64_t total4,
@@ -422,6 +454,20 @@ extern "C" int uwu_qsample_draw(const float* x, const float* coef, int B, int64_
                      use_norm, vae_mean, use_norm ? 1.f / vae_std : 1.f, x_norm, noise, noisy, (unsigned long long)seed,
                      (unsigned long long)offset);
   UWU_LAUNCH_CHECK("qsample_draw");
+  return UWU_OK;
+}
+
+extern "C" int uwu_posterior_draw(const float* moments, int ldm, int B, int latent, int64_t HW, float* z, float* mean_out,
+                                  float* logvar_out, uint64_t seed, uint64_t offset, void* stream) {
+  UWU_CHECK_ARG(moments && (z || mean_out || logvar_out), "posterior_draw: null pointer");
+  UWU_CHECK_ARG(B > 0 && latent > 0 && HW > 0 && ldm >= 2 * latent, "posterior_draw: bad shape B=%d latent=%d HW=%lld ldm=%d", B, latent,
+                (long long)HW, ldm);
+  const int64_t n = (int64_t)B * latent * HW;
+  UWU_CHECK_ARG(n % 4 == 0, "posterior_draw: B * latent * HW = %lld must be a multiple of 4", (long long)n);
+  UWU_CHECK_ARG((((uintptr_t)z | (uintptr_t)mean_out | (uintptr_t)logvar_out) & 15) == 0, "posterior_draw: misaligned output");
+  hipLaunchKernelGGL(posterior_draw_kernel, dim3(ew_grid(n / 4, 256)), dim3(256), 0, (hipStream_t)stream, moments, ldm, latent, HW, n / 4, z,
+                     mean_out, logvar_out, (unsigned long long)seed, (unsigned long long)offset);
+  UWU_LAUNCH_CHECK("posterior_draw");
   return UWU_OK;
 }
 

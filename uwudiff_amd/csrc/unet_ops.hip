@@ -57,6 +57,30 @@ __global__ void __launch_bounds__(256) col2im3x3_kernel(const T* __restrict__ dc
   }
 }
 
+// Column matrix of the 3x3 / stride 2 convolution that pads right and bottom only (F.pad(x, (0, 1, 0, 1)), padding 0):
+// col[(b, oy, ox), (ky, kx, c)] = x[b, 2 oy + ky, 2 ox + kx, c]   (zero where the index reaches H or W)
+template <typename T>
+__global__ void __launch_bounds__(256) im2col3x3_s2br_kernel(const T* __restrict__ x, T* __restrict__ col, int B, int H, int W, int C,
+                                                             int Ho, int Wo) {
+  const int c4n = C / 4;
+  const int64_t total = (int64_t)B * Ho * Wo * 9 * c4n;
+  const int64_t step = (int64_t)gridDim.x * 256;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += step) {
+    const int c4 = (int)(i % c4n);
+    int64_t r = i / c4n;
+    const int tap = (int)(r % 9);
+    r /= 9;
+    const int ox = (int)(r % Wo);
+    r /= Wo;
+    const int oy = (int)(r % Ho);
+    const int b = (int)(r / Ho);
+    const int iy = 2 * oy + tap / 3, ix = 2 * ox + tap % 3;
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (iy < H && ix < W) v = load4(x + (((int64_t)b * H + iy) * W + ix) * C + 4 * c4);
+    store4(col + i * 4, v);
+  }
+}
+
 // ---- GEGLU: h[m, :F] , gate[m, F:2F] -> out = h * gelu_erf(gate)   (diffusers GEGLU uses exact GELU) ------
 __device__ __forceinline__ float gelu_erf_f(float x) { return 0.5f * x * (1.f + erff(x * 0.70710678118654752f)); }
 __device__ __forceinline__ float dgelu_erf_f(float x) {
@@ -278,5 +302,18 @@ extern "C" int uwu_cl_to_nchw(const void* cl, float* nchw, int B, int C, int HW,
                 hipLaunchKernelGGL((layout_kernel<bf16_t, false>), dim3(ew_grid(total, 256)), dim3(256), 0, st, nchw,
                                    (bf16_t*)const_cast<void*>(cl), B, C, HW))
   UWU_LAUNCH_CHECK("cl_to_nchw");
+  return UWU_OK;
+}
+
+// (host-side launch for uwu_conv3x3_s2br_fwd, gemm.hip; arguments checked there)
+int uwu_im2col3x3_s2br(const void* x, void* col, int B, int H, int W, int C, int dtype, hipStream_t st) {
+  const int Ho = (H - 2) / 2 + 1, Wo = (W - 2) / 2 + 1;
+  const int64_t total = (int64_t)B * Ho * Wo * 9 * (C / 4);
+  UNET_DISPATCH(dtype,
+                hipLaunchKernelGGL((im2col3x3_s2br_kernel<float>), dim3(ew_grid(total, 256)), dim3(256), 0, st, (const float*)x,
+                                   (float*)col, B, H, W, C, Ho, Wo),
+                hipLaunchKernelGGL((im2col3x3_s2br_kernel<bf16_t>), dim3(ew_grid(total, 256)), dim3(256), 0, st, (const bf16_t*)x,
+                                   (bf16_t*)col, B, H, W, C, Ho, Wo))
+  UWU_LAUNCH_CHECK("im2col3x3_s2br");
   return UWU_OK;
 }

@@ -52,6 +52,7 @@ _SIGS = {
     "uwu_draw_timesteps": (c_int, [P, c_int, c_int, ctypes.c_uint64, ctypes.c_uint64, P]),
     "uwu_draw_u01": (c_int, [P, c_int, ctypes.c_uint64, ctypes.c_uint64, P]),
     "uwu_qsample_draw": (c_int, [P, P, c_int, c_int64, c_int, c_float, c_float, P, P, P, ctypes.c_uint64, ctypes.c_uint64, P]),
+    "uwu_posterior_draw": (c_int, [P, c_int, c_int, c_int, c_int64, P, P, P, ctypes.c_uint64, ctypes.c_uint64, P]),
     "uwu_qsample_norm": (c_int, [P, P, P, c_int, c_int64, c_float, c_float, P, P, P]),
     "uwu_ctx_place": (c_int, [P, c_int, P, P] + [c_int] * 7 + [P]),
     "uwu_loss_fwd_bwd": (c_int, [P, P, P, P, c_int, P, c_int, c_int, c_int, c_int, c_int64, P, P, P, P, P, P]),
@@ -100,6 +101,7 @@ _SIGS = {
     "uwu_add_ln_modulate_fwd_q8": (c_int, [P, P, P, P, P, c_int, P, P, c_int, P, c_int, P, P, P, P, c_int, c_int, c_int, c_float, P]),
     "uwu_add_ln_modulate_bwd": (c_int, [P, P, P, P, P, P, P, P, c_int, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, P]),
     "uwu_attention_fwd": (c_int, [P, P, P, P, P] + [c_int] * 9 + [c_float, c_int, P]),
+    "uwu_attention_d512_fwd": (c_int, [P, P, P, P] + [c_int] * 6 + [c_float, c_int, P]),
     "uwu_attention_bwd": (c_int, [P] * 10 + [c_int] * 9 + [c_float, c_int, P]),
     "uwu_attention_bias_fwd": (c_int, [P] * 6 + [c_int] * 9 + [c_float, c_int, P]),
     "uwu_attention_bias_bwd": (c_int, [P] * 11 + [c_int] * 9 + [c_float, c_int, P]),
@@ -118,11 +120,15 @@ _SIGS = {
     "uwu_unpatchify": (c_int, [P, c_int, P, c_int, c_int, c_int, c_int, c_int, P]),
     "uwu_add_pos": (c_int, [P, P, c_int, c_int, c_int, c_int, P]),
     "uwu_groupnorm_fwd": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_float, c_int, c_int, P]),
+    "uwu_groupnorm_fwd_det_ws_bytes": (ctypes.c_size_t, [c_int] * 4),
+    "uwu_groupnorm_fwd_det": (c_int, [P, P, P, P, P, P, P, ctypes.c_size_t, c_int, c_int, c_int, c_int, c_float, c_int, c_int, P]),
     "uwu_groupnorm_bwd": (c_int, [P] * 10 + [c_int] * 6 + [P]),
     "uwu_im2col3x3": (c_int, [P, P] + [c_int] * 6 + [P]),
     "uwu_col2im3x3": (c_int, [P, P] + [c_int] * 6 + [P]),
     "uwu_conv3x3_implicit_ok": (c_int, [c_int] * 7),
     "uwu_conv3x3_fwd": (c_int, [P, P, P, P] + [c_int] * 7 + [P]),
+    "uwu_conv3x3_s2br_ws_bytes": (ctypes.c_size_t, [c_int] * 6),
+    "uwu_conv3x3_s2br_fwd": (c_int, [P, P, P, P] + [c_int] * 6 + [P, ctypes.c_size_t, P]),
     "uwu_conv3x3_dgrad": (c_int, [P, P, P] + [c_int] * 7 + [P]),
     "uwu_conv3x3_wgrad_scratch_bytes": (ctypes.c_size_t, [c_int, c_int, c_int64]),
     "uwu_conv3x3_wgrad": (c_int, [P, P, P, P] + [c_int] * 7 + [P, ctypes.c_size_t, P]),

@@ -144,6 +144,39 @@ def conv3x3_fwd(x, w, bias, B, H, W, C, Cout, stride=1):
     return y
 
 
+def conv3x3_s2br_fwd(x, w, bias, B, H, W, C, Cout):
+    """3x3 / stride 2 convolution padded right and bottom only (``F.pad(x, (0, 1, 0, 1))`` + stride 2, padding 0), forward:
+    x [B*H*W, C] channels-last, w [Cout, 9*C] (tap-major) -> [B*Ho*Wo, Cout], Ho = (H - 2) // 2 + 1."""
+    Ho, Wo = (H - 2) // 2 + 1, (W - 2) // 2 + 1
+    y = torch.empty(max(B * Ho * Wo, 0), Cout, device=x.device, dtype=x.dtype)
+    need = L.load().uwu_conv3x3_s2br_ws_bytes(B, H, W, C, Cout, L.dt(x))
+    ws = shared_scratch(need, x.device) if need else None
+    L.call("uwu_conv3x3_s2br_fwd", L.ptr(x), L.ptr(w), L.ptr(bias), L.ptr(y), B, H, W, C, Cout, L.dt(x), L.ptr(ws),
+           ws.numel() if ws is not None else 0, L.stream())
+    return y
+
+
+def attention_d512_fwd(q, k, v, B, T, scale=None):
+    """One head of width 512, forward only: q / k / v 2-D views [B*T, >= 512] with unit inner stride -> o [B*T, 512]."""
+    scale = scale if scale is not None else 512 ** -0.5
+    o = torch.empty(B * T, 512, device=q.device, dtype=q.dtype)
+    L.call("uwu_attention_d512_fwd", _p(q), _p(k), _p(v), L.ptr(o), B, T, q.stride(0), k.stride(0), v.stride(0), o.stride(0),
+           scale, L.dt(q), L.stream())
+    return o
+
+
+def posterior_draw(moments, B, latent, HW, seed=0, offset=0, *, sample=True, mean=False, logvar=False):
+    """AutoencoderKL posterior from channels-last fp32 moments [B*HW, >= 2*latent]: (z, mean, logvar), each fp32 [B, latent, HW] or
+    None; z = mean + exp(0.5 clamp(logvar, -30, 20)) * uwu_philox_normal(n, seed, offset)."""
+    if moments.dtype != torch.float32:
+        raise L.UwuError(f"posterior_draw: moments must be fp32, got {moments.dtype}")
+    new = lambda on: torch.empty(B, latent, HW, device=moments.device, dtype=torch.float32) if on else None
+    z, mu, lv = new(sample), new(mean), new(logvar)
+    L.call("uwu_posterior_draw", L.ptr(moments), moments.stride(0), B, latent, HW, L.ptr(z), L.ptr(mu), L.ptr(lv), seed, offset,
+           L.stream())
+    return z, mu, lv
+
+
 def conv3x3_dgrad(dy, w, B, H, W, C, Cout, stride=1):
     dx = torch.empty(B * H * W, C, device=dy.device, dtype=dy.dtype)
     L.call("uwu_conv3x3_dgrad", L.ptr(dy), L.ptr(w), L.ptr(dx), B, H, W, C, Cout, stride, L.dt(dy), L.stream())
@@ -165,6 +198,18 @@ def groupnorm_fwd(x, gamma, beta, B, HW, C, G, eps, silu):
     rstd = torch.empty_like(mean)
     L.call("uwu_groupnorm_fwd", L.ptr(x), _p(gamma), _p(beta), L.ptr(y), L.ptr(mean), L.ptr(rstd), B, HW, C, G,
            float(eps), int(silu), L.dt(x), L.stream())
+    return y, mean, rstd
+
+
+def groupnorm_fwd_det(x, gamma, beta, B, HW, C, G, eps, silu):
+    """groupnorm_fwd with a fixed summation order (no float atomics): bit-identical between launches and batch sizes."""
+    y = torch.empty_like(x)
+    mean = torch.empty(B * G, device=x.device, dtype=torch.float32)
+    rstd = torch.empty_like(mean)
+    need = L.load().uwu_groupnorm_fwd_det_ws_bytes(B, HW, C, G)
+    ws = torch.empty(max(need, 4), device=x.device, dtype=torch.uint8)
+    L.call("uwu_groupnorm_fwd_det", L.ptr(x), _p(gamma), _p(beta), L.ptr(y), L.ptr(mean), L.ptr(rstd), L.ptr(ws), ws.numel(), B, HW, C,
+           G, float(eps), int(silu), L.dt(x), L.stream())
     return y, mean, rstd
 
 
