@@ -390,6 +390,34 @@ int uwu_attention_fwd(const void* q, const void* k, const void* v, void* o, floa
  * softmax, no T x T tensor in memory; fp32: exact-fp32 VALU kernel. */
 int uwu_attention_d512_fwd(const void* q, const void* k, const void* v, void* o, int B, int T, int ldq, int ldk, int ldv, int ldo,
                            float scale, int dtype, void* stream);
+/* Causal self-attention of a CLIP text transformer, forward only, no lse (transformers CLIPAttention under the causal mask of
+ * CLIPTextTransformer plus the padding mask built from `attention_mask`):  o = softmax(scale * Q K^T + M) V, where key j is visible
+ * to query i iff j <= i and (key_mask == NULL or key_mask[b, j] != 0).  key_mask: int64 [B, T], the tokenizer's attention_mask as
+ * ConcatTextEncoders holds it.  Addressing as uwu_attention_fwd (Tq = Tk = T), so a packed [B*T, 3*H*d] projection is read in
+ * place.  d = 64 and 1 <= T <= 128, anything else is refused; row strides multiples of 8 (bf16) / 4 (fp32) elements, 16-byte
+ * aligned bases.  Precondition, not checked on the device: key_mask[b, 0] != 0 (tokenizers always emit bos, so no row is fully
+ * masked; a row that is comes out as zeros).  bf16: MFMA kernel, one workgroup per (batch, head), K / V staged once in LDS,
+ * T padded to the MFMA tile inside the kernel, key tiles above the diagonal skipped, plain softmax in registers; fp32: exact-fp32
+ * VALU kernel. */
+int uwu_attention_causal_fwd(const void* q, const void* k, const void* v, const int64_t* key_mask, void* o, int B, int T, int H,
+                             int d, int ldq, int ldk, int ldv, int ldo, float scale, int dtype, void* stream);
+/* CLIPTextEmbeddings: out[b,t,:] = tok_table[ids[b,t],:] + pos_table[t,:].  ids int64 [B, T]; tok_table [vocab, D], pos_table
+ * [>= T, D] and out [B*T, D] in `dtype`; D a multiple of 8, 16-byte aligned tables.  An id outside [0, vocab) is CLAMPED to the
+ * nearest valid row (torch's embedding raises instead): nothing outside the table is ever read. */
+int uwu_text_embed(const int64_t* ids, const void* tok_table, const void* pos_table, void* out, int B, int T, int D, int vocab,
+                   int dtype, void* stream);
+/* y = act(x + bias) on [M, N] rows of stride ld (elements), the activations of CLIPMLP that the GEMM epilogue does not have:
+ * UWU_ACT_QUICK_GELU  v * sigmoid(1.702 v)  (transformers QuickGELUActivation, CLIP-L),  UWU_ACT_GELU_ERF  0.5 v (1 + erf(v /
+ * sqrt 2))  (nn.GELU, OpenCLIP-bigG).  bias fp32 [N] or NULL; y == x allowed; N and ld multiples of 8, 16-byte aligned.  fp32
+ * tensors are evaluated in double, bf16 tensors in fp32. */
+#define UWU_ACT_QUICK_GELU 0
+#define UWU_ACT_GELU_ERF 1
+int uwu_bias_act_fwd(const void* x, const float* bias, void* y, int M, int N, int ld, int kind, int dtype, void* stream);
+/* CLIP pooled output: pooled[b,:] = h[b, p_b, :] with p_b found on the device.  eos_id == 2: p_b = first position of the largest
+ * id (`input_ids.argmax(-1)`, the legacy rule of transformers' CLIPTextTransformer that every SDXL checkpoint takes); otherwise
+ * p_b = first position whose id equals eos_id, position 0 if there is none (`(input_ids == eos).int().argmax(-1)`).
+ * h [B*T, D], pooled [B, D] in `dtype`; D a multiple of 8. */
+int uwu_text_pool(const int64_t* ids, const void* h, void* pooled, int B, int T, int D, int eos_id, int dtype, void* stream);
 /* dq/dk/dv use the strides of q/k/v; dO uses ldo.  delta: fp32 workspace [B,H,Tq] (rowsum(dO*O)). */
 int uwu_attention_bwd(const void* q, const void* k, const void* v, const void* o, const void* dO,
                       const float* lse, float* delta, void* dq, void* dk, void* dv, int B, int Tq, int Tk, int H,

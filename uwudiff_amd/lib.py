@@ -15,6 +15,7 @@ LIB_PATH = os.path.join(_HERE, "libuwu_hip.so")
 F32, BF16 = 0, 1
 PT = {"epsilon": 0, "v_prediction": 1, "sample": 2, "rectified_flow": 3}
 EPI_NONE, EPI_BIAS, EPI_BIAS_GELU, EPI_DGELU, EPI_BIAS_SILU, EPI_ACCUM = 0, 1, 2, 3, 4, 5
+ACT = {"quick_gelu": 0, "gelu": 1}  # UWU_ACT_QUICK_GELU, UWU_ACT_GELU_ERF
 
 
 class UwuError(RuntimeError):
@@ -102,6 +103,10 @@ _SIGS = {
     "uwu_add_ln_modulate_bwd": (c_int, [P, P, P, P, P, P, P, P, c_int, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, P]),
     "uwu_attention_fwd": (c_int, [P, P, P, P, P] + [c_int] * 9 + [c_float, c_int, P]),
     "uwu_attention_d512_fwd": (c_int, [P, P, P, P] + [c_int] * 6 + [c_float, c_int, P]),
+    "uwu_attention_causal_fwd": (c_int, [P] * 5 + [c_int] * 8 + [c_float, c_int, P]),
+    "uwu_text_embed": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, P]),
+    "uwu_bias_act_fwd": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, P]),
+    "uwu_text_pool": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, P]),
     "uwu_attention_bwd": (c_int, [P] * 10 + [c_int] * 9 + [c_float, c_int, P]),
     "uwu_attention_bias_fwd": (c_int, [P] * 6 + [c_int] * 9 + [c_float, c_int, P]),
     "uwu_attention_bias_bwd": (c_int, [P] * 11 + [c_int] * 9 + [c_float, c_int, P]),

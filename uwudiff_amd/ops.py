@@ -165,6 +165,54 @@ def attention_d512_fwd(q, k, v, B, T, scale=None):
     return o
 
 
+def _ids(ids, B, T, what):
+    if ids.dtype != torch.int64 or tuple(ids.shape) != (B, T):
+        raise L.UwuError(f"{what} must be int64 [B, T] = [{B}, {T}], got {ids.dtype} {tuple(ids.shape)}")
+    return L.ptr(ids)
+
+
+def attention_causal_fwd(q, k, v, B, T, H, d=64, scale=None, key_mask=None):
+    """Causal self-attention of the CLIP text transformer, forward only: q / k / v 2-D views [B*T, >= H*d] with unit inner stride
+    (column slices of the packed projection) -> o [B*T, H*d].  key_mask: optional int64 [B, T] (attention_mask; row 0 visible)."""
+    scale = scale if scale is not None else d ** -0.5
+    o = torch.empty(B * T, H * d, device=q.device, dtype=q.dtype)
+    L.call("uwu_attention_causal_fwd", _p(q), _p(k), _p(v), None if key_mask is None else _ids(key_mask, B, T, "key_mask"), L.ptr(o),
+           B, T, H, d, q.stride(0), k.stride(0), v.stride(0), o.stride(0), scale, L.dt(q), L.stream())
+    return o
+
+
+def text_embed(ids, tok_table, pos_table):
+    """tok_table[ids] + pos_table[:T] -> [B*T, D] in the tables' dtype (ids outside the table are clamped)."""
+    B, T = ids.shape
+    vocab, D = tok_table.shape
+    if pos_table.shape[0] < T or pos_table.shape[1] != D or pos_table.dtype != tok_table.dtype:
+        raise L.UwuError(f"text_embed: position table {tuple(pos_table.shape)} does not cover T = {T}, D = {D}")
+    out = torch.empty(B * T, D, device=tok_table.device, dtype=tok_table.dtype)
+    L.call("uwu_text_embed", _ids(ids, B, T, "input_ids"), L.ptr(tok_table), L.ptr(pos_table), L.ptr(out), B, T, D, vocab, L.dt(out),
+           L.stream())
+    return out
+
+
+def bias_act_fwd(x, kind, bias=None, out=None, N=None):
+    """act(x + bias) over the first N columns of the rows of x [M, >= N]; kind "quick_gelu" | "gelu" (erf); out=x runs in place."""
+    M = x.shape[0]
+    N = N if N is not None else x.shape[1]
+    y = out if out is not None else torch.empty_like(x)
+    if y.stride(0) != x.stride(0) or y.dtype != x.dtype:
+        raise L.UwuError("bias_act_fwd: out must have the dtype and row stride of x")
+    L.call("uwu_bias_act_fwd", _p(x), L.ptr(bias), _p(y), M, N, x.stride(0), L.ACT[kind], L.dt(x), L.stream())
+    return y
+
+
+def text_pool(ids, h, eos_id):
+    """h [B*T, D] -> [B, D]: the row at the eos position of each sequence (uwu_text_pool's two rules), found on the device."""
+    B, T = ids.shape
+    D = h.shape[1]
+    pooled = torch.empty(B, D, device=h.device, dtype=h.dtype)
+    L.call("uwu_text_pool", _ids(ids, B, T, "input_ids"), L.ptr(h), L.ptr(pooled), B, T, D, int(eos_id), L.dt(h), L.stream())
+    return pooled
+
+
 def posterior_draw(moments, B, latent, HW, seed=0, offset=0, *, sample=True, mean=False, logvar=False):
     """AutoencoderKL posterior from channels-last fp32 moments [B*HW, >= 2*latent]: (z, mean, logvar), each fp32 [B, latent, HW] or
     None; z = mean + exp(0.5 clamp(logvar, -30, 20)) * uwu_philox_normal(n, seed, offset)."""

@@ -1,0 +1,353 @@
+"""The CLIP text transformer (SDXL's two text encoders) on the HIP kernels: frozen, forward only.
+
+The reference wraps ``transformers.CLIPTextModel`` / ``CLIPTextModelWithProjection`` in ``ConcatTextEncoders`` and runs them
+inside every training step under ``no_grad`` (reference src/duwu/modules/text_encoders.py:153-191, src/duwu/trainer/trainer.py:238).
+This module restates that model from its public description -- token + position embedding; L pre-LN layers ``h += out_proj(
+attn(LN1 h))``, ``h += fc2(act(fc1(LN2 h)))`` with causal self-attention that also hides the keys ``attention_mask`` marks as
+padding; ``final_layer_norm``; the pooled row at the eos token -- keeps transformers' parameter names in ``state_dict()`` and
+runs every operator through ``libuwu_hip.so``:
+
+  * activations stay ``[B*T, D]`` in the compute dtype; q, k and v are ONE bias GEMM on weights stored back to back, read in
+    place by ``uwu_attention_causal_fwd`` (which takes the 1/sqrt(d) scale); every LayerNorm is ``uwu_add_ln_modulate_fwd``
+    (affine) with the previous sublayer's residual add fused in; fc1 is ``uwu_gemm(EPI_BIAS)`` followed by ``uwu_bias_act_fwd``
+    in place with no bias; embedding and pooling are ``uwu_text_embed`` / ``uwu_text_pool`` (the eos position is found on the
+    device: no host synchronisation anywhere in the forward);
+  * all parameters live in one flat fp32 buffer (+ a bf16 shadow in bf16 mode), both registered as buffers;
+  * there is no backward and no CPU path.
+"""
+import hashlib
+import json
+import math
+import os
+
+import torch
+import torch.nn as nn
+
+from . import lib as L
+from . import ops
+
+_COMMON = dict(max_position_embeddings=77, vocab_size=49408, layer_norm_eps=1e-5, eos_token_id=2, bos_token_id=49406,
+               pad_token_id=1)
+# stabilityai/stable-diffusion-xl-base-1.0: text_encoder (CLIP ViT-L/14) and text_encoder_2 (OpenCLIP ViT-bigG/14)
+SDXL_TEXT_CONFIGS = {
+    "text_encoder": dict(_COMMON, hidden_size=768, num_attention_heads=12, num_hidden_layers=12, intermediate_size=3072,
+                         hidden_act="quick_gelu", projection_dim=768),
+    "text_encoder_2": dict(_COMMON, hidden_size=1280, num_attention_heads=20, num_hidden_layers=32, intermediate_size=5120,
+                           hidden_act="gelu", projection_dim=1280),
+}
+_HEAD_DIM = 64   # the one head width uwu_attention_causal_fwd is built for
+_MAX_T = 128     # and its longest sequence
+
+
+class _Config(dict):
+    """the transformers configuration, attribute-accessible (``model.config.hidden_size``)"""
+
+    def __getattr__(self, k):
+        try:
+            return self[k]
+        except KeyError as e:
+            raise AttributeError(k) from e
+
+
+def _pad64(n):
+    return (n + 63) // 64 * 64
+
+
+class _FinalLayerNorm:
+    """``model.final_layer_norm``: callable on any hidden state [B, T, D] (ConcatTextEncoders applies it to ``hidden_states[
+    layer_idx]``, text_encoders.py:185-186); runs on uwu_add_ln_modulate_fwd."""
+
+    def __init__(self, model):
+        self._m = model
+
+    def __call__(self, x):
+        m = self._m
+        m._require_device(x, "final_layer_norm")
+        D = m.config["hidden_size"]
+        if x.shape[-1] != D:
+            raise ValueError(f"final_layer_norm: expected [..., {D}], got {tuple(x.shape)}")
+        x2 = x.reshape(-1, D).to(m.dtype).contiguous()
+        return m._ln(x2, "final_layer_norm")[1].view(x.shape)
+
+
+class CLIPTextModel(nn.Module):
+    """``transformers.CLIPTextModel``: ``forward(...) -> (last_hidden_state, pooled[, hidden_states])``."""
+
+    kind = "clip_sd1"  # ConcatTextEncoders recomputes normed = final_layer_norm(hidden_states[layer_idx]) for this class
+    _uwu_keep_fp32_master = True  # duwu.loader.prepare_model: `precision: torch.float16` must not cast the flat fp32 master
+    _with_projection = False
+
+    def __init__(self, config=None, compute_dtype="bf16", **kw):
+        super().__init__()
+        init_weights = kw.pop("init_weights", True)
+        device = kw.pop("device", None)
+        seed = kw.pop("seed", None)
+        cfg = dict(SDXL_TEXT_CONFIGS["text_encoder"])
+        cfg.update({k: v for k, v in (config or {}).items() if not k.startswith("_")})
+        cfg.update(kw)
+        if compute_dtype not in ("bf16", "fp32"):
+            raise ValueError(f"compute_dtype must be 'bf16' or 'fp32', got {compute_dtype!r}")
+        if cfg["hidden_act"] not in L.ACT:
+            raise ValueError(f"CLIPTextModel: hidden_act {cfg['hidden_act']!r} is not built (known: {sorted(L.ACT)})")
+        D, H = int(cfg["hidden_size"]), int(cfg["num_attention_heads"])
+        if D != H * _HEAD_DIM:
+            raise ValueError(f"CLIPTextModel: the attention kernel is built for heads of width {_HEAD_DIM}, got {D} / {H}")
+        if cfg["max_position_embeddings"] > _MAX_T:
+            raise ValueError(f"CLIPTextModel: at most {_MAX_T} positions, got {cfg['max_position_embeddings']}")
+        if D % 8 or cfg["intermediate_size"] % 8 or (self._with_projection and cfg["projection_dim"] % 8):
+            raise ValueError("CLIPTextModel: widths must be multiples of 8")
+        self.config = _Config(cfg)
+        self.compute_dtype = compute_dtype
+        self.dtype = torch.bfloat16 if compute_dtype == "bf16" else torch.float32
+        self.registry, self.n = {}, 0          # stored name -> (offset, shape) in the flat buffer
+        self._names = {}                        # transformers name -> (stored name, first row, rows)
+
+        def add(name, shape, alias=None):
+            self.registry[name] = (self.n, tuple(shape))
+            self.n += _pad64(math.prod(shape))
+            if alias is None:
+                self._names[name] = (name, 0, shape[0])
+
+        F = int(cfg["intermediate_size"])
+        add("embeddings.token_embedding.weight", (cfg["vocab_size"], D))
+        add("embeddings.position_embedding.weight", (cfg["max_position_embeddings"], D))
+        for i in range(cfg["num_hidden_layers"]):
+            p = f"encoder.layers.{i}."
+            for sfx, shape in ((".weight", (3 * D, D)), (".bias", (3 * D,))):  # q, k, v back to back: one GEMM operand
+                add(p + "self_attn.qkv_proj" + sfx, shape, alias=True)
+                for c, row in (("k", D), ("v", 2 * D), ("q", 0)):  # (transformers lists k, v, q)
+                    self._names[f"{p}self_attn.{c}_proj{sfx}"] = (p + "self_attn.qkv_proj" + sfx, row, D)
+            for name, shape in (("self_attn.out_proj", (D, D)), ("layer_norm1", None), ("mlp.fc1", (F, D)), ("mlp.fc2", (D, F)),
+                                ("layer_norm2", None)):
+                add(p + name + ".weight", shape or (D,))
+                add(p + name + ".bias", (shape[0],) if shape else (D,))
+        add("final_layer_norm.weight", (D,))
+        add("final_layer_norm.bias", (D,))
+        if self._with_projection:
+            add("text_projection.weight", (cfg["projection_dim"], D))
+        self.register_buffer("flat", torch.zeros(self.n, dtype=torch.float32, device=device), persistent=False)
+        self.register_buffer("shadow", torch.zeros(0, dtype=torch.bfloat16, device=device), persistent=False)
+        self.register_buffer("ones", torch.ones(D, dtype=torch.float32, device=device), persistent=False)  # the residual's gate
+        self.final_layer_norm = _FinalLayerNorm(self)
+        if init_weights:
+            self.reset_parameters(seed)
+        self.eval().requires_grad_(False)
+
+    # ------------------------------------------------------------------ parameters
+    def _key(self, name):
+        """transformers name (flat, or the ``text_model.``-prefixed layout of hub checkpoints) -> the name used here"""
+        if name.startswith("text_model."):
+            name = name[len("text_model."):]
+        return name if name in self._names else None
+
+    def _public(self, name):
+        return name if not self._with_projection or name.startswith("text_projection.") else "text_model." + name
+
+    def _stored(self, buf, name):
+        off, shape = self.registry[name]
+        return buf[off:off + math.prod(shape)].view(shape)
+
+    def _view32(self, name):
+        stored, r0, rows = self._names[name]
+        return self._stored(self.flat, stored)[r0:r0 + rows]
+
+    def w(self, name):
+        """stored tensor in the compute dtype (GEMM operands, embedding tables)"""
+        return self._stored(self.shadow if self.dtype == torch.bfloat16 else self.flat, name)
+
+    def w32(self, name):
+        """stored tensor in fp32 (biases, LayerNorm gamma / beta)"""
+        return self._stored(self.flat, name)
+
+    @torch.no_grad()
+    def reset_parameters(self, seed=None):
+        """transformers' CLIP initialisation at initializer_factor 1 (embeddings N(0, 0.02), projections N(0, D^-1/2 (2L)^-1/2),
+        fc1 N(0, (2D)^-1/2), norms 1 / 0, biases 0), drawn on the CPU from `seed` (default: torch.initial_seed(), as
+        AutoencoderKL.reset_parameters) so the weights do not depend on the device the model is built on"""
+        g = torch.Generator().manual_seed((torch.initial_seed() if seed is None else seed) % (2 ** 31))
+        D, nl = self.config["hidden_size"], max(self.config["num_hidden_layers"], 1)
+        in_std, out_std, fc_std = D ** -0.5 * (2 * nl) ** -0.5, D ** -0.5, (2 * D) ** -0.5
+        for name in self._names:
+            v = self._view32(name)
+            if name.endswith(".bias"):
+                v.zero_()
+            elif "layer_norm" in name:
+                v.fill_(1.0)
+            else:
+                std = (0.02 if "embedding" in name else out_std if "out_proj" in name else fc_std if "fc1" in name
+                       else D ** -0.5 if "text_projection" in name else in_std)
+                v.copy_(torch.randn(v.shape, generator=g) * std)
+        self.refresh_shadow()
+
+    def named_tensors(self):
+        for name in self._names:
+            yield self._public(name), self._view32(name)
+
+    def state_dict(self, *args, destination=None, prefix="", keep_vars=False):
+        sd = destination if destination is not None else {}
+        for name, v in self.named_tensors():
+            sd[prefix + name] = v.detach().clone().contiguous()
+        return sd
+
+    @torch.no_grad()
+    def load_state_dict(self, state_dict, strict=True, assign=False):
+        got = {}
+        unexpected = []
+        for k in state_dict:
+            if k.endswith("position_ids"):  # a buffer older checkpoints carry
+                continue
+            name = self._key(k)
+            if name is None:
+                unexpected.append(k)
+            else:
+                got[name] = state_dict[k]
+        missing = [self._public(n) for n in self._names if n not in got]
+        if strict and (missing or unexpected):
+            raise RuntimeError(f"Error(s) in loading state_dict for {type(self).__name__}: missing {missing[:5]}, unexpected {unexpected[:5]}")
+        for name, src in got.items():
+            dst = self._view32(name)
+            if tuple(src.shape) != tuple(dst.shape):
+                raise RuntimeError(f"size mismatch for {name}: copying a param with shape {tuple(src.shape)}, the model has {tuple(dst.shape)}")
+        for name, src in got.items():
+            self._view32(name).copy_(src.float())
+        self.refresh_shadow()
+        return torch.nn.modules.module._IncompatibleKeys(missing, unexpected)
+
+    def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs):
+        """a parent's ``load_state_dict`` (a trainer checkpoint, whose entries ``state_dict()`` above wrote under the parent's
+        prefix) reaches the model here: the same loader, reporting into the parent's lists"""
+        own = {k[len(prefix):]: v for k, v in state_dict.items() if k.startswith(prefix)}
+        try:
+            res = self.load_state_dict(own, strict=False)
+        except RuntimeError as e:
+            error_msgs.append(str(e))
+            return
+        missing_keys.extend(prefix + k for k in res.missing_keys)
+        unexpected_keys.extend(prefix + k for k in res.unexpected_keys)
+
+    @torch.no_grad()
+    def refresh_shadow(self):
+        if self.dtype != torch.bfloat16 or not self.flat.is_cuda:
+            return
+        if self.shadow.numel() != self.n or self.shadow.device != self.flat.device:
+            self.shadow = torch.empty(self.n, device=self.flat.device, dtype=torch.bfloat16)
+        L.call("uwu_cast_f32_to_bf16", L.ptr(self.flat), L.ptr(self.shadow), self.n, L.stream())
+
+    def _apply(self, fn, recurse=True):
+        flat, ones = self.flat, self.ones
+        r = super()._apply(fn, recurse)
+        # a dtype cast (`.half()`, `.to(torch.bfloat16)`) must not touch the fp32 master: only the device moves
+        if self.flat.dtype != torch.float32:
+            self.flat, self.ones = flat.to(self.flat.device), ones.to(self.flat.device)
+        if self.shadow.dtype != torch.bfloat16:
+            self.shadow = torch.zeros(0, dtype=torch.bfloat16, device=self.flat.device)
+        self.refresh_shadow()
+        return r
+
+    # ------------------------------------------------------------------ forward
+    def _require_device(self, t, what):
+        if not torch.is_tensor(t) or not t.is_cuda or not self.flat.is_cuda:
+            raise L.UwuError(f"{type(self).__name__}.{what} runs on the HIP device only (no CPU fallback)")
+        if self.dtype == torch.bfloat16 and self.shadow.numel() != self.n:
+            self.refresh_shadow()
+
+    def _ln(self, x, name, y=None):
+        """(x + y, LayerNorm(x + y)): the residual add of the sublayer that produced y happens here"""
+        return ops.add_ln_modulate_fwd(x, 1, x.shape[0], y=y, gate=self.ones if y is not None else None, shift=self.w32(name + ".bias"),
+                                       scale=self.w32(name + ".weight"), mod_ld=0, eps=float(self.config["layer_norm_eps"]),
+                                       affine=True)[:2]
+
+    def _lin(self, x, name):
+        return ops.gemm(x, self.w(name + ".weight"), bias=self.w32(name + ".bias"), epilogue=L.EPI_BIAS)
+
+    @torch.no_grad()
+    def _encode(self, input_ids, attention_mask):
+        """-> (last_hidden_state [B, T, D], pooled [B, D], hidden_states: L + 1 tensors [B, T, D], embeddings first)"""
+        self._require_device(input_ids, "forward")
+        cfg = self.config
+        if input_ids.dim() != 2 or not 1 <= input_ids.shape[1] <= cfg["max_position_embeddings"]:
+            raise ValueError(f"input_ids must be [B, T <= {cfg['max_position_embeddings']}], got {tuple(input_ids.shape)}")
+        B, T = input_ids.shape
+        D, H = cfg["hidden_size"], cfg["num_attention_heads"]
+        ids = input_ids.long().contiguous()
+        mask = None
+        if attention_mask is not None:
+            if not attention_mask.is_cuda or tuple(attention_mask.shape) != (B, T):
+                raise L.UwuError(f"attention_mask must be a device tensor [{B}, {T}], got {tuple(attention_mask.shape)}")
+            mask = attention_mask.long().contiguous()
+        x = ops.text_embed(ids, self.w("embeddings.token_embedding.weight"), self.w("embeddings.position_embedding.weight"))
+        hidden, y = [], None
+        for i in range(cfg["num_hidden_layers"]):
+            p = f"encoder.layers.{i}."
+            x, n = self._ln(x, p + "layer_norm1", y)  # x: the input of layer i = the output of layer i - 1
+            hidden.append(x)
+            qkv = self._lin(n, p + "self_attn.qkv_proj")
+            o = ops.attention_causal_fwd(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], B, T, H, _HEAD_DIM, _HEAD_DIM ** -0.5, key_mask=mask)
+            x, n = self._ln(x, p + "layer_norm2", self._lin(o, p + "self_attn.out_proj"))
+            u = self._lin(n, p + "mlp.fc1")
+            ops.bias_act_fwd(u, cfg["hidden_act"], out=u)
+            y = self._lin(u, p + "mlp.fc2")
+        x, last = self._ln(x, "final_layer_norm", y)
+        hidden.append(x)
+        pooled = ops.text_pool(ids, last, cfg["eos_token_id"])
+        return last.view(B, T, D), pooled, tuple(h.view(B, T, D) for h in hidden)
+
+    @staticmethod
+    def _check_call(return_dict, kw):
+        if return_dict:
+            raise NotImplementedError("return_dict=True is not built: ConcatTextEncoders calls with return_dict=False")
+        extra = sorted(k for k, v in kw.items() if v is not None)
+        if extra:  # position_ids, output_attentions, ...: nothing is silently ignored
+            raise NotImplementedError(f"CLIPTextModel.forward: {extra} not built")
+
+    def forward(self, input_ids, attention_mask=None, output_hidden_states=False, return_dict=False, **kw):
+        self._check_call(return_dict, kw)
+        last, pooled, hidden = self._encode(input_ids, attention_mask)
+        return (last, pooled, hidden) if output_hidden_states else (last, pooled)
+
+    # ------------------------------------------------------------------ construction
+    @classmethod
+    def from_config(cls, config, **kw):
+        return cls(dict(config), **kw)
+
+    @classmethod
+    def from_pretrained(cls, pretrained_model_name_or_path=None, subfolder=None, **kw):
+        """A local directory (``<path>[/<subfolder>]`` with ``config.json`` and ``model.safetensors``) is loaded.  Any other name ->
+        deterministic random weights (seeded by the name and subfolder, not by the global seed) at the built-in SDXL configuration
+        keyed by ``subfolder`` (``text_encoder`` when there is none): nothing is ever fetched."""
+        for k in ("torch_dtype", "variant", "use_safetensors", "cache_dir", "local_files_only", "revision"):
+            kw.pop(k, None)
+        src = str(pretrained_model_name_or_path)
+        local = os.path.join(src, subfolder) if subfolder else src
+        if os.path.isdir(local) and os.path.exists(os.path.join(local, "config.json")):
+            from safetensors.torch import load_file
+
+            with open(os.path.join(local, "config.json")) as f:
+                config = {k: v for k, v in json.load(f).items() if k in SDXL_TEXT_CONFIGS["text_encoder"]}
+            config.update(kw.pop("config", None) or {})
+            model = cls(config, init_weights=False, **kw)
+            model.load_state_dict(load_file(os.path.join(local, "model.safetensors")))
+            return model
+        key = subfolder if subfolder is not None else "text_encoder"
+        if key not in SDXL_TEXT_CONFIGS:
+            raise ValueError(f"unknown text encoder {src!r} / subfolder {subfolder!r}: not a local directory with config.json; built-in "
+                             f"configurations: {sorted(SDXL_TEXT_CONFIGS)}")
+        config = dict(SDXL_TEXT_CONFIGS[key])
+        config.update(kw.pop("config", None) or {})
+        # the same name gives the same weights in every process, whatever the global seed
+        return cls(config, seed=int.from_bytes(hashlib.md5(f"{src}/{key}".encode()).digest()[:4], "little"), **kw)
+
+
+class CLIPTextModelWithProjection(CLIPTextModel):
+    """``transformers.CLIPTextModelWithProjection``: ``forward(...) -> (text_embeds, last_hidden_state[, hidden_states])`` with
+    ``text_embeds = text_projection(pooled)`` (no bias).  Not a plain ``CLIPTextModel`` for ConcatTextEncoders' normed-context rule
+    (the reference's ``isinstance`` test, text_encoders.py:185), hence no ``kind``."""
+
+    kind = "clip"
+    _with_projection = True
+
+    def forward(self, input_ids, attention_mask=None, output_hidden_states=False, return_dict=False, **kw):
+        self._check_call(return_dict, kw)
+        last, pooled, hidden = self._encode(input_ids, attention_mask)
+        embeds = ops.gemm(pooled, self.w("text_projection.weight"))
+        return (embeds, last, hidden) if output_hidden_states else (embeds, last)
