@@ -310,6 +310,20 @@ size_t uwu_gemm_wgrad_scratch_bytes(int M, int N, int K);
 int uwu_gemm_wgrad(const void* A, const void* B, float* C, float* bias_grad, int M, int N, int K, int lda, int ldb,
                    int ldc, int dtype, int blocks, void* scratch, size_t scratch_bytes, void* stream);
 
+/* Two weight gradients that share K (the token count) and the dtype: C_a[M_a,N_a] += A_a[K,M_a]^T . B_a[K,N_a] and the same for
+ * member b, each with its own shape, leading dimensions and optional bias gradient.  The wide streaming kernel flushes one
+ * fp32 tile per CU to the split-K scratch at the end of every launch, whatever the size of the weight; when both members take
+ * that kernel with the same tile orientation and have at most 32 tiles together, they run as ONE launch (member b's tiles
+ * follow member a's inside every K slice, scratch [slice][a's M x N, then b's M x N]) and one reduce.
+ * uwu_gemm_wgrad_pair_scratch_bytes returns the scratch that needs, or 0 when the shapes are not grouped.  With a smaller
+ * scratch, misaligned operands or shapes that are not grouped the call is two uwu_gemm_wgrad calls on the same scratch, and
+ * its results are theirs bit for bit.  Grouped results differ from them only in summation order. */
+size_t uwu_gemm_wgrad_pair_scratch_bytes(int M_a, int N_a, int M_b, int N_b, int K);
+int uwu_gemm_wgrad_pair(const void* A_a, const void* B_a, float* C_a, float* bias_grad_a, int M_a, int N_a, int lda_a,
+                        int ldb_a, int ldc_a, const void* A_b, const void* B_b, float* C_b, float* bias_grad_b, int M_b,
+                        int N_b, int lda_b, int ldb_b, int ldc_b, int K, int dtype, int blocks, void* scratch,
+                        size_t scratch_bytes, void* stream);
+
 /* Live measurement for bench.py's `roofline` object: when enabled, every uwu_gemm launch is bracketed by a HIP
  * event pair recorded on that launch's stream; collect() returns the summed launch duration, the summed
  * algorithmic FLOPs (2*M*N*K) and the launch count for operand kind 0 (bf16) or 1 (fp32). */

@@ -130,7 +130,9 @@ Layout make_layout(const uwu_dit_desc& d) {
   L.wsc_bytes = uwu_gemm_wgrad_scratch_bytes((int)L.D4, d.D, (int)L.M);
   for (const size_t t : {uwu_gemm_wgrad_scratch_bytes(d.D, (int)L.D4, (int)L.M),
                          uwu_gemm_wgrad_scratch_bytes((int)L.D3, d.D, (int)L.M),
-                         uwu_gemm_wgrad_scratch_bytes(d.D, d.D, (int)L.M)})
+                         uwu_gemm_wgrad_scratch_bytes(d.D, d.D, (int)L.M),
+                         uwu_gemm_wgrad_pair_scratch_bytes((int)L.D4, d.D, d.D, (int)L.D4, (int)L.M),  // fc1 + fc2
+                         uwu_gemm_wgrad_pair_scratch_bytes((int)L.D3, d.D, d.D, d.D, (int)L.M)})        // qkv + proj
     if (t > L.wsc_bytes) L.wsc_bytes = t;
   if (d.fp8) {
     for (const size_t t : {uwu_gemm_fp8_scratch_bytes((int)L.D4, d.D, (int)L.M), uwu_gemm_fp8_scratch_bytes(d.D, (int)L.D4, (int)L.M),
@@ -251,6 +253,18 @@ int lin_wgrad(const void* dY, const void* X, float* dW, int M, int N, int K, int
   return uwu_gemm(dY, X, dW, nullptr, nullptr, nullptr, N, K, M, N, K, K, 0, 1, 1, dt, UWU_F32, UWU_EPI_ACCUM, split, st);
 }
 
+// The bf16 weight (+ bias) gradients of two Linears over the same M tokens as ONE launch of the wide streaming kernel: every
+// such launch flushes a 192 x 384 fp32 tile per CU to the split-K scratch whatever the size of its weight, so a block's four
+// gradients go as two pairs (fc1 + fc2: 16 tiles x 16 slices, qkv + proj: 8 tiles x 32 slices at D = 384).
+bool wgrad_pair_ok(int M, int Na, int Ka, int Nb, int Kb, size_t scratch_bytes) {
+  const size_t need = uwu_gemm_wgrad_pair_scratch_bytes(Na, Ka, Nb, Kb, M);
+  return need && need <= scratch_bytes;
+}
+int lin_wgrad_pair(const void* dYa, const void* Xa, float* dWa, float* dba, int Na, int Ka, const void* dYb, const void* Xb,
+                   float* dWb, float* dbb, int Nb, int Kb, int M, void* st, void* scratch, size_t scratch_bytes) {
+  return uwu_gemm_wgrad_pair(dYa, Xa, dWa, dba, Na, Ka, Na, Ka, Ka, dYb, Xb, dWb, dbb, Nb, Kb, Nb, Kb, Kb, M, UWU_BF16,
+                             WGRAD_BLOCKS, scratch, scratch_bytes, st);
+}
 
 // dW += dY^T X and db += colsum(dY) of an fp32 conditioning Linear
 int lin_wgrad32(const float* dY, const float* X, float* dW, float* db, int M, int N, int K, void* st) {
@@ -653,6 +667,13 @@ extern "C" int uwu_dit_backward(const uwu_dit_desc* dp, const float* dout, void*
           fork_resources(fk, static_cast<hipStream_t>(d.side_stream));
   char* const wsc = P.at<char>(L.wsc);  // region k of the split-K scratch belongs to the stream that fn(.., k) runs on
   bool side_used[4] = {false, false, false, false};  // a consumer-done event of this slot has been recorded in this call
+  // One stream, bf16, the wide kernel's batch sizes: the fc2 / proj weight gradients wait for their block's fc1 / qkv
+  // weight gradient and share its launch.  dy, which they read, stays intact until the LayerNorm backward that follows the
+  // pair, and no saved activation lives longer than before.  (The forked small-batch path, fp8 and block recomputation keep
+  // one launch per gradient in the old order.)
+  const bool pairs = !fk.on && !d.fp8 && dt == UWU_BF16 && M > 16384 && !L.ckpt;
+  const bool pair_fc = pairs && wgrad_pair_ok(M, D4, D, D, D4, L.wsc_bytes);
+  const bool pair_attn = pairs && wgrad_pair_ok(M, D3, D, D, D, L.wsc_bytes);
 
   // ---- output head
   RUN(uwu_patchify(dout, P.at(L.dotok), B, d.out_ch, d.img, d.img, d.patch, dt, st));
@@ -689,10 +710,12 @@ extern "C" int uwu_dit_backward(const uwu_dit_desc* dp, const float* dout, void*
                  f8.role(l, 6), f8.role(l, 2), f8.role(l, 10)));
       }
     } else {
+    if (!pair_fc) {
     RUN(on_side(fk, 0, [&](void* s2, int k) {
       return lin_wgrad(P.at(L.dy), P.lay(l, L.o_f), g + w.off_fc2_w, M, D, D4, dt, s2, wsc + (size_t)k * L.wsc_bytes, L.wsc_bytes, g + w.off_fc2_b);
     }));
     side_used[0] = true;
+    }
     if (side_used[1]) RUN(join_side(fk, 1));  // the previous block's fc1 weight gradient still reads du
     // du = (dy.W2) * gelu'(u).  The fc1 bias gradient = colsum(du) comes out of the fc1 weight-gradient kernel (extra MFMAs
     // against an all-ones fragment, free there) -- as fp32 atomics in this epilogue it cost 79 us per launch at B = 768
@@ -705,10 +728,15 @@ extern "C" int uwu_dit_backward(const uwu_dit_desc* dp, const float* dout, void*
     } else {
       RUN(lin_dgrad(P.at(L.dy), w.fc2_w, P.at(L.du), P.lay(l, L.o_u), M, D, D4, dt, st, nullptr));
     }
+    if (pair_fc) {
+      RUN(lin_wgrad_pair(P.at(L.du), P.lay(l, L.o_h2), g + w.off_fc1_w, g + w.off_fc1_b, D4, D, P.at(L.dy), P.lay(l, L.o_f),
+                         g + w.off_fc2_w, g + w.off_fc2_b, D, D4, M, st, wsc, L.wsc_bytes));
+    } else {
     RUN(on_side(fk, 1, [&](void* s2, int k) {
       return lin_wgrad(P.at(L.du), P.lay(l, L.o_h2), g + w.off_fc1_w, M, D4, D, dt, s2, wsc + (size_t)k * L.wsc_bytes, L.wsc_bytes, g + w.off_fc1_b);
     }));
     side_used[1] = true;
+    }
     RUN(lin_dgrad(P.at(L.du), w.fc1_w, P.at(L.dh), nullptr, M, D4, D, dt, st));
     RUN(join_side(fk, 0));  // LN2 backward rewrites dy: the fc2 weight gradient must have read it
     }
@@ -721,10 +749,12 @@ extern "C" int uwu_dit_backward(const uwu_dit_desc* dp, const float* dout, void*
       RUN(f8_bwd(f8, P.at(L.dy), P.lay(l, L.o_aot), f8.w(l, 1, true), g + w.off_o_w, g + w.off_o_b, P.at(L.dao), nullptr, nullptr, M, D, D,
                  f8.role(l, 5), f8.role(l, 1), f8.role(l, 9)));
     } else {
+    if (!pair_attn) {
     RUN(on_side(fk, 2, [&](void* s2, int k) {
       return lin_wgrad(P.at(L.dy), P.lay(l, L.o_ao), g + w.off_o_w, M, D, D, dt, s2, wsc + (size_t)k * L.wsc_bytes, L.wsc_bytes, g + w.off_o_b);
     }));
     side_used[2] = true;
+    }
     RUN(lin_dgrad(P.at(L.dy), w.o_w, P.at(L.dao), nullptr, M, D, D, dt, st));
     if (side_used[3]) RUN(join_side(fk, 3));  // the previous block's qkv weight gradient still reads dqkv
     }
@@ -748,6 +778,9 @@ extern "C" int uwu_dit_backward(const uwu_dit_desc* dp, const float* dout, void*
     if (d.fp8) {  // (the input gradient follows the weight gradient inside f8_bwd; the block's event is recorded after both)
       RUN(f8_bwd(f8, dqkv, P.lay(l, L.o_h1t), f8.w(l, 0, true), g + w.off_qkv_w, g + w.off_qkv_b, P.at(L.dh), nullptr, nullptr, M, D3, D,
                  f8.role(l, 4), f8.role(l, 0), f8.role(l, 8)));
+    } else if (pair_attn) {
+      RUN(lin_wgrad_pair(dqkv, P.lay(l, L.o_h1), g + w.off_qkv_w, g + w.off_qkv_b, D3, D, P.at(L.dy), P.lay(l, L.o_ao),
+                         g + w.off_o_w, g + w.off_o_b, D, D, M, st, wsc, L.wsc_bytes));
     } else {
     RUN(on_side(fk, 3, [&](void* s2, int k) {
       return lin_wgrad(dqkv, P.lay(l, L.o_h1), g + w.off_qkv_w, M, D3, D, dt, s2, wsc + (size_t)k * L.wsc_bytes, L.wsc_bytes, g + w.off_qkv_b);

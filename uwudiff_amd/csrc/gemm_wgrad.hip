@@ -5,6 +5,7 @@
 //   gemm_tr_kernel   256x128 / 128x256 tiles, two workgroups per CU: reductions from K = 2048 on; its CONVW form is the weight
 //                    gradient of the implicit-GEMM 3x3 convolution
 //   gemm_trw_kernel  192x384 / 384x192 tiles, one workgroup per CU: M or N a multiple of 384 and K >= 32768
+//                    (uwu_gemm_wgrad_pair: two such gradients over the same K as one launch + one reduce)
 // and the two kernels that add the split-K slices of a scratch into C (also used by the fp8 weight gradients of gemm_f8.hip).
 // Everything else goes to uwu_gemm(transA = 1, transB = 1, UWU_EPI_ACCUM) in gemm.hip.
 // Reference op sequence replaced: the weight / bias gradient that autograd computes for nn.Linear inside the blocks (reference
@@ -288,8 +289,18 @@ constexpr int W_STAGE = W_NSUB * T_SUB;   // 40 KB
 //     neither waits vmcnt(0) before the visible reads nor drains the ring at the barrier; its completion is the hand-counted
 //     vmcnt wait.
 typedef short s16x4 __attribute__((ext_vector_type(4)));
+// Grouped launch: a second weight gradient dW_b[M,N] += A_b[K,M]^T . B_b[K,N] that shares K, the slice count and the scratch
+// with the one in GemmArgs (member a).  Every launch ends with the whole chip flushing its fp32 tiles to the scratch
+// (256 x 192 x 384 x 4 B = 75 MB, whatever the size of the weight), so two small gradients in one launch halve that traffic and
+// the number of reduces.  tiles == 0: a launch of member a alone.
+struct TrwPair {
+  const void* A;
+  const void* B;
+  const float* bias;
+  int M, N, lda, ldb, tiles, tiles_n;  // tiles = member b's tile count, tiles_n = its tile columns
+};
 template <int WM, int WN, int FI, int FJ, int NST>
-__global__ void __launch_bounds__(512, 2) gemm_trw_kernel(const GemmArgs g) {
+__global__ void __launch_bounds__(512, 2) gemm_trw_kernel(const GemmArgs g, const TrwPair p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   typedef bf16_t T;
   static_assert(WM * WN == 8, "8 waves");
@@ -300,11 +311,21 @@ __global__ void __launch_bounds__(512, 2) gemm_trw_kernel(const GemmArgs g) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave / WN, wn = wave - wm * WN;
   const int fr = lane & 15, fq = lane >> 4;
-  const int nblk = g.tiles_m * g.tiles_n;
+  // Workgroup -> (K slice, tile) as in gemm_tr_kernel; the tiles of member b follow member a's inside every slice, so the
+  // tiles of one (member, slice) still sit on one XCD, run in step and share their operand rows through its L2.
+  const int tiles_a = g.tiles_m * g.tiles_n, nblk = tiles_a + p.tiles;
   const int xcd = blockIdx.x & 7, loc = blockIdx.x >> 3;
-  const int zsl = xcd + 8 * (loc / nblk), tile = loc % nblk;
+  const int zsl = xcd + 8 * (loc / nblk);
+  int tile = loc % nblk;
   if (zsl >= g.wide) return;  // uniform per block
-  const int tm = tile / g.tiles_n, tn = tile - tm * g.tiles_n;
+  const bool mb = tile >= tiles_a;  // uniform per block: the member costs scalar registers only
+  if (mb) tile -= tiles_a;
+  const T* const opA = static_cast<const T*>(mb ? p.A : g.A);
+  const T* const opB = static_cast<const T*>(mb ? p.B : g.B);
+  const float* const bias = mb ? p.bias : g.bias;
+  const int M = mb ? p.M : g.M, N = mb ? p.N : g.N, lda = mb ? p.lda : g.lda, ldb = mb ? p.ldb : g.ldb;
+  const int tiles_n = mb ? p.tiles_n : g.tiles_n;
+  const int tm = tile / tiles_n, tn = tile - tm * tiles_n;
   const int m0 = tm * TBM, n0 = tn * TBN;
   const int s_begin = zsl * g.k_tiles_per_split;
   int s_end = s_begin + g.k_tiles_per_split;
@@ -323,11 +344,11 @@ __global__ void __launch_bounds__(512, 2) gemm_trw_kernel(const GemmArgs g) {
     const int xl = 128 * (isA ? q : q - NA) + 8 * dchunk;  // column inside the tile
     live[q] = xl < (isA ? TBM : TBN);
     int x = (isA ? m0 : n0) + xl;
-    const int X = isA ? g.M : g.N;
+    const int X = isA ? M : N;
     if (x > X - 8) x = X - 8;  // columns past the operand: clamped (their products are never stored)
-    src[q] = static_cast<const T*>(isA ? g.A : g.B) + (int64_t)(s_begin * 32 + 4 * wave + drow) * (isA ? g.lda : g.ldb) + x;
+    src[q] = (isA ? opA : opB) + (int64_t)(s_begin * 32 + 4 * wave + drow) * (isA ? lda : ldb) + x;
   }
-  const int64_t stepA = (int64_t)32 * g.lda, stepB = (int64_t)32 * g.ldb;
+  const int64_t stepA = (int64_t)32 * lda, stepB = (int64_t)32 * ldb;
   const unsigned smem_base = (unsigned)(size_t)((const __attribute__((address_space(3))) char*)smem);
   auto issue = [&](int s) {
     const unsigned st = smem_base + (unsigned)((s % NST) * W_STAGE + wave * 1024);
@@ -343,7 +364,7 @@ __global__ void __launch_bounds__(512, 2) gemm_trw_kernel(const GemmArgs g) {
 #pragma unroll
     for (int j = 0; j < FJ; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
   // fused bias gradient (column sums of A = dY): row fragment fi is summed by wave column fi % WN, in its slot fi / WN
-  const bool do_sum = g.bias != nullptr && tn == 0;  // wave-uniform
+  const bool do_sum = bias != nullptr && tn == 0;  // wave-uniform, per member
   constexpr int FS = (FI + WN - 1) / WN;
   f32x4 sacc[FS];
 #pragma unroll
@@ -404,22 +425,24 @@ __global__ void __launch_bounds__(512, 2) gemm_trw_kernel(const GemmArgs g) {
     }
   }
   if (do_sum) {
-    float* bg = const_cast<float*>(g.bias);
+    float* bg = const_cast<float*>(bias);
 #pragma unroll
     for (int i = 0; i < FS; ++i) {  // D[n][m]: column m = fr on the lane, every row equal
       const int fi = i * WN + wn;
       const int m = m0 + wm * 16 * FI + 16 * fi + fr;
-      if (fi < FI && fq == 0 && m < g.M) atomicAdd(bg + m, sacc[i][0]);
+      if (fi < FI && fq == 0 && m < M) atomicAdd(bg + m, sacc[i][0]);
     }
   }
-  float* P = static_cast<float*>(g.C2) + (int64_t)zsl * g.M * g.N;
+  // scratch [slice][member a's M x N, then member b's M x N]  (p.M = p.N = 0 without a member b)
+  const int64_t size_a = (int64_t)g.M * g.N;
+  float* P = static_cast<float*>(g.C2) + (int64_t)zsl * (size_a + (int64_t)p.M * p.N) + (mb ? size_a : 0);
 #pragma unroll
   for (int i = 0; i < FI; ++i) {
     const int m = m0 + wm * 16 * FI + 16 * i + fr;
 #pragma unroll
     for (int j = 0; j < FJ; ++j) {
       const int n = n0 + wn * 16 * FJ + 16 * j + 4 * fq;
-      if (m < g.M && n < g.N) store4(P + (int64_t)m * g.N + n, acc[i][j]);
+      if (m < M && n < N) store4(P + (int64_t)m * N + n, acc[i][j]);
     }
   }
 }
@@ -441,11 +464,13 @@ __global__ void __launch_bounds__(256) splitk_reduce_kernel(const float* __restr
 // (zl, cl) adds slices zl, zl + 4, .. of column group cl on two accumulators (loads of 8 slices in flight), the four partial sums
 // meet in LDS.  With one thread per output float4 a [384 x 384] gradient in 128 slices was 36 864 threads walking 128 dependent
 // adds each on 144 of the 256 CUs.
-__global__ void __launch_bounds__(256) splitk_reduce4_kernel(const float* __restrict__ part, float* __restrict__ C,
-                                                             int M, int N, int ldc, int split) {
+// A slice may hold two outputs back to back (grouped weight gradients): elements from M * N on belong to Cb[Mb, Nb].  Either way
+// every output element adds its slices in the same fixed order.
+__device__ __forceinline__ void splitk_reduce4_body(const float* __restrict__ part, int split, float* __restrict__ C, int M,
+                                                    int N, int ldc, float* __restrict__ Cb, int Mb, int Nb, int ldcb) {
   __shared__ f32x4 red[4][64];
   const int zl = threadIdx.x >> 6, cl = threadIdx.x & 63;
-  const int64_t slice = (int64_t)M * N;
+  const int64_t size_a = (int64_t)M * N, slice = size_a + (int64_t)Mb * Nb;
   for (int64_t base = (int64_t)blockIdx.x * 256; base < slice; base += (int64_t)gridDim.x * 256) {
     const int64_t idx = base + 4 * cl;
     f32x4 v0 = {0.f, 0.f, 0.f, 0.f}, v1 = v0;
@@ -461,12 +486,33 @@ __global__ void __launch_bounds__(256) splitk_reduce4_kernel(const float* __rest
     __syncthreads();
     if (zl == 0 && idx < slice) {
       const f32x4 v = (red[0][cl] + red[1][cl]) + (red[2][cl] + red[3][cl]);
-      const int m = (int)(idx / N), n = (int)(idx - (int64_t)m * N);
-      float* c = C + (int64_t)m * ldc + n;
+      const bool second = idx >= size_a;
+      const int64_t e = second ? idx - size_a : idx;
+      const int n_out = second ? Nb : N;
+      const int m = (int)(e / n_out), n = (int)(e - (int64_t)m * n_out);
+      float* c = (second ? Cb + (int64_t)m * ldcb : C + (int64_t)m * ldc) + n;
       store4(c, load4(c) + v);
     }
     __syncthreads();
   }
+}
+__global__ void __launch_bounds__(256) splitk_reduce4_kernel(const float* __restrict__ part, float* __restrict__ C,
+                                                             int M, int N, int ldc, int split) {
+  splitk_reduce4_body(part, split, C, M, N, ldc, nullptr, 0, 0, 0);
+}
+__global__ void __launch_bounds__(256) splitk_reduce4_pair_kernel(const float* __restrict__ part, int split,
+                                                                  float* __restrict__ C, int M, int N, int ldc,
+                                                                  float* __restrict__ Cb, int Mb, int Nb, int ldcb) {
+  splitk_reduce4_body(part, split, C, M, N, ldc, Cb, Mb, Nb, ldcb);
+}
+// the four-lane reduce over one output (Cb == NULL) or over the two outputs of a grouped launch: 64 float4 per workgroup and pass
+void launch_splitk_reduce4(const float* part, int split, float* C, int M, int N, int ldc, float* Cb, int Mb, int Nb, int ldcb,
+                           hipStream_t st) {
+  const int64_t quads = ((int64_t)M * N + (int64_t)Mb * Nb) / 4;
+  int rg = (int)((quads + 63) / 64);
+  if (rg > 8192) rg = 8192;
+  if (Cb) hipLaunchKernelGGL(splitk_reduce4_pair_kernel, dim3(rg), dim3(256), 0, st, part, split, C, M, N, ldc, Cb, Mb, Nb, ldcb);
+  else hipLaunchKernelGGL(splitk_reduce4_kernel, dim3(rg), dim3(256), 0, st, part, C, M, N, ldc, split);
 }
 // Number of K slices for the streaming weight-gradient kernel: a multiple of 8 (one group of slices per XCD), as
 // many groups as fit the XCD's 64 workgroup slots (32 CUs x 2) in one round.
@@ -503,41 +549,69 @@ int trw_split(int tiles, int steps) {
 }
 // 0 = not taken, 1 = 192 x 384 tiles, 2 = 384 x 192 tiles.  UWU_GEMM_TRW=0 turns it off
 // (test_gemm_wgrad_many_tiles_xcd_partition).
-int pick_trw(const GemmArgs& g) {
+int trw_kind(int M, int N, int K) {
   static UwuEnv on("UWU_GEMM_TRW");
   if (on.get().is('0')) return 0;
   // short reductions (per-GPU batch < 128 images): the 4-stage ring of a whole-LDS workgroup barely fills and nothing else fits
   // on its CU; the 256x128 kernel (two workgroups per CU) measured 1-2 % faster there.  UWU_GEMM_TRW=1 forces it
   // (test_gemm_wgrad_scratch_path).
   const bool force = on.is('1');
-  if (g.K % 32 || g.K < (force ? 4096 : 32768) || g.M % 8 || g.N % 8) return 0;
-  if ((((uintptr_t)g.A | (uintptr_t)g.B) & 15) || g.lda % 8 || g.ldb % 8) return 0;
-  if (g.N % 384 == 0 && g.M >= 192) return 1;
-  if (g.M % 384 == 0 && g.N >= 192) return 2;
+  if (K % 32 || K < (force ? 4096 : 32768) || M % 8 || N % 8) return 0;
+  if (N % 384 == 0 && M >= 192) return 1;
+  if (M % 384 == 0 && N >= 192) return 2;
   return 0;
 }
-size_t trw_scratch_bytes(int M, int N, int K, int kind) {
-  const int tiles = kind == 1 ? ((M + 191) / 192) * (N / 384) : (M / 384) * ((N + 191) / 192);
-  return (size_t)trw_split(tiles, K / 32) * M * N * sizeof(float);
+int pick_trw(const GemmArgs& g) {
+  if ((((uintptr_t)g.A | (uintptr_t)g.B) & 15) || g.lda % 8 || g.ldb % 8) return 0;
+  return trw_kind(g.M, g.N, g.K);
 }
+int trw_tiles(int M, int N, int kind) { return kind == 1 ? ((M + 191) / 192) * (N / 384) : (M / 384) * ((N + 191) / 192); }
+size_t trw_scratch_bytes(int M, int N, int K, int kind) {
+  return (size_t)trw_split(trw_tiles(M, N, kind), K / 32) * M * N * sizeof(float);
+}
+// Two weight gradients in one launch: both take the same tile orientation, and together they have at most 32 tiles -- beyond
+// that trw_split gives the pair the 8 slices each member has alone, and grouping saves no scratch traffic.  0 = not grouped.
+size_t trw_pair_scratch_bytes(int Ma, int Na, int Mb, int Nb, int K) {
+  const int kind = trw_kind(Ma, Na, K);
+  if (!kind || trw_kind(Mb, Nb, K) != kind) return 0;
+  const int tiles = trw_tiles(Ma, Na, kind) + trw_tiles(Mb, Nb, kind);
+  if (tiles > 32) return 0;
+  return (size_t)trw_split(tiles, K / 32) * ((size_t)Ma * Na + (size_t)Mb * Nb) * sizeof(float);
+}
+// b != NULL: the second member of a grouped launch (its A, B, C, bias, M, N and leading dimensions; K is g's)
 template <int WM, int WN, int FI, int FJ>
-int launch_trw(GemmArgs g, void* scratch, hipStream_t st) {
+int launch_trw(GemmArgs g, const GemmArgs* b, void* scratch, hipStream_t st) {
   constexpr int NST = 4;
+  constexpr int TBM = 16 * FI * WM, TBN = 16 * FJ * WN;
   constexpr auto kern = gemm_trw_kernel<WM, WN, FI, FJ, NST>;
   RETURN_IF(gemm_lds_optin<kern>("gemm_trw", NST * W_STAGE));
-  g.tiles_m = (g.M + 16 * FI * WM - 1) / (16 * FI * WM);
-  g.tiles_n = (g.N + 16 * FJ * WN - 1) / (16 * FJ * WN);
-  const int tiles = g.tiles_m * g.tiles_n, steps = g.K / 32;
+  g.tiles_m = (g.M + TBM - 1) / TBM;
+  g.tiles_n = (g.N + TBN - 1) / TBN;
+  TrwPair p{};
+  if (b) {
+    p.A = b->A; p.B = b->B; p.bias = b->bias; p.M = b->M; p.N = b->N; p.lda = b->lda; p.ldb = b->ldb;
+    p.tiles_n = (b->N + TBN - 1) / TBN;
+    p.tiles = ((b->M + TBM - 1) / TBM) * p.tiles_n;
+  }
+  const int tiles = g.tiles_m * g.tiles_n + p.tiles, steps = g.K / 32;
   int split = trw_split(tiles, steps);
   g.k_tiles_per_split = (steps + split - 1) / split;
   split = (steps + g.k_tiles_per_split - 1) / g.k_tiles_per_split;
   g.wide = split;
   g.C2 = scratch;
   const int grid = 8 * tiles * ((split + 7) / 8);
+  double flops = 2.0 * g.M * g.N * g.K, bytes = ((double)g.M * g.K + (double)g.N * g.K) * 2 + (double)g.M * g.N * 4;
   UwuProfScope prof(st);
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(512), NST * W_STAGE, st, g);
-  uwu_launch_splitk_reduce(static_cast<const float*>(scratch), static_cast<float*>(g.C), g.M, g.N, g.ldc, split, st);
-  prof.done(UWU_PROF_GEMM_WGRAD, 0, 2.0 * g.M * g.N * g.K, ((double)g.M * g.K + (double)g.N * g.K) * 2 + (double)g.M * g.N * 4);
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(512), NST * W_STAGE, st, g, p);
+  if (b) {
+    launch_splitk_reduce4(static_cast<const float*>(scratch), split, static_cast<float*>(g.C), g.M, g.N, g.ldc,
+                          static_cast<float*>(b->C), b->M, b->N, b->ldc, st);
+    flops += 2.0 * b->M * b->N * g.K;
+    bytes += ((double)b->M * g.K + (double)b->N * g.K) * 2 + (double)b->M * b->N * 4;
+  } else {
+    uwu_launch_splitk_reduce(static_cast<const float*>(scratch), static_cast<float*>(g.C), g.M, g.N, g.ldc, split, st);
+  }
+  prof.done(UWU_PROF_GEMM_WGRAD, 0, flops, bytes);  // (one record per launch: a grouped one carries both members' work)
   UWU_LAUNCH_CHECK("gemm_trw");
   return UWU_OK;
 }
@@ -548,9 +622,7 @@ int launch_trw(GemmArgs g, void* scratch, hipStream_t st) {
 void uwu_launch_splitk_reduce(const float* part, float* C, int M, int N, int ldc, int split, hipStream_t st) {
   const int64_t quads = (int64_t)M * N / 4;
   if (split >= 8) {
-    int rg = (int)((quads + 63) / 64);
-    if (rg > 8192) rg = 8192;
-    hipLaunchKernelGGL(splitk_reduce4_kernel, dim3(rg), dim3(256), 0, st, part, C, M, N, ldc, split);
+    launch_splitk_reduce4(part, split, C, M, N, ldc, nullptr, 0, 0, 0, st);
     return;
   }
   int rg = (int)((quads + 255) / 256);
@@ -663,8 +735,8 @@ extern "C" int uwu_gemm_wgrad(const void* A, const void* B, float* C, float* bia
     const int trw = pick_trw(g);
     if (trw && scratch && (((uintptr_t)C | (uintptr_t)scratch) & 15) == 0 && ldc % 4 == 0 &&
         scratch_bytes >= trw_scratch_bytes(M, N, K, trw)) {
-      if (trw == 1) return launch_trw<2, 4, 6, 6>(g, scratch, (hipStream_t)stream);
-      return launch_trw<4, 2, 6, 6>(g, scratch, (hipStream_t)stream);
+      if (trw == 1) return launch_trw<2, 4, 6, 6>(g, nullptr, scratch, (hipStream_t)stream);
+      return launch_trw<4, 2, 6, 6>(g, nullptr, scratch, (hipStream_t)stream);
     }
     const int tr = uwu_gemm_pick_tr(g);
     if (tr == 1) return uwu_launch_gemm_tr<8, 4>(g, scratch, scratch_bytes, (hipStream_t)stream);
@@ -684,4 +756,37 @@ extern "C" int uwu_gemm_wgrad(const void* A, const void* B, float* C, float* bia
   if (split < 1) split = 1;
   return uwu_gemm(A, B, C, nullptr, nullptr, nullptr, M, N, K, lda, ldb, ldc, 0, 1, 1, dtype, UWU_F32, UWU_EPI_ACCUM,
                   split, stream);
+}
+
+// Two weight gradients that share K (the token count) and the dtype, C_a += A_a^T . B_a and C_b += A_b^T . B_b, as ONE launch of
+// the wide kernel + one reduce when uwu_gemm_wgrad_pair_scratch_bytes() is non-zero and `scratch` holds that much; otherwise two
+// uwu_gemm_wgrad calls, one after the other on `stream`, with the same scratch.
+extern "C" size_t uwu_gemm_wgrad_pair_scratch_bytes(int M_a, int N_a, int M_b, int N_b, int K) {
+  if (M_a <= 0 || N_a <= 0 || M_b <= 0 || N_b <= 0 || K < 32) return 0;
+  return trw_pair_scratch_bytes(M_a, N_a, M_b, N_b, K);
+}
+
+extern "C" int uwu_gemm_wgrad_pair(const void* A_a, const void* B_a, float* C_a, float* bias_grad_a, int M_a, int N_a, int lda_a,
+                                   int ldb_a, int ldc_a, const void* A_b, const void* B_b, float* C_b, float* bias_grad_b,
+                                   int M_b, int N_b, int lda_b, int ldb_b, int ldc_b, int K, int dtype, int blocks,
+                                   void* scratch, size_t scratch_bytes, void* stream) {
+  UWU_CHECK_ARG(A_a && B_a && C_a && A_b && B_b && C_b, "gemm_wgrad_pair: null operand");
+  UWU_CHECK_ARG(M_a > 0 && N_a > 0 && M_b > 0 && N_b > 0 && K > 0, "gemm_wgrad_pair: bad shape");
+  UWU_CHECK_ARG(lda_a >= M_a && ldb_a >= N_a && ldc_a >= N_a && lda_b >= M_b && ldb_b >= N_b && ldc_b >= N_b,
+                "gemm_wgrad_pair: leading dimension too small");
+  if (dtype == UWU_BF16 && scratch) {
+    GemmArgs a{}, b{};
+    a.A = A_a; a.B = B_a; a.C = C_a; a.bias = bias_grad_a; a.M = M_a; a.N = N_a; a.K = K; a.lda = lda_a; a.ldb = ldb_a; a.ldc = ldc_a;
+    b.A = A_b; b.B = B_b; b.C = C_b; b.bias = bias_grad_b; b.M = M_b; b.N = N_b; b.K = K; b.lda = lda_b; b.ldb = ldb_b; b.ldc = ldc_b;
+    a.epi = b.epi = UWU_EPI_ACCUM;
+    const size_t need = trw_pair_scratch_bytes(M_a, N_a, M_b, N_b, K);
+    const int kind = pick_trw(a);
+    if (need && need <= scratch_bytes && kind && pick_trw(b) == kind && ldc_a % 4 == 0 && ldc_b % 4 == 0 &&
+        (((uintptr_t)C_a | (uintptr_t)C_b | (uintptr_t)scratch) & 15) == 0) {
+      if (kind == 1) return launch_trw<2, 4, 6, 6>(a, &b, scratch, (hipStream_t)stream);
+      return launch_trw<4, 2, 6, 6>(a, &b, scratch, (hipStream_t)stream);
+    }
+  }
+  RETURN_IF(uwu_gemm_wgrad(A_a, B_a, C_a, bias_grad_a, M_a, N_a, K, lda_a, ldb_a, ldc_a, dtype, blocks, scratch, scratch_bytes, stream));
+  return uwu_gemm_wgrad(A_b, B_b, C_b, bias_grad_b, M_b, N_b, K, lda_b, ldb_b, ldc_b, dtype, blocks, scratch, scratch_bytes, stream);
 }

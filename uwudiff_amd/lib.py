@@ -88,6 +88,8 @@ _SIGS = {
                                   P, P]),
     "uwu_gemm_wgrad_scratch_bytes": (ctypes.c_size_t, [c_int, c_int, c_int]),
     "uwu_gemm_wgrad": (c_int, [P, P, P, P] + [c_int] * 8 + [P, ctypes.c_size_t, P]),
+    "uwu_gemm_wgrad_pair_scratch_bytes": (ctypes.c_size_t, [c_int] * 5),
+    "uwu_gemm_wgrad_pair": (c_int, ([P, P, P, P] + [c_int] * 5) * 2 + [c_int] * 3 + [P, ctypes.c_size_t, P]),
     "uwu_gemm_prof_enable": (c_int, [c_int]),
     "uwu_gemm_prof_collect": (c_int, [c_int, P, P, P]),
     "uwu_prof_enable": (c_int, [c_int]),

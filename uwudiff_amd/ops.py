@@ -338,6 +338,28 @@ def gemm_wgrad(dy, x, dw, blocks=512, scratch=None, bias_grad=None):
     return dw
 
 
+def gemm_wgrad_pair(dy_a, x_a, dw_a, dy_b, x_b, dw_b, blocks=512, scratch=None, bias_grad_a=None, bias_grad_b=None):
+    """Two weight gradients over the same tokens, dw_a += dy_a^T @ x_a and dw_b += dy_b^T @ x_b, as one launch of the wide
+    streaming kernel when ``scratch`` (:func:`gemm_wgrad_pair_scratch`) allows it, else as two :func:`gemm_wgrad` calls."""
+    K = dy_a.shape[0]
+    args = []
+    for dy, x, dw, db in ((dy_a, x_a, dw_a, bias_grad_a), (dy_b, x_b, dw_b, bias_grad_b)):
+        assert dy.shape[0] == K and x.shape[0] == K and dw.shape == (dy.shape[1], x.shape[1])
+        assert dw.dtype == torch.float32 and dy.dtype == x.dtype == dy_a.dtype
+        args += [L.ptr(dy), L.ptr(x), L.ptr(dw), L.ptr(db), dy.shape[1], x.shape[1], dy.stride(0), x.stride(0), dw.stride(0)]
+    L.call("uwu_gemm_wgrad_pair", *args, K, L.dt(dy_a), blocks, L.ptr(scratch), scratch.numel() if scratch is not None else 0,
+           L.stream())
+    return dw_a, dw_b
+
+
+def gemm_wgrad_pair_scratch(Ma, Na, Mb, Nb, K, device="cuda"):
+    """Scratch for :func:`gemm_wgrad_pair`: the grouped launch's, or the larger member's when the pair is not grouped."""
+    lib = L.load()
+    need = max(lib.uwu_gemm_wgrad_pair_scratch_bytes(Ma, Na, Mb, Nb, K), lib.uwu_gemm_wgrad_scratch_bytes(Ma, Na, K),
+               lib.uwu_gemm_wgrad_scratch_bytes(Mb, Nb, K))
+    return torch.empty(need, dtype=torch.uint8, device=device)
+
+
 def gemm_wgrad_scratch(M, N, K, device="cuda"):
     return torch.empty(L.load().uwu_gemm_wgrad_scratch_bytes(M, N, K), dtype=torch.uint8, device=device)
 
