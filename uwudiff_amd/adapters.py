@@ -23,6 +23,8 @@ import re
 import torch
 import torch.nn as nn
 
+from .flat import pad64
+
 CONFIG_DEFAULTS = dict(algo="lora", linear_dim=4, linear_alpha=1.0, factor=-1, full_matrix=False, train_norm=False,
                        conv_dim=None, conv_alpha=None, use_tucker=False)
 PRESET_KEYS = ("target_module", "target_name", "enable_conv", "module_algo_map")
@@ -250,7 +252,7 @@ class LycorisNetwork(nn.Module):
         for s in self.specs:
             for t, shape in s.tensors:
                 self.offsets[(s.name, t)] = (n, shape)
-                n += (math.prod(shape) + 63) // 64 * 64
+                n += pad64(math.prod(shape))
         self.n = n
         if device is None:
             device = unet.flat.device if unet.flat.device.type != "meta" else "cpu"

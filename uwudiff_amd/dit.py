@@ -22,9 +22,9 @@ import os
 from dataclasses import dataclass
 
 import torch
-import torch.nn as nn
 
 from . import lib as L
+from .flat import FlatModule
 
 PRESETS = {
     "DiT-S/2": dict(depth=12, hidden=384, heads=6, patch=2),
@@ -52,10 +52,6 @@ class DiTConfig:
     compute_dtype: str = "bf16"  # "bf16" | "fp32" | "fp8" (bf16 activations, fp8 e4m3 / e5m2 operands of the block Linears)
     rope: bool = False           # learnable axial RoPE on q / k of every block (reference modules/rope.py, rope_unet.py:143-147)
     fp8_scaling: str = "delayed"  # "delayed" (amax of the previous step; the first step scales just in time) | "jit"
-
-
-def _pad64(n):
-    return (n + 63) // 64 * 64
 
 
 def sincos_2d(dim, grid):
@@ -89,7 +85,7 @@ class _DiTFn(torch.autograd.Function):
         return None, None, None, None, None
 
 
-class DiT(nn.Module):
+class DiT(FlatModule):
     def __init__(self, config: DiTConfig = None, init: str = "dit", **kw):
         super().__init__()
         if config is None:
@@ -114,16 +110,10 @@ class DiT(nn.Module):
                      (f"blocks.{l}.proj.weight", (D, D)), (f"blocks.{l}.proj.bias", (D,)),
                      (f"blocks.{l}.fc1.weight", (r * D, D)), (f"blocks.{l}.fc1.bias", (r * D,)),
                      (f"blocks.{l}.fc2.weight", (D, r * D)), (f"blocks.{l}.fc2.bias", (D,))]
-        self.registry = {}
-        off = 0
         for name, shape in spec:
-            n = math.prod(shape)
-            self.registry[name] = (off, shape)
-            off += _pad64(n)
-        self.n_flat = off
-        self.flat = nn.Parameter(torch.zeros(off, dtype=torch.float32))
+            self.P.add(name, shape)
+        self._alloc(c.compute_dtype != "fp32")
         self.register_buffer("pos", sincos_2d(D, c.sample_size // c.patch), persistent=False)
-        self.register_buffer("shadow", torch.zeros(0, dtype=torch.bfloat16), persistent=False)
         if c.rope:
             from .rope import make_axial_pos
 
@@ -145,13 +135,19 @@ class DiT(nn.Module):
         self.reset_parameters(init)
 
     # ------------------------------------------------------------------ parameters
-    def view(self, name):
-        off, shape = self.registry[name]
-        return self.flat.data[off:off + math.prod(shape)].view(shape)
+    n_flat = property(lambda self: self.P.n)
 
-    def grad_view(self, name):
-        off, shape = self.registry[name]
-        return self.flat.grad[off:off + math.prod(shape)].view(shape)
+    def _public_names(self):
+        names = super()._public_names()
+        if self.cfg.cond_dim == 0:  # the unconditional model stores a dummy y_embedder (the driver's layout) and does not publish it
+            names = {k: v for k, v in names.items() if not k.startswith("y_embedder")}
+        return names
+
+    def _wants_shadow(self):
+        return self.cfg.compute_dtype in ("bf16", "fp8")
+
+    def _moved(self):
+        self._desc = None
 
     @torch.no_grad()
     def reset_parameters(self, init="dit"):
@@ -181,47 +177,6 @@ class DiT(nn.Module):
                 bound = math.sqrt(6.0 / (shape[0] + shape[1]))
                 v.copy_((torch.rand(shape, generator=g) * 2 - 1) * bound)
         self.refresh_shadow()
-
-    def named_tensors(self):
-        for name in self.registry:
-            if name.startswith("y_embedder") and self.cfg.cond_dim == 0:
-                continue
-            yield name, self.view(name)
-
-    def state_dict(self, *args, destination=None, prefix="", keep_vars=False):
-        sd = destination if destination is not None else {}
-        for name, v in self.named_tensors():
-            sd[prefix + name] = v if keep_vars else v.detach().clone()
-        return sd
-
-    @torch.no_grad()
-    def load_state_dict(self, state_dict, strict=True, assign=False):
-        missing = []
-        for name, v in self.named_tensors():
-            if name in state_dict:
-                v.copy_(state_dict[name].to(v))
-            else:
-                missing.append(name)
-        if strict and missing:
-            raise RuntimeError(f"Missing key(s) in state_dict: {missing}")
-        self.refresh_shadow()
-        return torch.nn.modules.module._IncompatibleKeys(missing, [])
-
-    @torch.no_grad()
-    def refresh_shadow(self):
-        """bf16 copy of the flat parameters for the MFMA operands (kept fresh by the fused AdamW afterwards)."""
-        if self.cfg.compute_dtype not in ("bf16", "fp8") or not self.flat.is_cuda:
-            return
-        if self.shadow.numel() != self.n_flat or self.shadow.device != self.flat.device:
-            self.shadow = torch.empty(self.n_flat, device=self.flat.device, dtype=torch.bfloat16)
-        L.call("uwu_cast_f32_to_bf16", L.ptr(self.flat.data), L.ptr(self.shadow), self.n_flat, L.stream())
-        self.flat._uwu_bf16_shadow = self.shadow
-
-    def _apply(self, fn, recurse=True):
-        r = super()._apply(fn, recurse)
-        self._desc = None
-        self.refresh_shadow()
-        return r
 
     def enable_gradient_checkpointing(self, enabled=True):
         """Reference test_scripts/test_train.py:38-39 (diffusers checkpoints per transformer block, rope_unet.py:484-507).

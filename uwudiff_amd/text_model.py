@@ -17,14 +17,13 @@ runs every operator through ``libuwu_hip.so``:
 """
 import hashlib
 import json
-import math
 import os
 
 import torch
-import torch.nn as nn
 
 from . import lib as L
 from . import ops
+from .flat import FlatModule
 
 _COMMON = dict(max_position_embeddings=77, vocab_size=49408, layer_norm_eps=1e-5, eos_token_id=2, bos_token_id=49406,
                pad_token_id=1)
@@ -49,10 +48,6 @@ class _Config(dict):
             raise AttributeError(k) from e
 
 
-def _pad64(n):
-    return (n + 63) // 64 * 64
-
-
 class _FinalLayerNorm:
     """``model.final_layer_norm``: callable on any hidden state [B, T, D] (ConcatTextEncoders applies it to ``hidden_states[
     layer_idx]``, text_encoders.py:185-186); runs on uwu_add_ln_modulate_fwd."""
@@ -70,11 +65,10 @@ class _FinalLayerNorm:
         return m._ln(x2, "final_layer_norm")[1].view(x.shape)
 
 
-class CLIPTextModel(nn.Module):
+class CLIPTextModel(FlatModule):
     """``transformers.CLIPTextModel``: ``forward(...) -> (last_hidden_state, pooled[, hidden_states])``."""
 
     kind = "clip_sd1"  # ConcatTextEncoders recomputes normed = final_layer_norm(hidden_states[layer_idx]) for this class
-    _uwu_keep_fp32_master = True  # duwu.loader.prepare_model: `precision: torch.float16` must not cast the flat fp32 master
     _with_projection = False
 
     def __init__(self, config=None, compute_dtype="bf16", **kw):
@@ -99,14 +93,12 @@ class CLIPTextModel(nn.Module):
         self.config = _Config(cfg)
         self.compute_dtype = compute_dtype
         self.dtype = torch.bfloat16 if compute_dtype == "bf16" else torch.float32
-        self.registry, self.n = {}, 0          # stored name -> (offset, shape) in the flat buffer
-        self._names = {}                        # transformers name -> (stored name, first row, rows)
+        self._names = {}  # transformers name -> (stored name, first row, rows)
 
         def add(name, shape, alias=None):
-            self.registry[name] = (self.n, tuple(shape))
-            self.n += _pad64(math.prod(shape))
+            self.P.add(name, shape)
             if alias is None:
-                self._names[name] = (name, 0, shape[0])
+                self._names[name] = (name, 0, None)
 
         F = int(cfg["intermediate_size"])
         add("embeddings.token_embedding.weight", (cfg["vocab_size"], D))
@@ -125,8 +117,7 @@ class CLIPTextModel(nn.Module):
         add("final_layer_norm.bias", (D,))
         if self._with_projection:
             add("text_projection.weight", (cfg["projection_dim"], D))
-        self.register_buffer("flat", torch.zeros(self.n, dtype=torch.float32, device=device), persistent=False)
-        self.register_buffer("shadow", torch.zeros(0, dtype=torch.bfloat16, device=device), persistent=False)
+        self._alloc(compute_dtype == "bf16", device, buffer=True)
         self.register_buffer("ones", torch.ones(D, dtype=torch.float32, device=device), persistent=False)  # the residual's gate
         self.final_layer_norm = _FinalLayerNorm(self)
         if init_weights:
@@ -134,30 +125,16 @@ class CLIPTextModel(nn.Module):
         self.eval().requires_grad_(False)
 
     # ------------------------------------------------------------------ parameters
-    def _key(self, name):
-        """transformers name (flat, or the ``text_model.``-prefixed layout of hub checkpoints) -> the name used here"""
-        if name.startswith("text_model."):
-            name = name[len("text_model."):]
-        return name if name in self._names else None
-
     def _public(self, name):
         return name if not self._with_projection or name.startswith("text_projection.") else "text_model." + name
 
-    def _stored(self, buf, name):
-        off, shape = self.registry[name]
-        return buf[off:off + math.prod(shape)].view(shape)
+    def _public_names(self):
+        return {self._public(name): ent for name, ent in self._names.items()}
 
-    def _view32(self, name):
-        stored, r0, rows = self._names[name]
-        return self._stored(self.flat, stored)[r0:r0 + rows]
-
-    def w(self, name):
-        """stored tensor in the compute dtype (GEMM operands, embedding tables)"""
-        return self._stored(self.shadow if self.dtype == torch.bfloat16 else self.flat, name)
-
-    def w32(self, name):
-        """stored tensor in fp32 (biases, LayerNorm gamma / beta)"""
-        return self._stored(self.flat, name)
+    def _load_key(self, key):
+        """transformers name, flat or in the ``text_model.``-prefixed layout of hub checkpoints; ``position_ids`` is a buffer older
+        checkpoints carry"""
+        return None if key.endswith("position_ids") else self._public(key.removeprefix("text_model."))
 
     @torch.no_grad()
     def reset_parameters(self, seed=None):
@@ -167,8 +144,7 @@ class CLIPTextModel(nn.Module):
         g = torch.Generator().manual_seed((torch.initial_seed() if seed is None else seed) % (2 ** 31))
         D, nl = self.config["hidden_size"], max(self.config["num_hidden_layers"], 1)
         in_std, out_std, fc_std = D ** -0.5 * (2 * nl) ** -0.5, D ** -0.5, (2 * D) ** -0.5
-        for name in self._names:
-            v = self._view32(name)
+        for name, v in self.named_tensors():
             if name.endswith(".bias"):
                 v.zero_()
             elif "layer_norm" in name:
@@ -178,71 +154,6 @@ class CLIPTextModel(nn.Module):
                        else D ** -0.5 if "text_projection" in name else in_std)
                 v.copy_(torch.randn(v.shape, generator=g) * std)
         self.refresh_shadow()
-
-    def named_tensors(self):
-        for name in self._names:
-            yield self._public(name), self._view32(name)
-
-    def state_dict(self, *args, destination=None, prefix="", keep_vars=False):
-        sd = destination if destination is not None else {}
-        for name, v in self.named_tensors():
-            sd[prefix + name] = v.detach().clone().contiguous()
-        return sd
-
-    @torch.no_grad()
-    def load_state_dict(self, state_dict, strict=True, assign=False):
-        got = {}
-        unexpected = []
-        for k in state_dict:
-            if k.endswith("position_ids"):  # a buffer older checkpoints carry
-                continue
-            name = self._key(k)
-            if name is None:
-                unexpected.append(k)
-            else:
-                got[name] = state_dict[k]
-        missing = [self._public(n) for n in self._names if n not in got]
-        if strict and (missing or unexpected):
-            raise RuntimeError(f"Error(s) in loading state_dict for {type(self).__name__}: missing {missing[:5]}, unexpected {unexpected[:5]}")
-        for name, src in got.items():
-            dst = self._view32(name)
-            if tuple(src.shape) != tuple(dst.shape):
-                raise RuntimeError(f"size mismatch for {name}: copying a param with shape {tuple(src.shape)}, the model has {tuple(dst.shape)}")
-        for name, src in got.items():
-            self._view32(name).copy_(src.float())
-        self.refresh_shadow()
-        return torch.nn.modules.module._IncompatibleKeys(missing, unexpected)
-
-    def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs):
-        """a parent's ``load_state_dict`` (a trainer checkpoint, whose entries ``state_dict()`` above wrote under the parent's
-        prefix) reaches the model here: the same loader, reporting into the parent's lists"""
-        own = {k[len(prefix):]: v for k, v in state_dict.items() if k.startswith(prefix)}
-        try:
-            res = self.load_state_dict(own, strict=False)
-        except RuntimeError as e:
-            error_msgs.append(str(e))
-            return
-        missing_keys.extend(prefix + k for k in res.missing_keys)
-        unexpected_keys.extend(prefix + k for k in res.unexpected_keys)
-
-    @torch.no_grad()
-    def refresh_shadow(self):
-        if self.dtype != torch.bfloat16 or not self.flat.is_cuda:
-            return
-        if self.shadow.numel() != self.n or self.shadow.device != self.flat.device:
-            self.shadow = torch.empty(self.n, device=self.flat.device, dtype=torch.bfloat16)
-        L.call("uwu_cast_f32_to_bf16", L.ptr(self.flat), L.ptr(self.shadow), self.n, L.stream())
-
-    def _apply(self, fn, recurse=True):
-        flat, ones = self.flat, self.ones
-        r = super()._apply(fn, recurse)
-        # a dtype cast (`.half()`, `.to(torch.bfloat16)`) must not touch the fp32 master: only the device moves
-        if self.flat.dtype != torch.float32:
-            self.flat, self.ones = flat.to(self.flat.device), ones.to(self.flat.device)
-        if self.shadow.dtype != torch.bfloat16:
-            self.shadow = torch.zeros(0, dtype=torch.bfloat16, device=self.flat.device)
-        self.refresh_shadow()
-        return r
 
     # ------------------------------------------------------------------ forward
     def _require_device(self, t, what):

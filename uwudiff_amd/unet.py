@@ -23,10 +23,10 @@ import math
 import os
 
 import torch
-import torch.nn as nn
 
 from . import lib as L
 from . import ops
+from .flat import FlatModule, FlatParams, pad8, pad64
 
 SDXL_UNET_CONFIG = dict(
     in_channels=4, out_channels=4, block_out_channels=(320, 640, 1280), layers_per_block=2,
@@ -46,23 +46,11 @@ TINY_UNET_CONFIG = dict(
 )
 
 
-def _pad8(c):
-    return (c + 7) // 8 * 8
-
-
-def _pad64(n):
-    return (n + 63) // 64 * 64
-
-
-class _Ctx:
-    """Shared state of one model instance: flat parameters, shadow, gradient views, compute dtype."""
+class _Ctx(FlatParams):
+    """The UNet's store: the flat parameters (flat.FlatParams) + the side stream of the weight gradients + the adapter dispatch."""
 
     def __init__(self):
-        self.registry = {}
-        self.n = 0
-        self.flat = None
-        self.shadow = None
-        self.bf16 = True
+        super().__init__()
         self.side = None
         self._join_queued = False
         self._held = collections.deque()
@@ -101,52 +89,26 @@ class _Ctx:
         # weight gradients read can go back to the allocator now (they were held across the next forward before: several GB)
         self._held.clear()
 
-    def add(self, name, shape):
-        self.registry[name] = (self.n, tuple(shape))
-        self.n += _pad64(math.prod(shape))
-
-    def _view(self, buf, name):
-        if isinstance(name, tuple):  # (first name, n): n equally shaped matrices stored back to back, seen as one
-            first, n = name
-            off, (rows, cols) = self.registry[first]
-            return buf[off:off + n * rows * cols].view(n * rows, cols)
-        off, shape = self.registry[name]
-        return buf[off:off + math.prod(shape)].view(shape)
-
     def span(self, names):
-        """(first, n) when `names` sit back to back with no padding between them (one stacked GEMM operand), else None"""
-        off, shape = self.registry[names[0]]
-        for i, nm in enumerate(names):
-            o, sh = self.registry[nm]
-            if sh != shape or len(sh) != 2 or o != off + i * math.prod(shape):
-                return None
-        if self.ad is not None:  # all adapted or none; adapted fp32 operands must sit back to back in the effective copy
+        span = super().span(names)
+        # all adapted or none; adapted fp32 operands must sit back to back in the effective copy
+        if span is not None and self.ad is not None:
             flags = [nm in self.ad.seg for nm in names]
             if any(flags) and not all(flags):
                 return None
             if all(flags) and not self.bf16 and not self.ad.eff_contiguous(self, names):
                 return None
-        return (names[0], len(names))
-
-    def base32(self, name):  # the (frozen) base weights, whether or not adapters are attached
-        return self._view(self.flat.data, name)
+        return span
 
     def w32(self, name):
         if self.ad is not None and self.adapted(name):
             return self.ad.eff_view(self, name)
         return self._view(self.flat.data, name)
 
-    def w(self, name):  # GEMM operand copy
-        if self.bf16:
-            return self._view(self.shadow, name)
-        return self.w32(name)
-
     def g(self, name):
         if self.ad is not None:  # frozen base: gradients exist for the norm adapters only (None: a frozen tensor)
             return self.ad.grad_view(self, name)
-        if self.flat.grad is None:
-            self.flat.grad = torch.zeros_like(self.flat.data)
-        return self._view(self.flat.grad, name)
+        return super().g(name)
 
     # ---- adapters
     def adapted(self, name):
@@ -165,10 +127,6 @@ class _Ctx:
             self._index = {n: i for i, n in enumerate(self._names)}
         i = self._index[name[0]]
         return self._names[i:i + name[1]]
-
-    @property
-    def dtype(self):
-        return torch.bfloat16 if self.bf16 else torch.float32
 
 
 def _memset_zero(t):
@@ -229,7 +187,7 @@ class _Adapters:
         for nm in self.names:
             if not P.bf16 or self.seg[nm][1] == 0 or nm in self.fp32_names:
                 self.eff_off[nm] = n
-                n += _pad64(math.prod(P.registry[nm][1]))
+                n += pad64(math.prod(P.registry[nm][1]))
         self.eff = torch.empty(max(n, 64), device=P.flat.device, dtype=torch.float32)
         self.tab = self._table(P, self.eff_off, P.bf16)
         self.key, self.version = key, None
@@ -645,9 +603,9 @@ def sinusoid(t, dim, max_period=10000.0):
     return out
 
 
-class UNet2DConditionModel(nn.Module):
+class UNet2DConditionModel(FlatModule):
     def __init__(self, config=None, compute_dtype="bf16", **kw):
-        super().__init__()
+        super().__init__(_Ctx)
         # init_weights=False: leave the flat parameter buffer zero (a state dict is loaded next; the default initialisers draw
         # 0.9-2.6 G random numbers on the host)
         init_weights = kw.pop("init_weights", True)
@@ -669,8 +627,8 @@ class UNet2DConditionModel(nn.Module):
         boc = list(cfg["block_out_channels"])
         self.G = cfg["norm_num_groups"]
         self.temb = boc[0] * 4
-        P = self.P = _Ctx()
-        self.cin_pad, self.cout_pad = _pad8(cfg["in_channels"]), _pad8(cfg["out_channels"])
+        P = self.P
+        self.cin_pad, self.cout_pad = pad8(cfg["in_channels"]), pad8(cfg["out_channels"])
         self._conv_meta = {}
 
         # module name -> layer class (Linear / Conv2d / GroupNorm / LayerNorm): the LyCORIS preset matching (adapters.py)
@@ -785,10 +743,7 @@ class UNet2DConditionModel(nn.Module):
         norm("conv_norm_out", boc[0])
         conv("conv_out", boc[0], cfg["out_channels"], cout_store=self.cout_pad)
 
-        self.flat = nn.Parameter(torch.zeros(P.n, dtype=torch.float32, device=device))
-        P.flat = self.flat
-        P.bf16 = compute_dtype == "bf16"
-        self.register_buffer("shadow", torch.zeros(0, dtype=torch.bfloat16), persistent=False)
+        self._alloc(compute_dtype == "bf16", device)
         if init_weights:
             self.reset_parameters()
         else:
@@ -834,79 +789,24 @@ class UNet2DConditionModel(nn.Module):
                 w[cout:] = 0
                 self.P.base32(cname + ".bias")[cout:] = 0
 
-    def named_tensors(self):
-        """(diffusers name, tensor in diffusers layout) pairs; conv weights are returned as [Cout, Cin, 3, 3]."""
-        for name in self.P.registry:
-            v = self.P.base32(name)
-            base = name[:-7] if name.endswith(".weight") else name[:-5]
-            if base in self._conv_meta:
-                cin, cout, ci, co = self._conv_meta[base]
-                if name.endswith(".weight"):
-                    v = v.view(co, 3, 3, ci)[:cout, :, :, :cin].permute(0, 3, 1, 2)
-                else:
-                    v = v[:cout]
-            elif name.endswith("conv_shortcut.weight"):
-                v = v[:, :, None, None]
-            yield name, v
+    _after_load = _zero_padding
 
-    def state_dict(self, *args, destination=None, prefix="", keep_vars=False):
-        sd = destination if destination is not None else {}
-        for name, v in self.named_tensors():
-            sd[prefix + name] = v.detach().clone().contiguous()
-        return sd
-
-    @torch.no_grad()
-    def load_state_dict(self, state_dict, strict=True, assign=False):
-        missing = []
-        for name in self.P.registry:
-            if name not in state_dict:
-                missing.append(name)
-                continue
-            src = state_dict[name].float()
-            dst = self.P.base32(name)
-            base = name[:-7] if name.endswith(".weight") else name[:-5]
-            if base in self._conv_meta:
-                cin, cout, ci, co = self._conv_meta[base]
-                if name.endswith(".weight"):
-                    dst.view(co, 3, 3, ci)[:cout, :, :, :cin].copy_(src.permute(0, 2, 3, 1))
-                else:
-                    dst[:cout].copy_(src)
-            else:
-                dst.copy_(src.reshape(dst.shape))
-        if strict and missing:
-            raise RuntimeError(f"Missing key(s) in state_dict: {missing[:5]}...")
-        self._zero_padding()
-        self.refresh_shadow()
-        return torch.nn.modules.module._IncompatibleKeys(missing, [])
+    def _public_view(self, v, name):
+        """diffusers' layout: conv weights as [Cout, Cin, 3, 3] without the padded channels, the 1x1 shortcut as [Cout, Cin, 1, 1]"""
+        base, _, leaf = name.rpartition(".")
+        if base in self._conv_meta:
+            return self._conv_public(v, self._conv_meta[base], 9, leaf == "bias")
+        if name.endswith("conv_shortcut.weight"):
+            return v[:, :, None, None]
+        return v
 
     def grad_tensor(self, name):
         """Gradient of a parameter in diffusers layout (for parity checks)."""
-        gv = self.P.g(name)
-        base = name[:-7] if name.endswith(".weight") else name[:-5]
-        if base in self._conv_meta:
-            cin, cout, ci, co = self._conv_meta[base]
-            return gv.view(co, 3, 3, ci)[:cout, :, :, :cin].permute(0, 3, 1, 2) if name.endswith(".weight") else gv[:cout]
-        if name.endswith("conv_shortcut.weight"):
-            return gv[:, :, None, None]
-        return gv
+        return self._public_view(self.P.g(name), name)
 
-    @torch.no_grad()
-    def refresh_shadow(self):
+    def _shadow_stale(self):
         if self.P.ad is not None:  # the effective weights of the adapted tensors are merged again before the next forward
             self.P.ad.net.mark_dirty()
-        if not self.P.bf16 or not self.flat.is_cuda:
-            return
-        if self.shadow.numel() != self.P.n or self.shadow.device != self.flat.device:
-            self.shadow = torch.empty(self.P.n, device=self.flat.device, dtype=torch.bfloat16)
-        L.call("uwu_cast_f32_to_bf16", L.ptr(self.flat.data), L.ptr(self.shadow), self.P.n, L.stream())
-        self.P.shadow = self.shadow
-        self.flat._uwu_bf16_shadow = self.shadow
-
-    def _apply(self, fn, recurse=True):
-        r = super()._apply(fn, recurse)
-        self.P.flat = self.flat
-        self.refresh_shadow()
-        return r
 
     # ------------------------------------------------------------------ LyCORIS adapters (adapters.py, DESIGN.md 4.21)
     def _fp32_weight_names(self):

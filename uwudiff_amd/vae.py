@@ -12,8 +12,8 @@ last), GroupNorm + SiLU + conv_out -- keeps diffusers' parameter names in ``stat
   * activations stay channels-last ``[B*H*W, C]`` in the compute dtype between kernels; 3x3 convolutions are the implicit
     GEMM of the UNet (``uwu_conv3x3_fwd``), the encoder's downsampler is ``uwu_conv3x3_s2br_fwd``, the mid-block attention
     (one head of width 512) is ``uwu_attention_d512_fwd``, the posterior draw is ``uwu_posterior_draw``;
-  * all parameters live in one flat fp32 buffer (+ bf16 shadow), registered and viewed with the UNet's helpers
-    (``unet._Ctx``); conv weights sit there as ``[Cout][3][3][C]``; ``in_channels`` / ``out_channels`` / ``2 * latent`` are
+  * all parameters live in one flat fp32 buffer (+ bf16 shadow), the store every model here shares (``flat.FlatModule``);
+    conv weights sit there as ``[Cout][3][3][C]``; ``in_channels`` / ``out_channels`` / ``2 * latent`` are
     padded to 8 with zero weights;
   * there is no backward, no CPU path, no tiling / slicing, no ``kl()``.
 """
@@ -22,11 +22,10 @@ import math
 import os
 
 import torch
-import torch.nn as nn
 
 from . import lib as L
 from . import ops
-from .unet import _Ctx, _pad8
+from .flat import FlatModule, pad8
 
 SDXL_VAE_CONFIG = dict(
     in_channels=3, out_channels=3, latent_channels=4, block_out_channels=(128, 256, 512, 512), layers_per_block=2,
@@ -123,9 +122,7 @@ class DecoderOutput:
         return (self.sample,)[i]
 
 
-class AutoencoderKL(nn.Module):
-    _uwu_keep_fp32_master = True  # duwu.loader.prepare_model: `precision: torch.float16` must not cast the flat fp32 master
-
+class AutoencoderKL(FlatModule):
     def __init__(self, config=None, compute_dtype="bf16", **kw):
         super().__init__()
         init_weights = kw.pop("init_weights", True)
@@ -145,9 +142,9 @@ class AutoencoderKL(nn.Module):
         self.compute_dtype = compute_dtype
         self.G = int(cfg["norm_num_groups"])
         self.latent = int(cfg["latent_channels"])
-        self.cin_pad, self.cout_pad = _pad8(cfg["in_channels"]), _pad8(cfg["out_channels"])
-        self.mom_pad, self.lat_pad = _pad8(2 * self.latent), _pad8(self.latent)
-        P = self.P = _Ctx()
+        self.cin_pad, self.cout_pad = pad8(cfg["in_channels"]), pad8(cfg["out_channels"])
+        self.mom_pad, self.lat_pad = pad8(2 * self.latent), pad8(self.latent)
+        P = self.P
         self._conv_meta = {}  # 3x3 convolutions: name -> (cin, cout, stored cin, stored cout)
         self._pw_meta = {}    # 1x1 convolutions, stored as Linear [cout, cin]: the same
 
@@ -224,34 +221,19 @@ class AutoencoderKL(nn.Module):
         pw("quant_conv", 2 * self.latent, 2 * self.latent, ci=self.mom_pad, co=self.mom_pad)
         pw("post_quant_conv", self.latent, self.latent, ci=self.lat_pad, co=self.lat_pad)
 
-        self.flat = nn.Parameter(torch.zeros(P.n, dtype=torch.float32, device=device), requires_grad=False)
-        P.flat = self.flat
-        P.bf16 = compute_dtype == "bf16"
-        self.register_buffer("shadow", torch.zeros(0, dtype=torch.bfloat16), persistent=False)
+        self._alloc(compute_dtype == "bf16", device, trainable=False)
         if init_weights:
             self.reset_parameters()
         self.eval()
 
     # ------------------------------------------------------------------ parameters
-    def _meta(self, name):
-        base = name[:-7] if name.endswith(".weight") else name[:-5]
-        if base in self._conv_meta:
-            return 9, self._conv_meta[base]
-        if base in self._pw_meta:
-            return 1, self._pw_meta[base]
-        return 0, None
-
-    def _diffusers_view(self, v, name):
-        """the stored tensor `v` of registry entry `name` in diffusers' layout (a view: writes go to the flat buffer)"""
-        taps, meta = self._meta(name)
-        if not taps:
-            return v
-        cin, cout, ci, co = meta
-        if name.endswith(".bias"):
-            return v[:cout]
-        if taps == 9:
-            return v.view(co, 3, 3, ci)[:cout, :, :, :cin].permute(0, 3, 1, 2)
-        return v[:cout, :cin, None, None]
+    def _public_view(self, v, name):
+        """diffusers' layout of a 3x3 / 1x1 convolution: [Cout, Cin, k, k] without the padded channels"""
+        base, _, leaf = name.rpartition(".")
+        for taps, meta in ((9, self._conv_meta), (1, self._pw_meta)):
+            if base in meta:
+                return self._conv_public(v, meta[base], taps, leaf == "bias")
+        return v
 
     @torch.no_grad()
     def reset_parameters(self):
@@ -260,7 +242,7 @@ class AutoencoderKL(nn.Module):
         g = torch.Generator(device=self.flat.device).manual_seed(torch.initial_seed() % (2 ** 31))
         fan = {}
         for name, (off, shape) in self.P.registry.items():
-            v = self._diffusers_view(self.P.base32(name), name)
+            v = self._public_view(self.P.base32(name), name)
             if name.endswith(".weight") and len(shape) == 1:
                 v.fill_(1.0)
             elif name.endswith(".weight"):
@@ -271,52 +253,6 @@ class AutoencoderKL(nn.Module):
             else:
                 v.zero_()
         self.refresh_shadow()
-
-    def named_tensors(self):
-        for name in self.P.registry:
-            yield name, self._diffusers_view(self.P.base32(name), name)
-
-    def state_dict(self, *args, destination=None, prefix="", keep_vars=False):
-        sd = destination if destination is not None else {}
-        for name, v in self.named_tensors():
-            sd[prefix + name] = v.detach().clone().contiguous()
-        return sd
-
-    @torch.no_grad()
-    def load_state_dict(self, state_dict, strict=True, assign=False):
-        missing = [n for n in self.P.registry if n not in state_dict]
-        unexpected = [n for n in state_dict if n not in self.P.registry]
-        if strict and (missing or unexpected):
-            raise RuntimeError(f"Error(s) in loading state_dict for AutoencoderKL: missing {missing[:5]}, unexpected {unexpected[:5]}")
-        todo = []
-        for name in self.P.registry:
-            if name in missing:
-                continue
-            dst = self._diffusers_view(self.P.base32(name), name)
-            src = state_dict[name]
-            if tuple(src.shape) != tuple(dst.shape):
-                raise RuntimeError(f"size mismatch for {name}: copying a param with shape {tuple(src.shape)}, the model has "
-                                   f"{tuple(dst.shape)}")
-            todo.append((dst, src))
-        for dst, src in todo:
-            dst.copy_(src.float())
-        self.refresh_shadow()
-        return torch.nn.modules.module._IncompatibleKeys(missing, unexpected)
-
-    @torch.no_grad()
-    def refresh_shadow(self):
-        if not self.P.bf16 or not self.flat.is_cuda:
-            return
-        if self.shadow.numel() != self.P.n or self.shadow.device != self.flat.device:
-            self.shadow = torch.empty(self.P.n, device=self.flat.device, dtype=torch.bfloat16)
-        L.call("uwu_cast_f32_to_bf16", L.ptr(self.flat.data), L.ptr(self.shadow), self.P.n, L.stream())
-        self.P.shadow = self.shadow
-
-    def _apply(self, fn, recurse=True):
-        r = super()._apply(fn, recurse)
-        self.P.flat = self.flat
-        self.refresh_shadow()
-        return r
 
     # ------------------------------------------------------------------ blocks (forward only, channels-last tokens)
     def _gn(self, x, name, B, HW, C, silu):
