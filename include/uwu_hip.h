@@ -432,6 +432,36 @@ int uwu_bias_act_fwd(const void* x, const float* bias, void* y, int M, int N, in
  * p_b = first position whose id equals eos_id, position 0 if there is none (`(input_ids == eos).int().argmax(-1)`).
  * h [B*T, D], pooled [B, D] in `dtype`; D a multiple of 8. */
 int uwu_text_pool(const int64_t* ids, const void* h, void* pooled, int B, int T, int D, int eos_id, int dtype, void* stream);
+/* Self-attention of a T5 encoder, forward only, no lse (transformers T5Attention: bidirectional, a learned bias per head that
+ * depends on key - query only, plus the padding mask built from `attention_mask`):
+ *   o = softmax(scale * Q K^T + rel_bias[h, j - i + T - 1] + M) V      i: query, j: key
+ * rel_bias: fp32 [H, 2 T - 1] (uwu_t5_rel_bias gathers it; no [H, T, T] tensor exists anywhere).  key_mask: int64 [B, T] or NULL;
+ * key j is visible iff key_mask == NULL or key_mask[b, j] != 0.  A hidden key never contributes, whatever its K / V rows hold (NaN
+ * included).  Precondition: every sequence has at least one visible key; a sequence without one gives rows of zeros, not NaN.
+ * Addressing as uwu_attention_causal_fwd (packed [B*T, 3*H*64] projections are read in place: strides in elements, multiples of 8
+ * (bf16) / 4 (fp32), 16-byte aligned bases).  d == 64, 1 <= T <= 512, B * H <= 65535; anything else is refused.  T5 passes scale
+ * = 1.  bf16: MFMA kernel tiled over blocks of 64 queries, keys walked 64 at a time with an online softmax (T padded to the tile
+ * inside the kernel); fp32: exact-fp32 VALU kernel. */
+int uwu_attention_relbias_fwd(const void* q, const void* k, const void* v, const float* rel_bias, const int64_t* key_mask, void* o,
+                              int B, int T, int H, int d, int ldq, int ldk, int ldv, int ldo, float scale, int dtype, void* stream);
+/* T5LayerNorm with the previous sublayer's residual add fused in:  x_out = x_in + y (y may be NULL: x_out is then not written and
+ * may be NULL),  n_out = x_out * rsqrt(mean(x_out^2) + eps) * weight -- no mean subtraction, no bias.  x_in, y, x_out, n_out [M, D]
+ * contiguous in `dtype`, weight fp32 [D]; D a multiple of 8, 16-byte aligned; statistics in fp32, taken of x_out as stored.
+ * x_out may be x_in; n_out aliases nothing. */
+int uwu_add_rmsnorm_fwd(const void* x_in, const void* y, const float* weight, void* x_out, void* n_out, int M, int D, float eps,
+                        int dtype, void* stream);
+/* The gate of T5 v1.1's feed-forward:  out[M, F] = act(u[:, :F]) * u[:, F:2F]  on the [M, 2F] output of one GEMM over wi_0 | wi_1
+ * stored back to back (rows of stride ldu / ldo elements, multiples of 8; F a multiple of 8; 16-byte aligned; out must not overlap
+ * u).  UWU_GATE_GELU_TANH: transformers NewGELUActivation, 0.5 x (1 + tanh(sqrt(2 / pi) (x + 0.044715 x^3))).  fp32 tensors are
+ * evaluated in double, bf16 tensors in fp32. */
+#define UWU_GATE_GELU_TANH 0
+int uwu_gated_act_fwd(const void* u, void* out, int M, int F, int ldu, int ldo, int kind, int dtype, void* stream);
+/* T5's relative-position bias per offset:  out[h, o] = weight[bucket[o], h]  for o = key - query + T - 1 in [0, n), n = 2 T - 1.
+ * weight fp32 [num_buckets, H] (relative_attention_bias.weight), bucket int32 [n] (computed by the host; entries are clamped to
+ * the table), out fp32 [H, n]. */
+int uwu_t5_rel_bias(const float* weight, const int32_t* bucket, float* out, int num_buckets, int H, int n, void* stream);
+/* out[b,t,:] = tok_table[ids[b,t],:]: uwu_text_embed without a position table (T5 has none); the same clamping of ids. */
+int uwu_token_embed(const int64_t* ids, const void* tok_table, void* out, int B, int T, int D, int vocab, int dtype, void* stream);
 /* dq/dk/dv use the strides of q/k/v; dO uses ldo.  delta: fp32 workspace [B,H,Tq] (rowsum(dO*O)). */
 int uwu_attention_bwd(const void* q, const void* k, const void* v, const void* o, const void* dO,
                       const float* lse, float* delta, void* dq, void* dk, void* dv, int B, int Tq, int Tk, int H,

@@ -14,7 +14,9 @@ HIDDEN = {"text_encoder": 768, "text_encoder_2": 1280}
 
 
 class SyntheticTokenizer:
-    """Whitespace tokenizer hashed into a 49408-entry vocabulary; CLIP-style bos/eos/pad to 77."""
+    """Whitespace tokenizer hashed into a 49408-entry vocabulary; CLIP-style bos/eos/pad to 77.  A name that contains ``t5`` (any
+    case) gives the T5-shaped stand-in instead: ids hashed into [3, 32100) of the 32128-entry SentencePiece vocabulary, eos 1,
+    pad 0, no bos, up to 512 tokens (ConcatTextEncoders' ``max_length`` still caps it)."""
 
     model_max_length = 77
     vocab_size = 49408
@@ -23,14 +25,19 @@ class SyntheticTokenizer:
 
     def __init__(self, name="synthetic"):
         self.name = name
+        self.t5 = "t5" in str(name).lower()
+        if self.t5:
+            self.model_max_length, self.vocab_size, self.pad_token, self.eos_token = 512, 32128, "<pad>", "</s>"
 
     def _ids(self, text):
-        ids = [49406]
-        for w in text.lower().split():
-            ids.append(int(hashlib.md5(w.encode()).hexdigest(), 16) % 49000 + 300)
-        ids = ids[: self.model_max_length - 1] + [49407]
+        words = [int(hashlib.md5(w.encode()).hexdigest(), 16) for w in text.lower().split()]
+        if self.t5:
+            ids, eos, pad = [w % 32097 + 3 for w in words], 1, 0
+        else:
+            ids, eos, pad = [49406] + [w % 49000 + 300 for w in words], 49407, 49407
+        ids = ids[: self.model_max_length - 1] + [eos]
         n = len(ids)
-        ids = ids + [49407] * (self.model_max_length - n)
+        ids = ids + [pad] * (self.model_max_length - n)
         mask = [1] * n + [0] * (self.model_max_length - n)
         return ids, mask
 

@@ -77,8 +77,8 @@ class FlatModule(nn.Module):
     """Base of the models: ``self.P`` (the store), ``self.flat`` (parameter or buffer) and the non-persistent ``shadow`` buffer.
 
     A model adds its tensors to ``self.P`` and calls ``_alloc``; its public (checkpoint) names and layouts come from two hooks,
-    ``_public_names`` and ``_public_view``; ``_load_key``, ``_after_load``, ``_wants_shadow``, ``_shadow_stale`` and ``_moved``
-    cover what else differs between them."""
+    ``_public_names`` and ``_public_view``; ``_load_key``, ``_prepare_load``, ``_after_load``, ``_wants_shadow``, ``_shadow_stale``
+    and ``_moved`` cover what else differs between them."""
 
     _uwu_keep_fp32_master = True  # duwu.loader.prepare_model: `precision: torch.float16` leaves this module's dtype alone
 
@@ -130,6 +130,10 @@ class FlatModule(nn.Module):
         """a key of a loaded state dict -> public name (None: an entry to pass over)"""
         return key
 
+    def _prepare_load(self, state_dict):
+        """the state dict as the loader should see it (a tensor stored once under two public names); raises to refuse the load"""
+        return state_dict
+
     def _after_load(self):
         pass
 
@@ -161,6 +165,7 @@ class FlatModule(nn.Module):
     @torch.no_grad()
     def load_state_dict(self, state_dict, strict=True, assign=False):
         """Every key is resolved and every shape checked against the public view first; a refused load has written nothing."""
+        state_dict = self._prepare_load(state_dict)
         views = dict(self.named_tensors())
         todo, unexpected, errors = {}, [], []
         for key, src in state_dict.items():

@@ -16,6 +16,7 @@ F32, BF16 = 0, 1
 PT = {"epsilon": 0, "v_prediction": 1, "sample": 2, "rectified_flow": 3}
 EPI_NONE, EPI_BIAS, EPI_BIAS_GELU, EPI_DGELU, EPI_BIAS_SILU, EPI_ACCUM = 0, 1, 2, 3, 4, 5
 ACT = {"quick_gelu": 0, "gelu": 1}  # UWU_ACT_QUICK_GELU, UWU_ACT_GELU_ERF
+GATE = {"gated-gelu": 0}  # UWU_GATE_GELU_TANH
 
 
 class UwuError(RuntimeError):
@@ -109,6 +110,11 @@ _SIGS = {
     "uwu_text_embed": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, P]),
     "uwu_bias_act_fwd": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, P]),
     "uwu_text_pool": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, P]),
+    "uwu_attention_relbias_fwd": (c_int, [P] * 6 + [c_int] * 8 + [c_float, c_int, P]),
+    "uwu_add_rmsnorm_fwd": (c_int, [P] * 5 + [c_int, c_int, c_float, c_int, P]),
+    "uwu_gated_act_fwd": (c_int, [P, P] + [c_int] * 6 + [P]),
+    "uwu_t5_rel_bias": (c_int, [P, P, P, c_int, c_int, c_int, P]),
+    "uwu_token_embed": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, P]),
     "uwu_attention_bwd": (c_int, [P] * 10 + [c_int] * 9 + [c_float, c_int, P]),
     "uwu_attention_bias_fwd": (c_int, [P] * 6 + [c_int] * 9 + [c_float, c_int, P]),
     "uwu_attention_bias_bwd": (c_int, [P] * 11 + [c_int] * 9 + [c_float, c_int, P]),

@@ -213,6 +213,59 @@ def text_pool(ids, h, eos_id):
     return pooled
 
 
+def attention_relbias_fwd(q, k, v, rel_bias, B, T, H, d=64, scale=1.0, key_mask=None):
+    """Bidirectional self-attention of the T5 encoder, forward only: q / k / v 2-D views [B*T, >= H*d] with unit inner stride (column
+    slices of the packed projection), rel_bias fp32 [H, 2T - 1] indexed by key - query + T - 1 -> o [B*T, H*d].  key_mask: optional
+    int64 [B, T] (attention_mask; at least one visible key per sequence)."""
+    if rel_bias.dtype != torch.float32 or tuple(rel_bias.shape) != (H, 2 * T - 1):
+        raise L.UwuError(f"rel_bias must be fp32 [H, 2T - 1] = [{H}, {2 * T - 1}], got {rel_bias.dtype} {tuple(rel_bias.shape)}")
+    o = torch.empty(B * T, H * d, device=q.device, dtype=q.dtype)
+    L.call("uwu_attention_relbias_fwd", _p(q), _p(k), _p(v), L.ptr(rel_bias), None if key_mask is None else _ids(key_mask, B, T, "key_mask"),
+           L.ptr(o), B, T, H, d, q.stride(0), k.stride(0), v.stride(0), o.stride(0), scale, L.dt(q), L.stream())
+    return o
+
+
+def add_rmsnorm_fwd(x_in, weight, eps, y=None):
+    """(x_in + y, RMSNorm(x_in + y) * weight) on [M, D]; without y the first is x_in itself.  weight fp32 [D]."""
+    M, D = x_in.shape
+    if weight.dtype != torch.float32 or tuple(weight.shape) != (D,) or (y is not None and (y.shape != x_in.shape or y.dtype != x_in.dtype)):
+        raise L.UwuError(f"add_rmsnorm_fwd: weight must be fp32 [{D}] and y like x_in")
+    x_out = torch.empty_like(x_in) if y is not None else x_in
+    n = torch.empty_like(x_in)
+    L.call("uwu_add_rmsnorm_fwd", L.ptr(x_in), L.ptr(y), L.ptr(weight), L.ptr(x_out) if y is not None else None, L.ptr(n), M, D, eps,
+           L.dt(x_in), L.stream())
+    return x_out, n
+
+
+def gated_act_fwd(u, kind="gated-gelu"):
+    """u [M, 2F] (the GEMM on wi_0 | wi_1) -> act(u[:, :F]) * u[:, F:] as [M, F]; kind "gated-gelu" (tanh GELU)."""
+    M, F2 = u.shape
+    if F2 % 2:
+        raise L.UwuError(f"gated_act_fwd: u must be [M, 2F], got {tuple(u.shape)}")
+    out = torch.empty(M, F2 // 2, device=u.device, dtype=u.dtype)
+    L.call("uwu_gated_act_fwd", _p(u), L.ptr(out), M, F2 // 2, u.stride(0), out.stride(0), L.GATE[kind], L.dt(u), L.stream())
+    return out
+
+
+def t5_rel_bias(weight, bucket):
+    """weight fp32 [num_buckets, H], bucket int32 [2T - 1] -> fp32 [H, 2T - 1] with out[h, o] = weight[bucket[o], h]."""
+    nb, H = weight.shape
+    if weight.dtype != torch.float32 or bucket.dtype != torch.int32 or bucket.dim() != 1:
+        raise L.UwuError("t5_rel_bias: weight must be fp32 [num_buckets, H] and bucket int32 [2T - 1]")
+    out = torch.empty(H, bucket.numel(), device=weight.device, dtype=torch.float32)
+    L.call("uwu_t5_rel_bias", L.ptr(weight), L.ptr(bucket), L.ptr(out), nb, H, bucket.numel(), L.stream())
+    return out
+
+
+def token_embed(ids, tok_table):
+    """tok_table[ids] -> [B*T, D] in the table's dtype (ids outside the table are clamped)."""
+    B, T = ids.shape
+    vocab, D = tok_table.shape
+    out = torch.empty(B * T, D, device=tok_table.device, dtype=tok_table.dtype)
+    L.call("uwu_token_embed", _ids(ids, B, T, "input_ids"), L.ptr(tok_table), L.ptr(out), B, T, D, vocab, L.dt(out), L.stream())
+    return out
+
+
 def posterior_draw(moments, B, latent, HW, seed=0, offset=0, *, sample=True, mean=False, logvar=False):
     """AutoencoderKL posterior from channels-last fp32 moments [B*HW, >= 2*latent]: (z, mean, logvar), each fp32 [B, latent, HW] or
     None; z = mean + exp(0.5 clamp(logvar, -30, 20)) * uwu_philox_normal(n, seed, offset)."""

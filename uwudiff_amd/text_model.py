@@ -1,4 +1,5 @@
-"""The CLIP text transformer (SDXL's two text encoders) on the HIP kernels: frozen, forward only.
+"""The text encoders on the HIP kernels, frozen, forward only: the CLIP text transformer (SDXL's two; DESIGN.md section 4.23, described
+here) and, at the end of the file, the T5 v1.1 encoder (section 4.25).
 
 The reference wraps ``transformers.CLIPTextModel`` / ``CLIPTextModelWithProjection`` in ``ConcatTextEncoders`` and runs them
 inside every training step under ``no_grad`` (reference src/duwu/modules/text_encoders.py:153-191, src/duwu/trainer/trainer.py:238).
@@ -17,6 +18,7 @@ runs every operator through ``libuwu_hip.so``:
 """
 import hashlib
 import json
+import math
 import os
 
 import torch
@@ -262,3 +264,234 @@ class CLIPTextModelWithProjection(CLIPTextModel):
         last, pooled, hidden = self._encode(input_ids, attention_mask)
         embeds = ops.gemm(pooled, self.w("text_projection.weight"))
         return (embeds, last, hidden) if output_hidden_states else (embeds, last)
+
+
+# ====================================================================================================== T5 v1.1 encoder
+_T5_COMMON = dict(vocab_size=32128, d_kv=64, relative_attention_num_buckets=32, relative_attention_max_distance=128,
+                  layer_norm_epsilon=1e-6, feed_forward_proj="gated-gelu", pad_token_id=0, eos_token_id=1)
+# google/t5-v1_1-*: the published release (encoder stacks only are built here)
+T5_CONFIGS = {
+    "google/t5-v1_1-small": dict(_T5_COMMON, d_model=512, d_ff=1024, num_heads=6, num_layers=8),
+    "google/t5-v1_1-base": dict(_T5_COMMON, d_model=768, d_ff=2048, num_heads=12, num_layers=12),
+    "google/t5-v1_1-large": dict(_T5_COMMON, d_model=1024, d_ff=2816, num_heads=16, num_layers=24),
+    "google/t5-v1_1-xl": dict(_T5_COMMON, d_model=2048, d_ff=5120, num_heads=32, num_layers=24),
+    "google/t5-v1_1-xxl": dict(_T5_COMMON, d_model=4096, d_ff=10240, num_heads=64, num_layers=24),
+}
+_T5_MAX_T = 512  # the longest sequence uwu_attention_relbias_fwd is built for
+
+
+def t5_offset_buckets(T, num_buckets=32, max_distance=128):
+    """int32 [2T - 1]: the bucket of every offset ``key - query`` in ``-(T - 1) .. T - 1`` under T5's bidirectional rule -- half
+    the buckets for each direction (keys after the query take the upper half); inside a half the distances below a quarter of
+    ``num_buckets`` get a bucket each, the rest are spaced logarithmically up to ``max_distance`` and everything farther shares
+    the last bucket.  The logarithm is taken in fp32, the precision the published checkpoints were trained with: a bucket edge
+    that falls on an integer distance must land on the side it landed on then."""
+    rel = torch.arange(-(T - 1), T, dtype=torch.long)
+    half = num_buckets // 2
+    exact = half // 2
+    dist = rel.abs()
+    far = dist.clamp_min(1).to(torch.float32) / exact
+    log_bucket = exact + (torch.log(far) / math.log(max_distance / exact) * (half - exact)).to(torch.long)
+    bucket = torch.where(dist < exact, dist, log_bucket.clamp_max(half - 1)) + (rel > 0).long() * half
+    return bucket.to(torch.int32)
+
+
+class T5EncoderModel(FlatModule):
+    """``transformers.T5EncoderModel`` for the v1.1 (gated-GELU) checkpoints: ``forward(...) -> (last_hidden_state[, hidden_states])``
+    (DESIGN.md section 4.25).  ``h = shared[ids]``; L blocks ``h += o(attn(RMS h))``, ``h += wo(gelu_new(wi_0 n) * wi_1 n)`` with
+    ``n = RMS h``; ``final_layer_norm``.  No biases, no attention scale; the relative-position bias of block 0 is shared by all
+    blocks and reaches the kernel as one fp32 row per head, gathered once per sequence length."""
+
+    kind = "t5"
+
+    def __init__(self, config=None, compute_dtype="bf16", **kw):
+        super().__init__()
+        init_weights = kw.pop("init_weights", True)
+        device = kw.pop("device", None)
+        seed = kw.pop("seed", None)
+        cfg = dict(T5_CONFIGS["google/t5-v1_1-small"])
+        cfg.update({k: v for k, v in (config or {}).items() if not k.startswith("_")})
+        cfg.update(kw)
+        if compute_dtype not in ("bf16", "fp32"):
+            raise ValueError(f"compute_dtype must be 'bf16' or 'fp32', got {compute_dtype!r}")
+        built = "built: the T5 v1.1 encoder -- d_kv = 64, feed_forward_proj = 'gated-gelu', widths that are multiples of 8"
+        if cfg["feed_forward_proj"] not in L.GATE:
+            raise ValueError(f"T5EncoderModel: feed_forward_proj {cfg['feed_forward_proj']!r} is not built ({built})")
+        if int(cfg["d_kv"]) != _HEAD_DIM:
+            raise ValueError(f"T5EncoderModel: d_kv = {cfg['d_kv']} is not built ({built})")
+        D, H, F = int(cfg["d_model"]), int(cfg["num_heads"]), int(cfg["d_ff"])
+        if D % 8 or F % 8 or D < 8 or F < 8 or H < 1 or cfg["relative_attention_num_buckets"] < 4:
+            raise ValueError(f"T5EncoderModel: d_model = {D}, d_ff = {F}, num_heads = {H} ({built})")
+        self.config = _Config(cfg)
+        self.compute_dtype = compute_dtype
+        self.dtype = torch.bfloat16 if compute_dtype == "bf16" else torch.float32
+        self._names = {}  # transformers name -> (stored name, first row, rows)
+        self._buckets, self._bias = {}, {}  # per T: the bucket of every offset (int32, device), the gathered bias [H, 2T - 1]
+        HD = H * _HEAD_DIM
+
+        def add(name, shape, public=True):
+            self.P.add(name, shape)
+            if public:
+                self._names[name] = (name, 0, None)
+
+        add("shared.weight", (cfg["vocab_size"], D))
+        self._names["encoder.embed_tokens.weight"] = ("shared.weight", 0, None)  # one storage under both names
+        for i in range(cfg["num_layers"]):
+            a, f = f"encoder.block.{i}.layer.0.", f"encoder.block.{i}.layer.1."
+            add(a + "SelfAttention.qkv.weight", (3 * HD, D), public=False)  # q, k, v back to back: one GEMM operand
+            for j, c in enumerate("qkv"):
+                self._names[f"{a}SelfAttention.{c}.weight"] = (a + "SelfAttention.qkv.weight", j * HD, HD)
+            add(a + "SelfAttention.o.weight", (D, HD))
+            if i == 0:
+                add(a + "SelfAttention.relative_attention_bias.weight", (cfg["relative_attention_num_buckets"], H))
+            add(a + "layer_norm.weight", (D,))
+            add(f + "DenseReluDense.wi.weight", (2 * F, D), public=False)  # wi_0 | wi_1: one GEMM, gated by uwu_gated_act_fwd
+            for j in range(2):
+                self._names[f"{f}DenseReluDense.wi_{j}.weight"] = (f + "DenseReluDense.wi.weight", j * F, F)
+            add(f + "DenseReluDense.wo.weight", (D, F))
+            add(f + "layer_norm.weight", (D,))
+        add("encoder.final_layer_norm.weight", (D,))
+        self._alloc(compute_dtype == "bf16", device, buffer=True)
+        if init_weights and self.flat.device.type != "meta":
+            self.reset_parameters(seed)
+        self.eval().requires_grad_(False)
+
+    # ------------------------------------------------------------------ parameters
+    def _public_names(self):
+        return self._names
+
+    _TIED = ("shared.weight", "encoder.embed_tokens.weight")
+
+    def _prepare_load(self, state_dict):
+        """the embedding table may come under either of its two names or both; two tables that differ are refused before anything
+        is written"""
+        sd = dict(state_dict)
+        a, b = (sd.get(k) for k in self._TIED)
+        if a is not None and b is not None:
+            if a.shape != b.shape or not torch.equal(a, b):
+                raise RuntimeError(f"Error(s) in loading state_dict for {type(self).__name__}: {self._TIED[0]} and {self._TIED[1]} are "
+                                   "one tensor in this model, the state dict holds two that differ")
+        elif a is not None or b is not None:  # one name given: the other is the same tensor, not a missing key
+            sd[self._TIED[0]] = sd[self._TIED[1]] = a if a is not None else b
+        return sd
+
+    @torch.no_grad()
+    def reset_parameters(self, seed=None):
+        """transformers' T5 initialisation at initializer_factor 1 (embedding N(0, 1); q N(0, (d_model d_kv)^-1/2); k, v, wi_0, wi_1
+        and the bias table N(0, d_model^-1/2); o N(0, (H d_kv)^-1/2); wo N(0, d_ff^-1/2); norms 1), drawn tensor by tensor on the
+        CPU from `seed` (default: torch.initial_seed()): the weights do not depend on the device, and the host never holds more
+        than one tensor"""
+        g = torch.Generator().manual_seed((torch.initial_seed() if seed is None else seed) % (2 ** 31))
+        c = self.config
+        D, F, HD = c["d_model"], c["d_ff"], c["num_heads"] * _HEAD_DIM
+        for name, v in self.named_tensors():
+            if name == self._TIED[1]:
+                continue
+            if "layer_norm" in name:
+                v.fill_(1.0)
+                continue
+            std = (1.0 if name == "shared.weight" else (D * _HEAD_DIM) ** -0.5 if name.endswith(".q.weight") else HD ** -0.5
+                   if name.endswith(".o.weight") else F ** -0.5 if name.endswith(".wo.weight") else D ** -0.5)
+            v.copy_(torch.randn(v.shape, generator=g) * std)
+        self.refresh_shadow()
+
+    def _shadow_stale(self):  # weights loaded, reset, or the model moved: the gathered bias is rebuilt on the next call
+        self._bias = {}
+
+    def _moved(self):
+        self._buckets = {}
+
+    # ------------------------------------------------------------------ forward
+    _require_device = CLIPTextModel._require_device
+
+    def _rel_bias(self, T):
+        """fp32 [H, 2T - 1] on the device; in steady state a dictionary lookup"""
+        if T not in self._bias:
+            c = self.config
+            if T not in self._buckets:
+                self._buckets[T] = t5_offset_buckets(T, c["relative_attention_num_buckets"], c["relative_attention_max_distance"]).to(
+                    self.flat.device)
+            self._bias[T] = ops.t5_rel_bias(self.w32("encoder.block.0.layer.0.SelfAttention.relative_attention_bias.weight"), self._buckets[T])
+        return self._bias[T]
+
+    def _rms(self, x, name, y=None):
+        """(x + y, RMSNorm(x + y)): the residual add of the sublayer that produced y happens here"""
+        return ops.add_rmsnorm_fwd(x, self.w32(name), float(self.config["layer_norm_epsilon"]), y=y)
+
+    @torch.no_grad()
+    def _encode(self, input_ids, attention_mask):
+        """-> (last_hidden_state [B, T, D], hidden_states: L + 1 tensors [B, T, D] -- the embeddings, the output of every block but
+        the last, and last_hidden_state itself: transformers' encoder stack appends its final state after final_layer_norm)"""
+        self._require_device(input_ids, "forward")
+        cfg = self.config
+        if input_ids.dim() != 2 or not 1 <= input_ids.shape[1] <= _T5_MAX_T:
+            raise ValueError(f"input_ids must be [B, T <= {_T5_MAX_T}], got {tuple(input_ids.shape)}")
+        B, T = input_ids.shape
+        D, H = cfg["d_model"], cfg["num_heads"]
+        HD = H * _HEAD_DIM
+        ids = input_ids.long().contiguous()
+        mask = None
+        if attention_mask is not None:
+            if not attention_mask.is_cuda or tuple(attention_mask.shape) != (B, T):
+                raise L.UwuError(f"attention_mask must be a device tensor [{B}, {T}], got {tuple(attention_mask.shape)}")
+            mask = attention_mask.long().contiguous()
+        bias = self._rel_bias(T)
+        x = ops.token_embed(ids, self.w("shared.weight"))
+        hidden, y = [], None
+        for i in range(cfg["num_layers"]):
+            a, f = f"encoder.block.{i}.layer.0.", f"encoder.block.{i}.layer.1."
+            x, n = self._rms(x, a + "layer_norm.weight", y)  # x: the input of block i = the output of block i - 1
+            hidden.append(x)
+            qkv = ops.gemm(n, self.w(a + "SelfAttention.qkv.weight"))
+            o = ops.attention_relbias_fwd(qkv[:, :HD], qkv[:, HD:2 * HD], qkv[:, 2 * HD:], bias, B, T, H, _HEAD_DIM, 1.0, key_mask=mask)
+            x, n = self._rms(x, f + "layer_norm.weight", ops.gemm(o, self.w(a + "SelfAttention.o.weight")))
+            u = ops.gemm(n, self.w(f + "DenseReluDense.wi.weight"))
+            y = ops.gemm(ops.gated_act_fwd(u, cfg["feed_forward_proj"]), self.w(f + "DenseReluDense.wo.weight"))
+        _, last = self._rms(x, "encoder.final_layer_norm.weight", y)
+        hidden.append(last)
+        return last.view(B, T, D), tuple(h.view(B, T, D) for h in hidden)
+
+    def forward(self, input_ids, attention_mask=None, output_hidden_states=False, return_dict=False, **kw):
+        if return_dict:
+            raise NotImplementedError("return_dict=True is not built: ConcatTextEncoders calls with return_dict=False")
+        extra = sorted(k for k, v in kw.items() if v is not None)
+        if extra:  # inputs_embeds, head_mask, output_attentions, ...: nothing is silently ignored
+            raise NotImplementedError(f"T5EncoderModel.forward: {extra} not built")
+        last, hidden = self._encode(input_ids, attention_mask)
+        return (last, hidden) if output_hidden_states else (last,)
+
+    # ------------------------------------------------------------------ construction
+    @classmethod
+    def from_config(cls, config, **kw):
+        return cls(dict(config), **kw)
+
+    @classmethod
+    def from_pretrained(cls, pretrained_model_name_or_path=None, subfolder=None, **kw):
+        """A local directory (``<path>[/<subfolder>]`` with ``config.json`` and ``model.safetensors``) is loaded.  Any other name ->
+        deterministic random weights (seeded by the name, not by the global seed) at the built-in configuration of that name
+        (``T5_CONFIGS``): nothing is ever fetched.  Without a ``device=`` the random model is built on the HIP device when there
+        is one -- google/t5-v1_1-xxl is 19 GB of fp32, which the host never holds: the weights are drawn tensor by tensor.
+        The local-directory path does not share that property yet: it builds the model where ``device=`` says (the CPU by
+        default, as CLIP's does) and reads the whole safetensors file into host memory before copying it, 19 GB for xxl."""
+        for k in ("torch_dtype", "variant", "use_safetensors", "cache_dir", "local_files_only", "revision"):
+            kw.pop(k, None)
+        src = str(pretrained_model_name_or_path)
+        local = os.path.join(src, subfolder) if subfolder else src
+        if os.path.isdir(local) and os.path.exists(os.path.join(local, "config.json")):
+            from safetensors.torch import load_file
+
+            with open(os.path.join(local, "config.json")) as f:
+                config = {k: v for k, v in json.load(f).items() if k in T5_CONFIGS["google/t5-v1_1-small"]}
+            config.update(kw.pop("config", None) or {})
+            model = cls(config, init_weights=False, **kw)
+            model.load_state_dict(load_file(os.path.join(local, "model.safetensors")))
+            return model
+        if src not in T5_CONFIGS:
+            raise ValueError(f"unknown T5 encoder {src!r}: not a local directory with config.json; built-in configurations: "
+                             f"{sorted(T5_CONFIGS)}")
+        config = dict(T5_CONFIGS[src])
+        config.update(kw.pop("config", None) or {})
+        if "device" not in kw and torch.cuda.is_available():
+            kw["device"] = "cuda"
+        # the same name gives the same weights in every process, whatever the global seed
+        return cls(config, seed=int.from_bytes(hashlib.md5(src.encode()).digest()[:4], "little"), **kw)
