@@ -163,6 +163,27 @@ int uwu_sampler_combine(const float* base, const float* eps_cond, const float* e
                         float* out, int64_t n, float cfg, float a, float b, float c, void* stream);
 int uwu_scale_copy(const float* x, float* y, int64_t n, float scale, void* stream);
 
+/* Prompt-to-image sampling glue.
+ * uwu_cfg_input: the guidance batch of the denoiser.  x fp32 [B, n] -> y fp32 [2B, n], both halves x * c_in: one read and two writes
+ *   instead of uwu_scale_copy + torch.cat (reference sampling/cfg.py:116-118, k_diffusion_wrapper.py:103-106).  B * n % 4 == 0.
+ * uwu_sampler_combine_draw: uwu_sampler_combine with the noise term drawn in the kernel -- element i takes element i of
+ *   uwu_philox_normal(n, seed, offset), the counter convention of uwu_qsample_draw -- so no noise tensor exists in memory
+ *   (k_diffusion_euler.py:46-47, :104-105; k_diffusion_dpm2.py:32-35, :86-89).  Same device functions as the two entries it fuses:
+ *   bit-identical to uwu_philox_normal followed by uwu_sampler_combine.  n % 4 == 0.
+ * uwu_latent_finish: y = (rescale ? x / std_b : x) * vae_std + vae_mean on fp32 [B, n] latents, std_b = torch.std over the n elements
+ *   of sample b (divisor n - 1) (sampling/sampling.py:114-116).  Two deterministic stages over a partition that depends on n alone
+ *   (per-workgroup partials added in ascending order): a sample's bits do not depend on its batch.  ws: uwu_latent_finish_ws_bytes(B, n)
+ *   bytes, needed with rescale only.  n % 4 == 0.
+ * uwu_image_u8: vae_image_postprocess for a batch (data/utils.py:10-19).  x [B, 3, H, W] (UWU_F32 / UWU_BF16) -> y uint8 [B, H, W, 3],
+ *   trunc(clamp((x * 0.5 + 0.5) * 255, 0, 255)) in fp32 in that order.  Any H, W. */
+int uwu_cfg_input(const float* x, float* y, int B, int64_t n, float c_in, void* stream);
+int uwu_sampler_combine_draw(const float* base, const float* eps_cond, const float* eps_uncond, float* out, int64_t n, float cfg,
+                             float a, float b, float c, uint64_t seed, uint64_t offset, void* stream);
+size_t uwu_latent_finish_ws_bytes(int B, int64_t n);
+int uwu_latent_finish(const float* x, float* y, int B, int64_t n, int rescale, float vae_std, float vae_mean, void* ws,
+                      size_t ws_bytes, void* stream);
+int uwu_image_u8(const void* x, int dtype, void* y, int B, int H, int W, void* stream);
+
 /* ------------------------------------------------------------------ optimizer (a15) */
 
 /* Global L2 norm of a flat fp32 buffer (Lightning gradient_clip_val, demo_training.yaml:12):

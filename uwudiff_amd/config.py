@@ -16,6 +16,7 @@ import yaml
 ALIASES = {
     "diffusers.EulerDiscreteScheduler": "uwudiff_amd.scheduler.EulerDiscreteScheduler",
     "diffusers.AutoencoderKL": "uwudiff_amd.vae.AutoencoderKL",
+    "diffusers.UNet2DConditionModel": "uwudiff_amd.unet.UNet2DConditionModel",  # the unet node of the sampling YAML
     "transformers.CLIPTextModel": "uwudiff_amd.conditioning.SyntheticCLIPTextModel",  # kind "clip_sd1": normed ctx = LN(layer_idx)
     "transformers.CLIPTextModelWithProjection": "uwudiff_amd.conditioning.SyntheticTextModel",
     "transformers.T5EncoderModel": "uwudiff_amd.text_model.T5EncoderModel",  # native: never the hub

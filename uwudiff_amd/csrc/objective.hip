@@ -597,6 +597,14 @@ extern "C" int uwu_sampler_step(const float* x, const float* eps_cond, const flo
 }
 
 // out = base + a * (eu + cfg (ec - eu)) + b * eu + c * noise ; eu == NULL: unguided (eu := ec); noise == NULL: c unused
+// One device function for the update: sampler_combine_kernel reads the noise, sampler_combine_draw_kernel draws it, and both
+// evaluate the same expression, so the two routes give the same bits.
+__device__ __forceinline__ f32x4 sampler_combine4(f32x4 xv, f32x4 cv, f32x4 uv, f32x4 nv, bool noisy, float cfg, float a, float b,
+                                                  float c) {
+  f32x4 o = xv + (uv + (cv - uv) * cfg) * a + uv * b;
+  if (noisy) o = o + nv * c;
+  return o;
+}
 __global__ void __launch_bounds__(256) sampler_combine_kernel(const float* __restrict__ base, const float* __restrict__ ec,
                                                               const float* __restrict__ eu, const float* __restrict__ nz,
                                                               float* __restrict__ out, int64_t n4, float cfg, float a,
@@ -604,9 +612,21 @@ __global__ void __launch_bounds__(256) sampler_combine_kernel(const float* __res
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
     const f32x4 xv = load4(base + 4 * i), cv = load4(ec + 4 * i);
     const f32x4 uv = eu ? load4(eu + 4 * i) : cv;
-    f32x4 o = xv + (uv + (cv - uv) * cfg) * a + uv * b;
-    if (nz) o = o + load4(nz + 4 * i) * c;
-    store4(out + 4 * i, o);
+    const f32x4 nv = nz ? load4(nz + 4 * i) : f32x4{0.f, 0.f, 0.f, 0.f};
+    store4(out + 4 * i, sampler_combine4(xv, cv, uv, nv, nz != nullptr, cfg, a, b, c));
+  }
+}
+// The same update with the noise drawn here: element i takes element i of uwu_philox_normal(n, seed, offset) (counter offset + i / 4,
+// the convention of qsample_draw_kernel).  16 B read per tensor and 16 B written per lane and trip; no noise tensor in memory.
+__global__ void __launch_bounds__(256) sampler_combine_draw_kernel(const float* __restrict__ base, const float* __restrict__ ec,
+                                                                   const float* __restrict__ eu, float* __restrict__ out, int64_t n4,
+                                                                   float cfg, float a, float b, float c, unsigned long long seed,
+                                                                   unsigned long long offset) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
+    const f32x4 xv = load4(base + 4 * i), cv = load4(ec + 4 * i);
+    const f32x4 uv = eu ? load4(eu + 4 * i) : cv;
+    const f32x4 nv = philox_normal4(offset + (unsigned long long)i, seed);
+    store4(out + 4 * i, sampler_combine4(xv, cv, uv, nv, true, cfg, a, b, c));
   }
 }
 
@@ -623,5 +643,17 @@ extern "C" int uwu_scale_copy(const float* x, float* y, int64_t n, float scale, 
   UWU_CHECK_ARG(x && y && n > 0 && n % 4 == 0, "scale_copy: bad args");
   hipLaunchKernelGGL(scale_copy_kernel, dim3(ew_grid(n / 4, 256)), dim3(256), 0, (hipStream_t)stream, x, y, n / 4, scale);
   UWU_LAUNCH_CHECK("scale_copy");
+  return UWU_OK;
+}
+
+extern "C" int uwu_sampler_combine_draw(const float* base, const float* eps_cond, const float* eps_uncond, float* out, int64_t n,
+                                        float cfg, float a, float b, float c, uint64_t seed, uint64_t offset, void* stream) {
+  UWU_CHECK_ARG(base && eps_cond && out, "sampler_combine_draw: null pointer");
+  UWU_CHECK_ARG(n > 0 && n % 4 == 0, "sampler_combine_draw: n=%lld must be a positive multiple of 4", (long long)n);
+  UWU_CHECK_ARG((((uintptr_t)base | (uintptr_t)eps_cond | (uintptr_t)eps_uncond | (uintptr_t)out) & 15) == 0,
+                "sampler_combine_draw: pointers must be 16-byte aligned");
+  hipLaunchKernelGGL(sampler_combine_draw_kernel, dim3(ew_grid(n / 4, 256)), dim3(256), 0, (hipStream_t)stream, base, eps_cond,
+                     eps_uncond, out, n / 4, cfg, a, b, c, (unsigned long long)seed, (unsigned long long)offset);
+  UWU_LAUNCH_CHECK("sampler_combine_draw");
   return UWU_OK;
 }

@@ -67,6 +67,11 @@ _SIGS = {
     "uwu_aggregate_first": (c_int, [P, P, P, c_int, c_int64, P]),
     "uwu_sampler_combine": (c_int, [P, P, P, P, P, c_int64, c_float, c_float, c_float, c_float, P]),
     "uwu_scale_copy": (c_int, [P, P, c_int64, c_float, P]),
+    "uwu_cfg_input": (c_int, [P, P, c_int, c_int64, c_float, P]),
+    "uwu_sampler_combine_draw": (c_int, [P, P, P, P, c_int64, c_float, c_float, c_float, c_float, ctypes.c_uint64, ctypes.c_uint64, P]),
+    "uwu_latent_finish_ws_bytes": (ctypes.c_size_t, [c_int, c_int64]),
+    "uwu_latent_finish": (c_int, [P, P, c_int, c_int64, c_int, c_float, c_float, P, ctypes.c_size_t, P]),
+    "uwu_image_u8": (c_int, [P, c_int, P, c_int, c_int, c_int, P]),
     "uwu_grad_sqnorm_clip": (c_int, [P, c_int64, c_float, c_float, P, P, P]),
     "uwu_adamw_step": (c_int, [P, P, P, P, P, c_int64, c_float, c_float, c_float, c_float, c_float, c_int, c_float,
                                P, c_int, P]),

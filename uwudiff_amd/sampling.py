@@ -226,3 +226,191 @@ def sample_dpm2_cfgpp(denoiser: DiscreteEpsDDPMDenoiser, x, sigmas, cond_kwargs,
         eps_c2, eps_u2 = _eval_eps(denoiser, x2, xin, s_mid, kw, True)
         x = _combine(x2, eps_c2, eps_u2, None, cfg, -s_mid, s_next)
     return x
+
+
+# ---- prompt-to-image path: the guided model that duwu.sampling's cfg_wrapper / cond_text_wrapper return, and the
+# loops over it.  Per step the glue is uwu_cfg_input (guidance batch) + uwu_sampler_combine[_draw] (update, noise drawn in the
+# kernel); the denoiser's fp32 output is read in place.
+def reserve_noise(device, n):
+    """(seed, offset) of the n / 4 Philox counters of one noise tensor of n elements, taken from torch's CUDA generator as
+    ``DiffusionLoss._reserve`` takes them: ``torch.manual_seed`` reproduces a run and consecutive reservations do not overlap."""
+    from .objective import DiffusionLoss
+
+    if n % 4:
+        raise L.UwuError(f"in-kernel noise needs a multiple of 4 elements, got {n}")
+    return DiffusionLoss._reserve(device, n // 4)
+
+
+def _scalar(s):
+    return float(s.reshape(-1)[0]) if torch.is_tensor(s) else float(s)
+
+
+class GuidedModel:
+    """cfg.py:9-127 as an object: holds the (doubled) context, mask and ``added_cond`` of a prompt batch and evaluates the eps model
+    on the guidance batch.  ``guided=False`` is ``cond_text_wrapper`` (one branch, no guidance).  Called as the reference's
+    closure, ``model(x, sigma, sigma_cond=None)``, it returns the ``(cfg_denoised, uncond_denoised)`` tensors (``(denoised, None)``
+    unguided); the fused loops below use :meth:`eps` instead and never form the denoised tensors."""
+
+    def __init__(self, denoiser, context, mask=None, added_cond=None, cfg=1.0, guided=True):
+        self.denoiser, self.context, self.mask, self.added_cond = denoiser, context, mask, added_cond
+        self.cfg, self.guided = float(cfg), bool(guided)
+        self.noise_draws = []  # (step, seed, offset) of every in-kernel draw of the last loop, in step order
+        self._xin = None
+
+    def to(self, device, dtype=None):
+        """Move the conditioning to ``device`` once (``dtype``: the context's, i.e. the denoiser's compute dtype)."""
+        self.context = self.context.to(device=device, dtype=dtype or self.context.dtype).contiguous()
+        if self.mask is not None:
+            self.mask = self.mask.to(device)
+        if self.added_cond is not None:
+            self.added_cond = {k: v.to(device=device, dtype=torch.float32).contiguous() for k, v in self.added_cond.items()}
+        return self
+
+    def _prepare(self, x):
+        store = getattr(self.denoiser.inner_model, "P", None)
+        self.to(x.device, getattr(store, "dtype", None))
+
+    @torch.no_grad()
+    def eps(self, x, sigma, sigma_cond=None):
+        """(eps_cond, eps_uncond | None) at (x, sigma): views of the denoiser's own fp32 output, no cast and no copy."""
+        s = _scalar(sigma)
+        B, n = x.shape[0], x.numel() // x.shape[0]
+        rows = 2 * B if self.guided else B
+        if self._xin is None or self._xin.shape != (rows,) + tuple(x.shape[1:]) or self._xin.device != x.device:
+            self._xin = torch.empty((rows,) + tuple(x.shape[1:]), device=x.device, dtype=torch.float32)
+        c_in = 1.0 / math.sqrt(s * s + 1.0)
+        if self.guided:
+            L.call("uwu_cfg_input", L.ptr(x), L.ptr(self._xin), B, n, c_in, L.stream())
+        else:
+            L.call("uwu_scale_copy", L.ptr(x), L.ptr(self._xin), x.numel(), c_in, L.stream())
+        kw = {"encoder_hidden_states": self.context}
+        if self.mask is not None:
+            kw["encoder_attention_mask"] = self.mask
+        if self.added_cond is not None:
+            kw["added_cond_kwargs"] = self.added_cond
+        out = self.denoiser.eps(self._xin, s if sigma_cond is None else _scalar(sigma_cond), **kw)
+        if out.dtype != torch.float32 or not out.is_contiguous() or tuple(out.shape) != tuple(self._xin.shape):
+            raise L.UwuError(f"the denoiser must return contiguous fp32 {tuple(self._xin.shape)}, got {out.dtype} {tuple(out.shape)}")
+        return (out[:B], out[B:]) if self.guided else (out, None)
+
+    @torch.no_grad()
+    def __call__(self, x, sigma, sigma_cond=None):
+        x = _as_latents(x)
+        self._prepare(x)
+        s = _scalar(sigma)
+        eps_c, eps_u = self.eps(x, s, sigma_cond)
+        if not self.guided:
+            return _combine(x, eps_c, None, None, 1.0, -s, 0.0), None
+        return _combine(x, eps_c, eps_u, None, self.cfg, -s, 0.0), _combine(x, eps_u, None, None, 1.0, -s, 0.0)
+
+
+def _as_latents(x):
+    if x.dtype != torch.float32 or not x.is_contiguous():
+        x = x.float().contiguous()
+    return x
+
+
+def _noisy_combine(model, step, base, eps_c, eps_u, a, b, c, noise_sampler, sig, sig_next):
+    """``_combine`` with a noise term: drawn inside uwu_sampler_combine_draw (one reservation of n / 4 counters), or read from the
+    caller's ``noise_sampler(sigma, sigma_next)`` tensor."""
+    if noise_sampler is not None:
+        return _combine(base, eps_c, eps_u, _as_latents(noise_sampler(sig, sig_next).to(base.device)), model.cfg, a, b, c)
+    seed, offset = reserve_noise(base.device, base.numel())
+    model.noise_draws.append((step, seed, offset))
+    out = torch.empty_like(base)
+    L.call("uwu_sampler_combine_draw", L.ptr(base), L.ptr(eps_c), L.ptr(eps_u) if eps_u is not None else None, L.ptr(out),
+           base.numel(), model.cfg, float(a), float(b), float(c), seed, offset, L.stream())
+    return out
+
+
+def _begin(model, x, sigmas, extra_args):
+    if extra_args:
+        raise ValueError("extra_args: the conditioning is bound by cfg_wrapper / cond_text_wrapper")
+    x = _as_latents(x)
+    model._prepare(x)
+    model.noise_draws = []
+    return x, [float(s) for s in sigmas]  # one host copy of the grid; the loop itself never synchronises
+
+
+@torch.no_grad()
+def guided_euler_ancestral(model: GuidedModel, x, sigmas, extra_args=None, callback=None, eta=1.0, s_noise=1.0, noise_sampler=None,
+                           cfgpp=False):
+    """k_diffusion_euler.py:8-48 (``cfgpp``: :51-106) over a :class:`GuidedModel`; per step uwu_cfg_input, the denoiser and one
+    uwu_sampler_combine[_draw].  x' = x + eps_cfg (sigma_down - sigma) (+ noise); cfg++: x' = x - sigma eps_cfg + sigma_down eps_uncond."""
+    x, sig = _begin(model, x, sigmas, extra_args)
+    if cfgpp and not model.guided:
+        raise ValueError("the CFG++ samplers need the model of cfg_wrapper (two branches)")
+    for i in range(len(sig) - 1):
+        s, s_next = sig[i], sig[i + 1]
+        eps_c, eps_u = model.eps(x, s)
+        sd, su = get_ancestral_step(s, s_next, eta)
+        if callback is not None:
+            info = {"x": x, "i": i, "sigma": sigmas[i], "sigma_hat": sigmas[i]}
+            den = _combine(x, eps_c, eps_u, None, model.cfg, -s, 0.0)
+            if cfgpp:
+                info.update(cfg_denoised=den, uncond_denoised=_combine(x, eps_u, None, None, 1.0, -s, 0.0))
+            else:
+                info["denoised"] = den
+            callback(info)
+        a, b = (-s, sd) if cfgpp else (sd - s, 0.0)
+        if s_next > 0:
+            x = _noisy_combine(model, i, x, eps_c, eps_u, a, b, s_noise * su, noise_sampler, sigmas[i], sigmas[i + 1])
+        else:
+            x = _combine(x, eps_c, eps_u, None, model.cfg, a, b)
+    return x
+
+
+@torch.no_grad()
+def guided_dpm2(model: GuidedModel, x, sigmas, extra_args=None, s_churn=0.0, s_tmin=0.0, s_tmax=float("inf"), s_noise=1.0,
+                single_call=False, noise_sampler=None, cfgpp=False):
+    """k_diffusion_dpm2.py:8-57 (``cfgpp``: :60-111, where the reference marks ``single_call`` as not working) over a
+    :class:`GuidedModel`.  Noise is drawn only on the steps that use it (gamma > 0)."""
+    x, sig = _begin(model, x, sigmas, extra_args)
+    if cfgpp and (single_call or not model.guided):
+        raise ValueError("sample_dpm2_cfgpp needs the model of cfg_wrapper and single_call=False")
+    cached = None
+    nsteps = len(sig) - 1
+    for i in range(nsteps):
+        s, s_next = sig[i], sig[i + 1]
+        gamma = min(s_churn / nsteps, 2 ** 0.5 - 1) if s_tmin <= s <= s_tmax else 0.0
+        s_hat = s * (gamma + 1)
+        if gamma > 0:  # x + noise * s_noise * sqrt(s_hat^2 - s^2): the combine with a = b = 0 (its eps operand is not used)
+            x = _noisy_combine(model, i, x, x, None, 0.0, 0.0, s_noise * (s_hat ** 2 - s ** 2) ** 0.5, noise_sampler, sigmas[i],
+                               sigmas[i + 1])
+        if s_next == 0:  # Euler step; cfg++: x = cfg_denoised
+            eps_c, eps_u = model.eps(x, s_hat)
+            x = _combine(x, eps_c, eps_u, None, model.cfg, -s_hat if cfgpp else s_next - s_hat, 0.0)
+            continue
+        if single_call and cached is not None:
+            eps_c, eps_u = cached
+        else:
+            eps_c, eps_u = model.eps(x, s_hat)
+        s_mid = math.exp(0.5 * (math.log(s_hat) + math.log(s_next)))
+        x2 = _combine(x, eps_c, eps_u, None, model.cfg, *((-s_hat, s_mid) if cfgpp else (s_mid - s_hat, 0.0)))
+        eps_c2, eps_u2 = model.eps(x2, s_mid)
+        cached = (eps_c2, eps_u2)  # every denoiser call returns a tensor of its own: the views stay valid
+        x = _combine(x2 if cfgpp else x, eps_c2, eps_u2, None, model.cfg, *((-s_mid, s_next) if cfgpp else (s_next - s_hat, 0.0)))
+    return x
+
+
+def latent_finish(x, rescale=False, vae_std=1.0, vae_mean=0.0):
+    """sampling.py:114-116 on fp32 [B, ...] latents: (x / x.std([1, 2, 3]) if rescale else x) * vae_std + vae_mean (uwu_latent_finish)."""
+    x = _as_latents(x)
+    B, n = x.shape[0], x.numel() // x.shape[0]
+    y = torch.empty_like(x)
+    ws, nbytes = None, 0
+    if rescale:
+        nbytes = int(L.load().uwu_latent_finish_ws_bytes(B, n))
+        ws = torch.empty(nbytes, device=x.device, dtype=torch.uint8)
+    L.call("uwu_latent_finish", L.ptr(x), L.ptr(y), B, n, int(bool(rescale)), float(vae_std), float(vae_mean), L.ptr(ws), nbytes, L.stream())
+    return y
+
+
+def image_u8(img):
+    """vae_image_postprocess (data/utils.py:10-19) for a batch: [B, 3, H, W] fp32 / bf16 on the device -> uint8 [B, H, W, 3]."""
+    if img.dim() != 4 or img.shape[1] != 3:
+        raise ValueError(f"image_u8: expected [B, 3, H, W], got {tuple(img.shape)}")
+    B, _, H, W = img.shape
+    out = torch.empty(B, H, W, 3, device=img.device, dtype=torch.uint8)
+    L.call("uwu_image_u8", L.ptr(img), L.dt(img), L.ptr(out), B, H, W, L.stream())
+    return out

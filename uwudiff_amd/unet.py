@@ -1052,14 +1052,31 @@ class UNet2DConditionModel(FlatModule):
         x = self._conv(x, "conv_out", B, h, w, boc[0])
         return (_FromCL.apply(x, B, cfg.out_channels, h, w, self.cout_pad),)
 
+    @staticmethod
+    def _preset(name):
+        presets = {"sdxl": SDXL_UNET_CONFIG, "stabilityai/stable-diffusion-xl-base-1.0": SDXL_UNET_CONFIG,
+                   "tiny-unet": TINY_UNET_CONFIG, "sdxl-rope": dict(SDXL_UNET_CONFIG, rope=True, zero_init=True),
+                   "sdxl-hd": dict(SDXL_UNET_CONFIG, zero_init=True)}
+        if name not in presets:
+            raise ValueError(f"unknown UNet config {name!r}; known: {sorted(presets)}")
+        return presets[name]
+
     @classmethod
     def from_config(cls, config, **kw):
         kw.pop("subfolder", None)
         if isinstance(config, str):
-            presets = {"sdxl": SDXL_UNET_CONFIG, "stabilityai/stable-diffusion-xl-base-1.0": SDXL_UNET_CONFIG,
-                       "tiny-unet": TINY_UNET_CONFIG, "sdxl-rope": dict(SDXL_UNET_CONFIG, rope=True, zero_init=True),
-                       "sdxl-hd": dict(SDXL_UNET_CONFIG, zero_init=True)}
-            if config not in presets:
-                raise ValueError(f"unknown UNet config {config!r}; known: {sorted(presets)}")
-            config = presets[config]
+            config = cls._preset(config)
         return cls(dict(config), **kw)
+
+    @classmethod
+    def from_pretrained(cls, pretrained_model_name_or_path=None, subfolder=None, **kw):
+        """``diffusers.UNet2DConditionModel.from_pretrained`` of the reference's sampling YAML (uwudiff_amd/config.py ALIASES).  A hub
+        name gives its preset shape with seeded default initialisation, as :meth:`from_config` treats it (nothing is fetched); a
+        ``config=`` mapping overrides entries of the preset, as for the text models.  Trained weights arrive afterwards through the
+        node's ``_load_config_`` (``ckpt_path``, ``state_dict_key``, ``state_dict_prefix``; duwu.loader.prepare_model)."""
+        for k in ("torch_dtype", "variant", "use_safetensors", "cache_dir", "local_files_only", "revision"):
+            kw.pop(k, None)
+        src = "sdxl" if pretrained_model_name_or_path is None else pretrained_model_name_or_path
+        config = dict(src) if isinstance(src, dict) else dict(cls._preset(str(src)))
+        config.update(kw.pop("config", None) or {})
+        return cls(config, **kw)
