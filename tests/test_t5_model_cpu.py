@@ -161,10 +161,14 @@ def test_load_state_dict_refusals_write_nothing():
     assert all(torch.equal(before[k], after[k]) for k in before)
 
 
-def test_local_directory_round_trip(tmp_path):
+def test_local_directory_round_trip(tmp_path, monkeypatch):
     from safetensors.torch import save_file
 
     from uwudiff_amd.text_model import T5EncoderModel
+    from uwudiff_amd.flat import FlatModule
+
+    calls, inner = [], FlatModule._from_local_dir.__func__  # every local directory goes through the one loader in flat.py
+    monkeypatch.setattr(FlatModule, "_from_local_dir", classmethod(lambda c, *a, **kw: calls.append(c) or inner(c, *a, **kw)))
 
     cfg = dict(t5_oracle.TINY, **SMALL)
     ref = t5_oracle.random_state_dict(cfg, seed=5)
@@ -173,9 +177,10 @@ def test_local_directory_round_trip(tmp_path):
     (d / "config.json").write_text(json.dumps(dict(cfg, architectures=["T5EncoderModel"], model_type="t5", is_gated_act=True)))
     save_file({k: v.clone().contiguous() for k, v in ref.items() if k != "encoder.embed_tokens.weight"}, str(d / "model.safetensors"))
     for m in (T5EncoderModel.from_pretrained(str(d), torch_dtype=torch.float16), T5EncoderModel.from_pretrained(str(tmp_path), subfolder="enc")):
-        assert m.config.d_model == 128 and m.config.num_layers == 2 and m.kind == "t5"
+        assert m.config.d_model == 128 and m.config.num_layers == 2 and m.kind == "t5" and "is_gated_act" not in m.config
         got = m.state_dict()
         assert all(torch.equal(got[k], v) for k, v in ref.items())
+    assert calls == [T5EncoderModel] * 2
 
 
 def test_same_name_same_weights_and_builtin_configs():

@@ -173,6 +173,22 @@ def test_attention_relbias_fully_masked_sequence_gives_zeros(dtype):
         torch.testing.assert_close(got.double(), ref, **_tol(dtype))
 
 
+@pytest.mark.parametrize("dtype", [torch.float32, BF], ids=["f32", "bf16"])
+def test_attention_relbias_first_key_tile_hidden(dtype):
+    """T = 77 (two 64-row query blocks), sequence 0 hides keys 0 .. 39 -- the whole first 32-key tile of the fp32 path and part of the
+    next, so the running maximum is still -inf when the first visible key arrives -- and sequence 1 sees every key.  Every row sees
+    a key and matches fp64.  Scores as in test_attention_relbias_matches_fp64: no exponent near underflow."""
+    B, T, H = 2, 77, 2
+    q, k, v, bias, _ = _attn_inputs(T, B, H, dtype)
+    mask = torch.ones(B, T, dtype=torch.long)
+    mask[0, :40] = 0
+    ref = _ref_attn(q, k, v, bias, mask)
+    for packed in (True, False):
+        got = _run_attn(q, k, v, bias, mask, packed)
+        assert bool(torch.isfinite(got).all())
+        torch.testing.assert_close(got.double(), ref, **_tol(dtype))
+
+
 def test_attention_relbias_refusals():
     """null pointers, d = 72, T = 0, T = 513, misaligned bases, strides too short or not a multiple of 8: a UwuError that names the
     entry point, and nothing is launched (the output keeps its sentinel)"""

@@ -151,10 +151,14 @@ def test_parent_module_state_dict_round_trips():
         b.load_state_dict(sd)
 
 
-def test_local_directory_round_trips(tmp_path):
+def test_local_directory_round_trips(tmp_path, monkeypatch):
     """a save_pretrained-style directory: config.json (with keys this build ignores) + model.safetensors in the prefixed layout"""
     from safetensors.torch import save_file
     from uwudiff_amd.text_model import CLIPTextModel, CLIPTextModelWithProjection
+    from uwudiff_amd.flat import FlatModule
+
+    calls, inner = [], FlatModule._from_local_dir.__func__  # every local directory goes through the one loader in flat.py
+    monkeypatch.setattr(FlatModule, "_from_local_dir", classmethod(lambda c, *a, **kw: calls.append(c) or inner(c, *a, **kw)))
 
     cfg = clip_oracle.TINY_GELU
     sd = clip_oracle.random_state_dict(cfg, seed=5, projection=True)
@@ -167,9 +171,11 @@ def test_local_directory_round_trips(tmp_path):
     for m in (CLIPTextModelWithProjection.from_pretrained(str(d)),
               CLIPTextModelWithProjection.from_pretrained(str(tmp_path / "repo"), subfolder="text_encoder_2")):
         assert m.config.hidden_act == "gelu" and m.config.eos_token_id == 999 and m.config.num_hidden_layers == 3
+        assert "architectures" not in m.config and "torch_dtype" not in m.config
         got = m.state_dict()
         assert sorted(got) == sorted("text_model." + k if not k.startswith("text_projection") else k for k in sd)
         assert all(torch.equal(got["text_model." + k if not k.startswith("text_projection") else k], v.half().float()) for k, v in sd.items())
+    assert calls == [CLIPTextModelWithProjection] * 2
     with pytest.raises(RuntimeError, match="text_projection"):  # the plain class refuses the extra tensor
         CLIPTextModel.from_pretrained(str(d))
 

@@ -149,6 +149,44 @@ def test_attention_causal_hidden_keys_never_contribute(dtype):
     torch.testing.assert_close(got[keep], ref[keep], **_tol(dtype))
 
 
+@pytest.mark.parametrize("dtype", [torch.float32, BF], ids=["f32", "bf16"])
+def test_attention_causal_fully_masked_sequence_gives_zeros(dtype):
+    """the precondition (key 0 visible) broken for sequence 1 of 2, whose key mask is all zeros and whose K and V rows are NaN: its
+    rows are exactly zero, not NaN; sequence 0 is unaffected"""
+    B, T, H = 2, 17, 2
+    g = torch.Generator().manual_seed(31)
+    q, k, v = (torch.randn(B, T, H, D_HEAD, generator=g).to(dtype) for _ in range(3))
+    mask = torch.ones(B, T, dtype=torch.long)
+    mask[1] = 0
+    ref = _ref_attn(q, k, v, mask)[:T]
+    k[1] = float("nan")
+    v[1] = float("nan")
+    for packed in (True, False):
+        got = _run_attn(q, k, v, mask, packed)
+        assert not bool(got[T:].any())  # (NaN != 0 counts as set)
+        torch.testing.assert_close(got[:T].double(), ref, **_tol(dtype))
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, BF], ids=["f32", "bf16"])
+def test_attention_causal_first_key_tile_hidden(dtype):
+    """T = 77 (two 64-row query blocks), sequence 0 hides keys 0 .. 39 -- the whole first 32-key tile of the fp32 path and part of the
+    next, so its running maximum is still -inf when the first visible key arrives -- and sequence 1 sees every key.  Rows 0 .. 39
+    of sequence 0 see nothing and are exactly zero; every other row matches fp64.  Scores as in test_attention_causal_matches_fp64:
+    a spread of a few units, no exponent near underflow whatever the maximum is carried as."""
+    B, T, H, n0 = 2, 77, 2, 40
+    g = torch.Generator().manual_seed(32)
+    q, k, v = (torch.randn(B, T, H, D_HEAD, generator=g).to(dtype) for _ in range(3))
+    q = q * 1.5
+    mask = torch.ones(B, T, dtype=torch.long)
+    mask[0, :n0] = 0
+    ref = _ref_attn(q, k, v, mask)
+    assert bool(torch.isnan(ref[:n0]).all()) and bool(torch.isfinite(ref[n0:]).all())  # the rows the reference has nothing for
+    for packed in (True, False):
+        got = _run_attn(q, k, v, mask, packed)
+        assert not bool(got[:n0].any())
+        torch.testing.assert_close(got[n0:].double(), ref[n0:], **_tol(dtype))
+
+
 def test_attention_causal_refusals():
     """null pointers, d = 72, T = 0, T = 129, a misaligned base, ld not a multiple of 8: a UwuError that names the entry point, and
     nothing is launched (the output keeps its sentinel)"""

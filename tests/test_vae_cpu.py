@@ -161,9 +161,13 @@ def test_seeded_initialisation_is_reproducible():
     assert torch.equal(a["encoder.conv_norm_out.weight"], torch.ones(64)) and not a["encoder.conv_norm_out.bias"].any()
 
 
-def test_local_directory_loads(tmp_path):
+def test_local_directory_loads(tmp_path, monkeypatch):
     from safetensors.torch import save_file
     from uwudiff_amd.vae import AutoencoderKL
+    from uwudiff_amd.flat import FlatModule
+
+    calls, inner = [], FlatModule._from_local_dir.__func__  # every local directory goes through the one loader in flat.py
+    monkeypatch.setattr(FlatModule, "_from_local_dir", classmethod(lambda c, *a, **kw: calls.append(c) or inner(c, *a, **kw)))
 
     cfg = {"_class_name": "AutoencoderKL", "_diffusers_version": "0.0", "in_channels": 3, "out_channels": 3, "latent_channels": 4,
            "block_out_channels": [32, 64], "layers_per_block": 1, "norm_num_groups": 32, "act_fn": "silu",
@@ -179,6 +183,9 @@ def test_local_directory_loads(tmp_path):
         assert m.config.scaling_factor == 0.5 and tuple(m.config.block_out_channels) == (32, 64)
         got = m.state_dict()
         assert sorted(got) == sorted(sd) and all(torch.equal(got[k], sd[k].float()) for k in sd)
+        assert "force_upcast" not in m.config and "_class_name" not in m.config
+    assert calls == [AutoencoderKL] * 2
+    assert AutoencoderKL.from_pretrained(str(d), config={"scaling_factor": 0.25}).config.scaling_factor == 0.25  # as the text models
     with pytest.raises(ValueError):
         AutoencoderKL.from_pretrained(str(tmp_path / "repo"))  # a directory without config.json is not a known name
 

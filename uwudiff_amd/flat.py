@@ -6,7 +6,9 @@ driver all address that buffer by offset, so the order of ``add`` calls is the l
 views, ``FlatModule`` the ``nn.Module`` side: named views as ``state_dict()``, a loader that checks before it writes, the shadow,
 and moves / casts that keep the master fp32.
 """
+import json
 import math
+import os
 
 import torch
 import torch.nn as nn
@@ -20,6 +22,16 @@ def pad8(c):
 
 def pad64(n):
     return (n + 63) // 64 * 64
+
+
+class _Config(dict):
+    """a model's transformers / diffusers configuration, attribute-accessible (``model.config.hidden_size``)"""
+
+    def __getattr__(self, k):
+        try:
+            return self[k]
+        except KeyError as e:
+            raise AttributeError(k) from e
 
 
 class FlatParams:
@@ -202,6 +214,30 @@ class FlatModule(nn.Module):
             return
         missing_keys.extend(prefix + k for k in res.missing_keys)
         unexpected_keys.extend(prefix + k for k in res.unexpected_keys)
+
+    @staticmethod
+    def _drop_hub_keywords(kw):
+        """`kw` of a ``from_pretrained`` without the keywords that only steer a download or a cast: nothing is ever fetched, and
+        no dtype is taken from the caller"""
+        hub = ("torch_dtype", "variant", "use_safetensors", "cache_dir", "local_files_only", "revision")
+        return {k: v for k, v in kw.items() if k not in hub}
+
+    @classmethod
+    def _from_local_dir(cls, path, subfolder, known, weights, **kw):
+        """The local-directory branch of every ``from_pretrained``.  When ``<path>[/<subfolder>]`` is a directory with
+        ``config.json``: the model built from that file's keys in `known` (the rest is not built) under a ``config=`` override,
+        holding the tensors of the safetensors file `weights`.  Anything else (a hub name, a preset) -> None."""
+        local = os.path.join(path, subfolder) if subfolder else path
+        if not (os.path.isdir(local) and os.path.exists(os.path.join(local, "config.json"))):
+            return None
+        from safetensors.torch import load_file
+
+        with open(os.path.join(local, "config.json")) as f:
+            config = {k: v for k, v in json.load(f).items() if k in known}
+        config.update(kw.pop("config", None) or {})
+        model = cls(config, init_weights=False, **kw)
+        model.load_state_dict(load_file(os.path.join(local, weights)))
+        return model
 
     # ------------------------------------------------------------------ shadow, moves
     @torch.no_grad()

@@ -17,15 +17,13 @@ runs every operator through ``libuwu_hip.so``:
   * there is no backward and no CPU path.
 """
 import hashlib
-import json
 import math
-import os
 
 import torch
 
 from . import lib as L
 from . import ops
-from .flat import FlatModule
+from .flat import FlatModule, _Config
 
 _COMMON = dict(max_position_embeddings=77, vocab_size=49408, layer_norm_eps=1e-5, eos_token_id=2, bos_token_id=49406,
                pad_token_id=1)
@@ -38,16 +36,6 @@ SDXL_TEXT_CONFIGS = {
 }
 _HEAD_DIM = 64   # the one head width uwu_attention_causal_fwd is built for
 _MAX_T = 128     # and its longest sequence
-
-
-class _Config(dict):
-    """the transformers configuration, attribute-accessible (``model.config.hidden_size``)"""
-
-    def __getattr__(self, k):
-        try:
-            return self[k]
-        except KeyError as e:
-            raise AttributeError(k) from e
 
 
 class _FinalLayerNorm:
@@ -67,7 +55,59 @@ class _FinalLayerNorm:
         return m._ln(x2, "final_layer_norm")[1].view(x.shape)
 
 
-class CLIPTextModel(FlatModule):
+class _TextEncoder(FlatModule):
+    """What the two encoders share on the host side: the constructor preamble, the checks on what ``forward`` is given, and
+    ``from_config``.  A subclass brings its parameter table, ``reset_parameters``, ``_encode`` and ``from_pretrained``."""
+
+    def _setup(self, defaults, config, compute_dtype, kw):
+        """the head of a constructor: `config` and the remaining keywords merged over `defaults` into ``self.config``, the compute
+        dtype checked and set -> (init_weights, device, seed)"""
+        init_weights = kw.pop("init_weights", True)
+        device = kw.pop("device", None)
+        seed = kw.pop("seed", None)
+        cfg = dict(defaults)
+        cfg.update({k: v for k, v in (config or {}).items() if not k.startswith("_")})
+        cfg.update(kw)
+        if compute_dtype not in ("bf16", "fp32"):
+            raise ValueError(f"compute_dtype must be 'bf16' or 'fp32', got {compute_dtype!r}")
+        self.config = _Config(cfg)
+        self.compute_dtype = compute_dtype
+        self.dtype = torch.bfloat16 if compute_dtype == "bf16" else torch.float32
+        self._names = {}  # transformers name -> (stored name, first row, rows)
+        return init_weights, device, seed
+
+    def _require_device(self, t, what):
+        if not torch.is_tensor(t) or not t.is_cuda or not self.flat.is_cuda:
+            raise L.UwuError(f"{type(self).__name__}.{what} runs on the HIP device only (no CPU fallback)")
+        if self.dtype == torch.bfloat16 and self.shadow.numel() != self.n:
+            self.refresh_shadow()
+
+    def _ids_and_mask(self, input_ids, attention_mask, max_T):
+        """-> (int64 ids [B, T], int64 key mask [B, T] or None), both contiguous on the device"""
+        self._require_device(input_ids, "forward")
+        if input_ids.dim() != 2 or not 1 <= input_ids.shape[1] <= max_T:
+            raise ValueError(f"input_ids must be [B, T <= {max_T}], got {tuple(input_ids.shape)}")
+        B, T = input_ids.shape
+        mask = None
+        if attention_mask is not None:
+            if not attention_mask.is_cuda or tuple(attention_mask.shape) != (B, T):
+                raise L.UwuError(f"attention_mask must be a device tensor [{B}, {T}], got {tuple(attention_mask.shape)}")
+            mask = attention_mask.long().contiguous()
+        return input_ids.long().contiguous(), mask
+
+    def _check_call(self, return_dict, kw):
+        if return_dict:
+            raise NotImplementedError("return_dict=True is not built: ConcatTextEncoders calls with return_dict=False")
+        extra = sorted(k for k, v in kw.items() if v is not None)
+        if extra:  # position_ids, inputs_embeds, output_attentions, ...: nothing is silently ignored
+            raise NotImplementedError(f"{type(self).__name__}.forward: {extra} not built")
+
+    @classmethod
+    def from_config(cls, config, **kw):
+        return cls(dict(config), **kw)
+
+
+class CLIPTextModel(_TextEncoder):
     """``transformers.CLIPTextModel``: ``forward(...) -> (last_hidden_state, pooled[, hidden_states])``."""
 
     kind = "clip_sd1"  # ConcatTextEncoders recomputes normed = final_layer_norm(hidden_states[layer_idx]) for this class
@@ -75,14 +115,8 @@ class CLIPTextModel(FlatModule):
 
     def __init__(self, config=None, compute_dtype="bf16", **kw):
         super().__init__()
-        init_weights = kw.pop("init_weights", True)
-        device = kw.pop("device", None)
-        seed = kw.pop("seed", None)
-        cfg = dict(SDXL_TEXT_CONFIGS["text_encoder"])
-        cfg.update({k: v for k, v in (config or {}).items() if not k.startswith("_")})
-        cfg.update(kw)
-        if compute_dtype not in ("bf16", "fp32"):
-            raise ValueError(f"compute_dtype must be 'bf16' or 'fp32', got {compute_dtype!r}")
+        init_weights, device, seed = self._setup(SDXL_TEXT_CONFIGS["text_encoder"], config, compute_dtype, kw)
+        cfg = self.config
         if cfg["hidden_act"] not in L.ACT:
             raise ValueError(f"CLIPTextModel: hidden_act {cfg['hidden_act']!r} is not built (known: {sorted(L.ACT)})")
         D, H = int(cfg["hidden_size"]), int(cfg["num_attention_heads"])
@@ -92,10 +126,6 @@ class CLIPTextModel(FlatModule):
             raise ValueError(f"CLIPTextModel: at most {_MAX_T} positions, got {cfg['max_position_embeddings']}")
         if D % 8 or cfg["intermediate_size"] % 8 or (self._with_projection and cfg["projection_dim"] % 8):
             raise ValueError("CLIPTextModel: widths must be multiples of 8")
-        self.config = _Config(cfg)
-        self.compute_dtype = compute_dtype
-        self.dtype = torch.bfloat16 if compute_dtype == "bf16" else torch.float32
-        self._names = {}  # transformers name -> (stored name, first row, rows)
 
         def add(name, shape, alias=None):
             self.P.add(name, shape)
@@ -158,12 +188,6 @@ class CLIPTextModel(FlatModule):
         self.refresh_shadow()
 
     # ------------------------------------------------------------------ forward
-    def _require_device(self, t, what):
-        if not torch.is_tensor(t) or not t.is_cuda or not self.flat.is_cuda:
-            raise L.UwuError(f"{type(self).__name__}.{what} runs on the HIP device only (no CPU fallback)")
-        if self.dtype == torch.bfloat16 and self.shadow.numel() != self.n:
-            self.refresh_shadow()
-
     def _ln(self, x, name, y=None):
         """(x + y, LayerNorm(x + y)): the residual add of the sublayer that produced y happens here"""
         return ops.add_ln_modulate_fwd(x, 1, x.shape[0], y=y, gate=self.ones if y is not None else None, shift=self.w32(name + ".bias"),
@@ -176,18 +200,10 @@ class CLIPTextModel(FlatModule):
     @torch.no_grad()
     def _encode(self, input_ids, attention_mask):
         """-> (last_hidden_state [B, T, D], pooled [B, D], hidden_states: L + 1 tensors [B, T, D], embeddings first)"""
-        self._require_device(input_ids, "forward")
         cfg = self.config
-        if input_ids.dim() != 2 or not 1 <= input_ids.shape[1] <= cfg["max_position_embeddings"]:
-            raise ValueError(f"input_ids must be [B, T <= {cfg['max_position_embeddings']}], got {tuple(input_ids.shape)}")
-        B, T = input_ids.shape
+        ids, mask = self._ids_and_mask(input_ids, attention_mask, cfg["max_position_embeddings"])
+        B, T = ids.shape
         D, H = cfg["hidden_size"], cfg["num_attention_heads"]
-        ids = input_ids.long().contiguous()
-        mask = None
-        if attention_mask is not None:
-            if not attention_mask.is_cuda or tuple(attention_mask.shape) != (B, T):
-                raise L.UwuError(f"attention_mask must be a device tensor [{B}, {T}], got {tuple(attention_mask.shape)}")
-            mask = attention_mask.long().contiguous()
         x = ops.text_embed(ids, self.w("embeddings.token_embedding.weight"), self.w("embeddings.position_embedding.weight"))
         hidden, y = [], None
         for i in range(cfg["num_hidden_layers"]):
@@ -205,14 +221,6 @@ class CLIPTextModel(FlatModule):
         pooled = ops.text_pool(ids, last, cfg["eos_token_id"])
         return last.view(B, T, D), pooled, tuple(h.view(B, T, D) for h in hidden)
 
-    @staticmethod
-    def _check_call(return_dict, kw):
-        if return_dict:
-            raise NotImplementedError("return_dict=True is not built: ConcatTextEncoders calls with return_dict=False")
-        extra = sorted(k for k, v in kw.items() if v is not None)
-        if extra:  # position_ids, output_attentions, ...: nothing is silently ignored
-            raise NotImplementedError(f"CLIPTextModel.forward: {extra} not built")
-
     def forward(self, input_ids, attention_mask=None, output_hidden_states=False, return_dict=False, **kw):
         self._check_call(return_dict, kw)
         last, pooled, hidden = self._encode(input_ids, attention_mask)
@@ -220,26 +228,14 @@ class CLIPTextModel(FlatModule):
 
     # ------------------------------------------------------------------ construction
     @classmethod
-    def from_config(cls, config, **kw):
-        return cls(dict(config), **kw)
-
-    @classmethod
     def from_pretrained(cls, pretrained_model_name_or_path=None, subfolder=None, **kw):
         """A local directory (``<path>[/<subfolder>]`` with ``config.json`` and ``model.safetensors``) is loaded.  Any other name ->
         deterministic random weights (seeded by the name and subfolder, not by the global seed) at the built-in SDXL configuration
         keyed by ``subfolder`` (``text_encoder`` when there is none): nothing is ever fetched."""
-        for k in ("torch_dtype", "variant", "use_safetensors", "cache_dir", "local_files_only", "revision"):
-            kw.pop(k, None)
+        kw = cls._drop_hub_keywords(kw)
         src = str(pretrained_model_name_or_path)
-        local = os.path.join(src, subfolder) if subfolder else src
-        if os.path.isdir(local) and os.path.exists(os.path.join(local, "config.json")):
-            from safetensors.torch import load_file
-
-            with open(os.path.join(local, "config.json")) as f:
-                config = {k: v for k, v in json.load(f).items() if k in SDXL_TEXT_CONFIGS["text_encoder"]}
-            config.update(kw.pop("config", None) or {})
-            model = cls(config, init_weights=False, **kw)
-            model.load_state_dict(load_file(os.path.join(local, "model.safetensors")))
+        model = cls._from_local_dir(src, subfolder, SDXL_TEXT_CONFIGS["text_encoder"], "model.safetensors", **kw)
+        if model is not None:
             return model
         key = subfolder if subfolder is not None else "text_encoder"
         if key not in SDXL_TEXT_CONFIGS:
@@ -296,7 +292,7 @@ def t5_offset_buckets(T, num_buckets=32, max_distance=128):
     return bucket.to(torch.int32)
 
 
-class T5EncoderModel(FlatModule):
+class T5EncoderModel(_TextEncoder):
     """``transformers.T5EncoderModel`` for the v1.1 (gated-GELU) checkpoints: ``forward(...) -> (last_hidden_state[, hidden_states])``
     (DESIGN.md section 4.25).  ``h = shared[ids]``; L blocks ``h += o(attn(RMS h))``, ``h += wo(gelu_new(wi_0 n) * wi_1 n)`` with
     ``n = RMS h``; ``final_layer_norm``.  No biases, no attention scale; the relative-position bias of block 0 is shared by all
@@ -306,14 +302,8 @@ class T5EncoderModel(FlatModule):
 
     def __init__(self, config=None, compute_dtype="bf16", **kw):
         super().__init__()
-        init_weights = kw.pop("init_weights", True)
-        device = kw.pop("device", None)
-        seed = kw.pop("seed", None)
-        cfg = dict(T5_CONFIGS["google/t5-v1_1-small"])
-        cfg.update({k: v for k, v in (config or {}).items() if not k.startswith("_")})
-        cfg.update(kw)
-        if compute_dtype not in ("bf16", "fp32"):
-            raise ValueError(f"compute_dtype must be 'bf16' or 'fp32', got {compute_dtype!r}")
+        init_weights, device, seed = self._setup(T5_CONFIGS["google/t5-v1_1-small"], config, compute_dtype, kw)
+        cfg = self.config
         built = "built: the T5 v1.1 encoder -- d_kv = 64, feed_forward_proj = 'gated-gelu', widths that are multiples of 8"
         if cfg["feed_forward_proj"] not in L.GATE:
             raise ValueError(f"T5EncoderModel: feed_forward_proj {cfg['feed_forward_proj']!r} is not built ({built})")
@@ -322,10 +312,6 @@ class T5EncoderModel(FlatModule):
         D, H, F = int(cfg["d_model"]), int(cfg["num_heads"]), int(cfg["d_ff"])
         if D % 8 or F % 8 or D < 8 or F < 8 or H < 1 or cfg["relative_attention_num_buckets"] < 4:
             raise ValueError(f"T5EncoderModel: d_model = {D}, d_ff = {F}, num_heads = {H} ({built})")
-        self.config = _Config(cfg)
-        self.compute_dtype = compute_dtype
-        self.dtype = torch.bfloat16 if compute_dtype == "bf16" else torch.float32
-        self._names = {}  # transformers name -> (stored name, first row, rows)
         self._buckets, self._bias = {}, {}  # per T: the bucket of every offset (int32, device), the gathered bias [H, 2T - 1]
         HD = H * _HEAD_DIM
 
@@ -402,8 +388,6 @@ class T5EncoderModel(FlatModule):
         self._buckets = {}
 
     # ------------------------------------------------------------------ forward
-    _require_device = CLIPTextModel._require_device
-
     def _rel_bias(self, T):
         """fp32 [H, 2T - 1] on the device; in steady state a dictionary lookup"""
         if T not in self._bias:
@@ -422,19 +406,11 @@ class T5EncoderModel(FlatModule):
     def _encode(self, input_ids, attention_mask):
         """-> (last_hidden_state [B, T, D], hidden_states: L + 1 tensors [B, T, D] -- the embeddings, the output of every block but
         the last, and last_hidden_state itself: transformers' encoder stack appends its final state after final_layer_norm)"""
-        self._require_device(input_ids, "forward")
         cfg = self.config
-        if input_ids.dim() != 2 or not 1 <= input_ids.shape[1] <= _T5_MAX_T:
-            raise ValueError(f"input_ids must be [B, T <= {_T5_MAX_T}], got {tuple(input_ids.shape)}")
-        B, T = input_ids.shape
+        ids, mask = self._ids_and_mask(input_ids, attention_mask, _T5_MAX_T)
+        B, T = ids.shape
         D, H = cfg["d_model"], cfg["num_heads"]
         HD = H * _HEAD_DIM
-        ids = input_ids.long().contiguous()
-        mask = None
-        if attention_mask is not None:
-            if not attention_mask.is_cuda or tuple(attention_mask.shape) != (B, T):
-                raise L.UwuError(f"attention_mask must be a device tensor [{B}, {T}], got {tuple(attention_mask.shape)}")
-            mask = attention_mask.long().contiguous()
         bias = self._rel_bias(T)
         x = ops.token_embed(ids, self.w("shared.weight"))
         hidden, y = [], None
@@ -452,19 +428,11 @@ class T5EncoderModel(FlatModule):
         return last.view(B, T, D), tuple(h.view(B, T, D) for h in hidden)
 
     def forward(self, input_ids, attention_mask=None, output_hidden_states=False, return_dict=False, **kw):
-        if return_dict:
-            raise NotImplementedError("return_dict=True is not built: ConcatTextEncoders calls with return_dict=False")
-        extra = sorted(k for k, v in kw.items() if v is not None)
-        if extra:  # inputs_embeds, head_mask, output_attentions, ...: nothing is silently ignored
-            raise NotImplementedError(f"T5EncoderModel.forward: {extra} not built")
+        self._check_call(return_dict, kw)
         last, hidden = self._encode(input_ids, attention_mask)
         return (last, hidden) if output_hidden_states else (last,)
 
     # ------------------------------------------------------------------ construction
-    @classmethod
-    def from_config(cls, config, **kw):
-        return cls(dict(config), **kw)
-
     @classmethod
     def from_pretrained(cls, pretrained_model_name_or_path=None, subfolder=None, **kw):
         """A local directory (``<path>[/<subfolder>]`` with ``config.json`` and ``model.safetensors``) is loaded.  Any other name ->
@@ -473,18 +441,10 @@ class T5EncoderModel(FlatModule):
         is one -- google/t5-v1_1-xxl is 19 GB of fp32, which the host never holds: the weights are drawn tensor by tensor.
         The local-directory path does not share that property yet: it builds the model where ``device=`` says (the CPU by
         default, as CLIP's does) and reads the whole safetensors file into host memory before copying it, 19 GB for xxl."""
-        for k in ("torch_dtype", "variant", "use_safetensors", "cache_dir", "local_files_only", "revision"):
-            kw.pop(k, None)
+        kw = cls._drop_hub_keywords(kw)
         src = str(pretrained_model_name_or_path)
-        local = os.path.join(src, subfolder) if subfolder else src
-        if os.path.isdir(local) and os.path.exists(os.path.join(local, "config.json")):
-            from safetensors.torch import load_file
-
-            with open(os.path.join(local, "config.json")) as f:
-                config = {k: v for k, v in json.load(f).items() if k in T5_CONFIGS["google/t5-v1_1-small"]}
-            config.update(kw.pop("config", None) or {})
-            model = cls(config, init_weights=False, **kw)
-            model.load_state_dict(load_file(os.path.join(local, "model.safetensors")))
+        model = cls._from_local_dir(src, subfolder, T5_CONFIGS["google/t5-v1_1-small"], "model.safetensors", **kw)
+        if model is not None:
             return model
         if src not in T5_CONFIGS:
             raise ValueError(f"unknown T5 encoder {src!r}: not a local directory with config.json; built-in configurations: "

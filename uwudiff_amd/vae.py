@@ -17,15 +17,13 @@ last), GroupNorm + SiLU + conv_out -- keeps diffusers' parameter names in ``stat
     padded to 8 with zero weights;
   * there is no backward, no CPU path, no tiling / slicing, no ``kl()``.
 """
-import json
 import math
-import os
 
 import torch
 
 from . import lib as L
 from . import ops
-from .flat import FlatModule, pad8
+from .flat import FlatModule, _Config, pad8
 
 SDXL_VAE_CONFIG = dict(
     in_channels=3, out_channels=3, latent_channels=4, block_out_channels=(128, 256, 512, 512), layers_per_block=2,
@@ -40,16 +38,6 @@ PRESETS = {
 }
 _EPS = 1e-6
 _ATTN_DIM = 512  # the one head width uwu_attention_d512_fwd is built for
-
-
-class _Config(dict):
-    """the diffusers configuration, attribute-accessible (``vae.config.scaling_factor``)"""
-
-    def __getattr__(self, k):
-        try:
-            return self[k]
-        except KeyError as e:
-            raise AttributeError(k) from e
 
 
 class DiagonalGaussianDistribution:
@@ -358,22 +346,13 @@ class AutoencoderKL(FlatModule):
         """Hub names of the reference's YAMLs -> the SDXL preset with seeded default initialisation (nothing is fetched, as
         UNet2DFromScratch.from_config treats hub names); a dict is a configuration; a local directory with ``config.json`` and
         ``diffusion_pytorch_model.safetensors`` is loaded."""
-        for k in ("torch_dtype", "variant", "use_safetensors", "cache_dir", "local_files_only", "revision"):
-            kw.pop(k, None)
-        src = pretrained_model_name_or_path
-        if src is None:
-            src = "sdxl-vae"
+        kw = cls._drop_hub_keywords(kw)
+        src = "sdxl-vae" if pretrained_model_name_or_path is None else pretrained_model_name_or_path
         if isinstance(src, dict):
             return cls(dict(src), **kw)
         src = str(src)
-        local = os.path.join(src, subfolder) if subfolder else src
-        if os.path.isdir(local) and os.path.exists(os.path.join(local, "config.json")):
-            from safetensors.torch import load_file
-
-            with open(os.path.join(local, "config.json")) as f:
-                config = {k: v for k, v in json.load(f).items() if not k.startswith("_")}
-            model = cls({k: v for k, v in config.items() if k in SDXL_VAE_CONFIG}, init_weights=False, **kw)  # (force_upcast etc.: not built)
-            model.load_state_dict(load_file(os.path.join(local, "diffusion_pytorch_model.safetensors")))
+        model = cls._from_local_dir(src, subfolder, SDXL_VAE_CONFIG, "diffusion_pytorch_model.safetensors", **kw)  # (force_upcast etc.: not built)
+        if model is not None:
             return model
         if src in PRESETS:
             return cls(dict(PRESETS[src]), **kw)
