@@ -1,9 +1,10 @@
 """Time prompt-to-image sampling (duwu.sampling.diffusion_sampling) at the SDXL shape on one GPU.
 
-    python tools/bench_sampling.py [--sizes 1024 256] [--samples 8] [--steps 24] [--runs 3] [--warmup 1] [--json]
+    python tools/bench_sampling.py [--family sdxl] [--sizes 1024 256] [--samples 8] [--steps 24] [--runs 3] [--warmup 1] [--json]
+    python tools/bench_sampling.py --family sd15        # the Stable Diffusion 1.x-shape stack at 512 and 256, guidance 7
 
 The models are the nodes of configs/sampling/demo_sampling.yaml (seeded SDXL-shape UNet in bf16, the YAML's text encoders, the
-SDXL VAE); the UNet's initial weights are drawn on the device.  Per size: --warmup runs, then --runs timed runs, the median of each
+SDXL VAE) or, with --family sd15, of configs/sampling/demo_sampling_sd.yaml; the UNet's initial weights are drawn on the device.  Per size: --warmup runs, then --runs timed runs, the median of each
 figure.  A run is the pipeline of diffusion_sampling with device events placed around its stages:
 
   text encoding        cfg_wrapper (both prompt lists through the text encoders, context assembly)
@@ -24,6 +25,8 @@ import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
+# per family: the sampling YAML, the default --sizes
+FAMILIES = {"sdxl": ("demo_sampling.yaml", [1024, 256]), "sd15": ("demo_sampling_sd.yaml", [512, 256])}
 GLUE = ("uwu_cfg_input", "uwu_sampler_combine", "uwu_sampler_combine_draw", "uwu_scale_copy")
 
 
@@ -117,7 +120,8 @@ def one_run(models, sched, prompts, negatives, size, samples, steps, cfg_scale=4
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--sizes", type=int, nargs="+", default=[1024, 256])
+    ap.add_argument("--family", choices=sorted(FAMILIES), default="sdxl")
+    ap.add_argument("--sizes", type=int, nargs="+", default=None, help="default: 1024 256 (sdxl), 512 256 (sd15)")
     ap.add_argument("--samples", type=int, default=8)
     ap.add_argument("--steps", type=int, default=24)
     ap.add_argument("--runs", type=int, default=3)
@@ -132,14 +136,16 @@ def main():
     from uwudiff_amd.config import load_yaml
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    cfg = load_yaml(os.path.join(root, "configs", "sampling", "demo_sampling.yaml"))
-    cfg.model_config.unet["device"] = "cuda"  # draw the 2.6 G initial weights on the device
+    yaml_name, sizes = FAMILIES[args.family]
+    cfg = load_yaml(os.path.join(root, "configs", "sampling", yaml_name))
+    cfg.model_config.unet["device"] = "cuda"  # draw the initial weights (2.6 G at the SDXL shape) on the device
     models = tuple(load_any(cfg.model_config[k]) for k in ("unet", "te", "vae"))
     sched = instantiate_any(cfg.sampling_func.train_scheduler)
     prompts, negatives = list(cfg.sampling_func.prompt), list(cfg.sampling_func.neg_prompt)
     rows = []
-    for size in args.sizes:
-        runs = [one_run(models, sched, prompts, negatives, size, args.samples, args.steps, eta=args.eta)
+    cfg_scale = 4.0 if args.family == "sdxl" else float(cfg.sampling_func.cfg_scale)
+    for size in args.sizes or sizes:
+        runs = [one_run(models, sched, prompts, negatives, size, args.samples, args.steps, cfg_scale=cfg_scale, eta=args.eta)
                 for _ in range(args.warmup + args.runs)][args.warmup:]
         row = {k: statistics.median(r[k] for r in runs) for k in runs[0]}
         row.update(size=size, samples=args.samples, steps=args.steps, eta=args.eta, runs=args.runs, warmup=args.warmup)

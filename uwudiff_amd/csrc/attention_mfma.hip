@@ -1,5 +1,5 @@
-// MFMA flash attention for gfx950 (bf16 operands, fp32 softmax/accumulate); head dim 64 (the tuned case), 72 (DiT-XL)
-// and 128; self- and cross-attention.
+// MFMA flash attention for gfx950 (bf16 operands, fp32 softmax/accumulate); head dim 64 (the tuned case), 72 (DiT-XL),
+// 128, and 40 / 80 (the Stable Diffusion 1.x UNet: 8 heads at 320 / 640 channels); self- and cross-attention.
 // Head dims other than 64 reuse the 64-wide machinery: every LDS image is NB = ceil(DH/64) blocks of [64][64] bf16 with
 // the same swizzle, columns past DH are zero-filled while staging, and the product loops run over NKS = ceil(DH/16)
 // contraction steps and NDT = ceil(DH/32) output tiles (d = 72: 5 and 3 instead of 4.5 and 2.25 -- the MFMAs are not
@@ -24,6 +24,8 @@
 //   its 32-key slice into a shared [q][key] bf16 image, then each wave computes two 16x16 blocks of
 //   dQ^T[d][q] = K^T[d][key].dS^T[key][q] over ALL keys with v_mfma_f32_16x16x32_bf16 against a resident K^T
 //   image -- no cross-wave reduction (LDS float atomics measured 5x slower than the whole rest of the kernel).
+#include <type_traits>
+
 #include "common.h"
 
 namespace {
@@ -122,6 +124,12 @@ struct HeadGeom {
   static constexpr int NB = (DH + 63) / 64;   // 64-wide LDS blocks per image
   static constexpr int NKS = (DH + 15) / 16;  // contraction steps over the head dim (k = 16 per 32x32x16 MFMA)
   static constexpr int NDT = (DH + 31) / 32;  // 32-row output tiles over the head dim
+  // Head dim 80: the 512-thread dK / dV kernel in its general form needs more than the 256 registers a lane has at two
+  // waves per SIMD (5 + 5 K / V fragments, 2 x 3 accumulator tiles, two 64-wide staging blocks).  Its lean form drops the
+  // staged O block (delta[q] comes from the dQ pass, which runs first and writes it to `delta`), applies the key bias as the
+  // addend of the exponent's FMA (the key is the lane: one scalar) instead of an accumulator pass, and keeps the two 32-row
+  // halves of a query tile as a rolled loop -- 255 registers, no scratch.  72 and 128 keep their form.
+  static constexpr bool LEAN = DH == 80;
 };
 __device__ __forceinline__ uint4 load16_or_zero(const bf16_t* p, bool ok) {
   return ok ? *reinterpret_cast<const uint4*>(p) : uint4{0u, 0u, 0u, 0u};
@@ -393,9 +401,12 @@ __global__ void __launch_bounds__(512, 2) attn_bwd_mfma(const MArgs a) {
   // staging registers: row-major Q and dO (one 16-B chunk each), transposed Q (threads 0-255) or dO (256-511)
   // delta[q] = sum_d dO[q][d] * O[q][d] is computed here from the staged dO chunk and the matching O chunk (8 lanes
   // per row, three shuffles) instead of by a separate pass over O and dO
-  uint4 qreg[NB], greg[NB], oreg[NB];
+  constexpr bool LEAN = G::LEAN;
+  constexpr int SUB_UNROLL = LEAN ? 1 : 2;
+  uint4 qreg[NB], greg[NB], oreg[LEAN ? 1 : NB];
   TStage treg[NB];
-  float lreg = 0.f;
+  float lreg = 0.f, dreg = 0.f;
+  (void)dreg;
   const float inv_scale = 1.f / a.scale;
   auto load_tile = [&](int q0) {
     const int row = tid >> 3, ch = tid & 7;
@@ -405,12 +416,14 @@ __global__ void __launch_bounds__(512, 2) attn_bwd_mfma(const MArgs a) {
       qreg[blk] = load16_or_zero(qb + (int64_t)(q0 + row) * a.ldq + col, col < DH);
       if constexpr (ROPE) qreg[blk] = rope8(qreg[blk], a.rope + (int64_t)(q0 + row) * a.ldt + hd * DH + col);
       greg[blk] = load16_or_zero(gb + (int64_t)(q0 + row) * a.ldo + col, col < DH);
-      oreg[blk] = load16_or_zero(ob + (int64_t)(q0 + row) * a.ldo + col, col < DH);
+      if constexpr (!LEAN) oreg[blk] = load16_or_zero(ob + (int64_t)(q0 + row) * a.ldo + col, col < DH);
       if (tid < 256) treg[blk].load(qb + 64 * blk, a.ldq, q0, tid, 0x7fffffff, DH - 64 * blk,
                                     ROPE ? a.rope + hd * DH + 64 * blk : nullptr, a.ldt);
       else treg[blk].load(gb + 64 * blk, a.ldo, q0, tid - 256, 0x7fffffff, DH - 64 * blk);
     }
     if (tid < 64) lreg = -lseb[q0 + tid] * inv_scale;  // row constant of S, in units of the raw dot product
+    if constexpr (LEAN)
+      if (tid < 64) dreg = -a.delta[((int64_t)b * a.H + hd) * a.T + q0 + tid];
   };
   auto store_tile = [&](int stage) {
     char* st = smem + stage * BWD_STAGE;
@@ -422,13 +435,19 @@ __global__ void __launch_bounds__(512, 2) attn_bwd_mfma(const MArgs a) {
       *reinterpret_cast<uint4*>(st + (NB + blk) * 8192 + swz(row, ch)) = greg[blk];
       if (tid < 256) treg[blk].store(st + (2 * NB + blk) * 8192, tid);
       else treg[blk].store(st + (3 * NB + blk) * 8192, tid - 256);
-      const bf16x8 gv = *reinterpret_cast<const bf16x8*>(&greg[blk]), ov = *reinterpret_cast<const bf16x8*>(&oreg[blk]);
+      if constexpr (!LEAN) {
+        const bf16x8 gv = *reinterpret_cast<const bf16x8*>(&greg[blk]), ov = *reinterpret_cast<const bf16x8*>(&oreg[blk]);
 #pragma unroll
-      for (int j = 0; j < 8; ++j) ds += (float)gv[j] * (float)ov[j];
+        for (int j = 0; j < 8; ++j) ds += (float)gv[j] * (float)ov[j];
+      }
     }
     float* ls = reinterpret_cast<float*>(smem + BWD_OFF_LSE) + stage * 64;
     float* dl = reinterpret_cast<float*>(smem + BWD_OFF_LSE + 512) + stage * 64;
     if (tid < 64) ls[tid] = lreg;
+    if constexpr (LEAN) {
+      if (tid < 64) dl[tid] = dreg;
+      return;
+    }
     ds += __shfl_xor(ds, 1, 64);
     ds += __shfl_xor(ds, 2, 64);
     ds += __shfl_xor(ds, 4, 64);
@@ -452,7 +471,7 @@ __global__ void __launch_bounds__(512, 2) attn_bwd_mfma(const MArgs a) {
     if (t + 1 < nt) load_tile((t + 1) * 64);
     // ---- phase 1: this wave's 32 keys against the 64 staged query rows
     if (active) {
-#pragma unroll
+#pragma unroll SUB_UNROLL
       for (int sub = 0; sub < 2; ++sub) {
         // the row constants -lse / scale and -delta are the INITIAL accumulators of S and dP (one LDS read each, no
         // subtraction after the chains): p = exp2(c * S'), dS = p * dP'
@@ -463,7 +482,7 @@ __global__ void __launch_bounds__(512, 2) attn_bwd_mfma(const MArgs a) {
           const f32x4 d4 = load4(dl + 32 * sub + 8 * g4 + 4 * h);
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
-            S[4 * g4 + e] = BIAS ? l4[e] + kbr : l4[e];
+            S[4 * g4 + e] = (BIAS && !LEAN) ? l4[e] + kbr : l4[e];
             dP[4 * g4 + e] = d4[e];
           }
         }
@@ -477,7 +496,7 @@ __global__ void __launch_bounds__(512, 2) attn_bwd_mfma(const MArgs a) {
         // P and dS in place (rows = q in registers, cols = key on lanes)
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-          float p = fexp2(S[i] * c);
+          float p = (BIAS && LEAN) ? fexp2(fmaf(S[i], c, kbr * c)) : fexp2(S[i] * c);
           if constexpr (!DQ) p = kvalid ? p : 0.f;  // (self-attention with T <= 256: every key of an active wave exists)
           S[i] = p;
           dP[i] *= p;
@@ -639,6 +658,8 @@ __global__ void __launch_bounds__(256, 2) attn_bwd_dq_mfma(const MArgs a) {
       for (int j = 0; j < 8; ++j) dl += (float)gv[j] * (float)ov[j];
     }
     dl += __shfl_xor(dl, 32, 64);  // the two lane halves hold the two halves of the row
+    if constexpr (G::LEAN)  // the dK / dV kernel of this head dim reads delta instead of forming it (launched after this one)
+      if (h == 0) a.delta[((int64_t)b * a.H + hd) * a.T + q0 + r] = dl;
     lq = a.lse[((int64_t)b * a.H + hd) * a.T + q0 + r] * 1.4426950408889634f;
   }
   f32x16 dq[NDT];
@@ -759,10 +780,10 @@ __global__ void __launch_bounds__(256, 2) attn_bwd_dq_mfma(const MArgs a) {
 }  // namespace
 
 // ------------------------------------------------------------------------------------------- host side
-// head dim 64 / 72 / 128, whole 64-row query tiles; any number of keys (ragged key tiles are masked: cross-attention,
+// head dim 40 / 64 / 72 / 80 / 128, whole 64-row query tiles; any number of keys (ragged key tiles are masked: cross-attention,
 // Tk = 77)
 bool uwu_attn_mfma_fwd_ok(int Tq, int Tk, int d, int ldq, int ldk, int ldv, int ldo) {
-  return (d == 64 || d == 72 || d == 128) && Tk >= 1 && Tq % 64 == 0 && ldq % 8 == 0 && ldk % 8 == 0 && ldv % 8 == 0 &&
+  return (d == 40 || d == 64 || d == 72 || d == 80 || d == 128) && Tk >= 1 && Tq % 64 == 0 && ldq % 8 == 0 && ldk % 8 == 0 && ldv % 8 == 0 &&
          ldo % 8 == 0;
 }
 bool uwu_attn_mfma_bwd_ok(int Tq, int Tk, int d, int ldq, int ldk, int ldv, int ldo) {
@@ -809,9 +830,11 @@ int launch_bwd(const MArgs& a, hipStream_t st) {
                   allow_lds(attn_bwd_dq_mfma<false, DH>, lds_dq, done[4], what)))
     return UWU_ELAUNCH;
   const dim3 gkv(a.B * a.H * ((a.Tk + 255) / 256)), gq(a.B * a.H * ((a.T + 127) / 128));
+  constexpr bool dq_first = HeadGeom<DH>::LEAN;  // the lean dK / dV kernel reads the delta the dQ pass writes
   if (a.kbias) {  // biased scores: always the two-kernel form
+    if (dq_first) hipLaunchKernelGGL((attn_bwd_dq_mfma<true, DH>), gq, dim3(256), lds_dq, st, a);
     hipLaunchKernelGGL((attn_bwd_mfma<false, true, DH>), gkv, dim3(512), lds_kv, st, a);
-    hipLaunchKernelGGL((attn_bwd_dq_mfma<true, DH>), gq, dim3(256), lds_dq, st, a);
+    if (!dq_first) hipLaunchKernelGGL((attn_bwd_dq_mfma<true, DH>), gq, dim3(256), lds_dq, st, a);
     return UWU_OK;
   }
   if constexpr (DH == 64) {
@@ -821,9 +844,25 @@ int launch_bwd(const MArgs& a, hipStream_t st) {
     }
   }
   // dK / dV per block of 256 keys, dQ per tile of 128 queries
+  if (dq_first) hipLaunchKernelGGL((attn_bwd_dq_mfma<false, DH>), gq, dim3(256), lds_dq, st, a);
   hipLaunchKernelGGL((attn_bwd_mfma<false, false, DH>), gkv, dim3(512), lds_kv, st, a);
-  hipLaunchKernelGGL((attn_bwd_dq_mfma<false, DH>), gq, dim3(256), lds_dq, st, a);
+  if (!dq_first) hipLaunchKernelGGL((attn_bwd_dq_mfma<false, DH>), gq, dim3(256), lds_dq, st, a);
   return UWU_OK;
+}
+
+// the instantiated head dims (uwu_attn_mfma_fwd_ok admits exactly these)
+template <typename F>
+int by_head_dim(int d, F&& launch) {
+  switch (d) {
+    case 40: return launch(std::integral_constant<int, 40>{});
+    case 64: return launch(std::integral_constant<int, 64>{});
+    case 72: return launch(std::integral_constant<int, 72>{});
+    case 80: return launch(std::integral_constant<int, 80>{});
+    case 128: return launch(std::integral_constant<int, 128>{});
+    default:
+      uwu_set_error("attention(mfma): head dim %d not instantiated (40, 64, 72, 80, 128)", d);
+      return UWU_EINVAL;
+  }
 }
 
 }  // namespace
@@ -890,7 +929,7 @@ int uwu_attn_mfma_fwd(const void* q, const void* k, const void* v, void* o, floa
   a.q = (const bf16_t*)q; a.k = (const bf16_t*)k; a.v = (const bf16_t*)v; a.out = (bf16_t*)o; a.lse = lse;
   a.kbias = kbias;
   a.B = B; a.T = T; a.Tk = Tk; a.H = H; a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo; a.scale = scale;
-  const int rc = d == 64 ? launch_fwd<64>(a, st) : d == 72 ? launch_fwd<72>(a, st) : launch_fwd<128>(a, st);
+  const int rc = by_head_dim(d, [&](auto dh) { return launch_fwd<decltype(dh)::value>(a, st); });
   if (rc != UWU_OK) return rc;
   UWU_LAUNCH_CHECK("attention_fwd(mfma)");
   return UWU_OK;
@@ -907,7 +946,7 @@ int uwu_attn_mfma_bwd(const void* q, const void* k, const void* v, const void* o
   UWU_CHECK_ARG((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)o | (uintptr_t)dO | (uintptr_t)dq |
                   (uintptr_t)dk | (uintptr_t)dv) & 15) == 0,
                 "attention_bwd(mfma): tensors must be 16-byte aligned");
-  (void)delta;  // the row sums of dO * O are formed inside the kernels
+  // the row sums of dO * O are formed inside the kernels (head dim 80 passes them from the dQ pass to dK / dV through `delta`)
   if (!kbias && uwu_attn_p256_ok(T, Tk, d, ldq, ldk, ldv, ldo))
     return uwu_attn_p256_bwd(q, k, v, o, dO, lse, dq, dk, dv, B, H, d, ldq, ldk, ldv, ldo, scale, st);
   MArgs a{};
@@ -916,7 +955,7 @@ int uwu_attn_mfma_bwd(const void* q, const void* k, const void* v, const void* o
   a.dq = (bf16_t*)dq; a.dk = (bf16_t*)dk; a.dv = (bf16_t*)dv;
   a.kbias = kbias;
   a.B = B; a.T = T; a.Tk = Tk; a.H = H; a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo; a.scale = scale;
-  const int rc = d == 64 ? launch_bwd<64>(a, st) : d == 72 ? launch_bwd<72>(a, st) : launch_bwd<128>(a, st);
+  const int rc = by_head_dim(d, [&](auto dh) { return launch_bwd<decltype(dh)::value>(a, st); });
   if (rc != UWU_OK) return rc;
   UWU_LAUNCH_CHECK("attention_bwd(mfma)");
   return UWU_OK;

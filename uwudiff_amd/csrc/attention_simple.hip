@@ -1,7 +1,7 @@
 // Generic-dtype scaled-dot-product attention (forward + backward), VALU only.
 //
 // This is the exact-fp32 parity path (and the fallback for shapes the MFMA kernel in attention_mfma.hip does
-// not cover: query counts that are not multiples of 64, head dim 32, fp32 operands).  Two lanes share one
+// not cover: query counts that are not multiples of 64, head dims 32 and 160, fp32 operands).  Two lanes share one
 // row (each owns half of the head dimension, partial dot products are exchanged with one DPP/shuffle), K/V (or
 // Q/dO) tiles of 32 rows are staged in LDS as fp32 and read as wave-broadcasts.
 // Semantics: F.scaled_dot_product_attention(q,k,v, dropout_p=0, is_causal=False) -- reference
@@ -288,10 +288,13 @@ template <typename T>
 int by_head(const AttnArgs& a, bool bwd, hipStream_t st) {
   switch (a.d) {
     case 32: return bwd ? run_bwd<T, 32>(a, st) : run_fwd<T, 32>(a, st);
+    case 40: return bwd ? run_bwd<T, 40>(a, st) : run_fwd<T, 40>(a, st);
     case 64: return bwd ? run_bwd<T, 64>(a, st) : run_fwd<T, 64>(a, st);
     case 72: return bwd ? run_bwd<T, 72>(a, st) : run_fwd<T, 72>(a, st);
+    case 80: return bwd ? run_bwd<T, 80>(a, st) : run_fwd<T, 80>(a, st);
+    case 160: return bwd ? run_bwd<T, 160>(a, st) : run_fwd<T, 160>(a, st);
     default:
-      uwu_set_error("attention: head dim %d not instantiated in the generic kernels (32, 64, 72)", a.d);
+      uwu_set_error("attention: head dim %d not instantiated in the generic kernels (32, 40, 64, 72, 80, 160)", a.d);
       return UWU_EINVAL;
   }
 }

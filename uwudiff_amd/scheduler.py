@@ -20,6 +20,8 @@ _SD15 = dict(_SDXL)  # same beta schedule family; SD1.x uses identical betas
 KNOWN_SCHEDULERS = {
     "stabilityai/stable-diffusion-xl-base-1.0": _SDXL,
     "runwayml/stable-diffusion-v1-5": _SD15,
+    "CompVis/stable-diffusion-v1-4": _SD15,
+    "bdsqlsz/stable-diffusion-v1-5": _SD15,
     "sdxl": _SDXL,
 }
 

@@ -36,6 +36,17 @@ SDXL_UNET_CONFIG = dict(
     addition_embed_type="text_time", addition_time_embed_dim=256, projection_class_embeddings_input_dim=2816,
     norm_num_groups=32, sample_size=128,
 )
+# Stable Diffusion 1.x (CompVis/stable-diffusion-v1-4, .../stable-diffusion-v1-5): four levels, 8 heads everywhere (head widths
+# 40 / 80 / 160 -- diffusers' `attention_head_dim` is the NUMBER of heads), CLIP ViT-L/14 context, no pooled-text conditioning,
+# 1x1-convolution proj_in / proj_out.  859,520,964 parameters.
+SD15_UNET_CONFIG = dict(
+    in_channels=4, out_channels=4, block_out_channels=(320, 640, 1280, 1280), layers_per_block=2,
+    down_block_types=("CrossAttnDownBlock2D", "CrossAttnDownBlock2D", "CrossAttnDownBlock2D", "DownBlock2D"),
+    up_block_types=("UpBlock2D", "CrossAttnUpBlock2D", "CrossAttnUpBlock2D", "CrossAttnUpBlock2D"),
+    transformer_layers_per_block=1, attention_head_dim=8, cross_attention_dim=768, addition_embed_type=None,
+    use_linear_projection=False, norm_num_groups=32, sample_size=64,
+)
+SD15_NAMES = ("sd15", "CompVis/stable-diffusion-v1-4", "runwayml/stable-diffusion-v1-5", "bdsqlsz/stable-diffusion-v1-5")
 # BASELINE.json configs[0]: "tiny-UNet 32x32x3 pixel diffusion" (build-defined plumbing model)
 TINY_UNET_CONFIG = dict(
     in_channels=3, out_channels=3, block_out_channels=(64, 128), layers_per_block=1,
@@ -619,6 +630,14 @@ class UNet2DConditionModel(FlatModule):
         # q rotated, k only in self-attention; zero_init: HDUNet2DConditionModel's exact-zero residual-branch outputs (:562-580)
         cfg.setdefault("rope", False)
         cfg.setdefault("zero_init", False)
+        # False (SD 1.x): proj_in / proj_out of every Transformer2D are 1x1 convolutions -- on token-major activations the very
+        # Linear launched otherwise; only the public layout of their weights differs ([C, C, 1, 1]: _public_view, against
+        # which load_state_dict checks shapes)
+        cfg.setdefault("use_linear_projection", True)
+        nlev = len(cfg["block_out_channels"])
+        for key in ("attention_head_dim", "transformer_layers_per_block"):  # one int = the same at every level
+            if isinstance(cfg[key], int):
+                cfg[key] = (cfg[key],) * nlev
         self.cfg_dict = cfg
         c = type("cfg", (), cfg)()
         c.compute_dtype = compute_dtype
@@ -796,9 +815,13 @@ class UNet2DConditionModel(FlatModule):
         base, _, leaf = name.rpartition(".")
         if base in self._conv_meta:
             return self._conv_public(v, self._conv_meta[base], 9, leaf == "bias")
-        if name.endswith("conv_shortcut.weight"):
+        if name.endswith("conv_shortcut.weight") or self._proj_is_conv(name):
             return v[:, :, None, None]
         return v
+
+    def _proj_is_conv(self, name):
+        return not self.cfg_dict["use_linear_projection"] and name.endswith((".proj_in.weight", ".proj_out.weight")) \
+            and name[:name.rindex(".proj_")] in self._t2d_heads
 
     def grad_tensor(self, name):
         """Gradient of a parameter in diffusers layout (for parity checks)."""
@@ -1056,7 +1079,7 @@ class UNet2DConditionModel(FlatModule):
     def _preset(name):
         presets = {"sdxl": SDXL_UNET_CONFIG, "stabilityai/stable-diffusion-xl-base-1.0": SDXL_UNET_CONFIG,
                    "tiny-unet": TINY_UNET_CONFIG, "sdxl-rope": dict(SDXL_UNET_CONFIG, rope=True, zero_init=True),
-                   "sdxl-hd": dict(SDXL_UNET_CONFIG, zero_init=True)}
+                   "sdxl-hd": dict(SDXL_UNET_CONFIG, zero_init=True), **{n: SD15_UNET_CONFIG for n in SD15_NAMES}}
         if name not in presets:
             raise ValueError(f"unknown UNet config {name!r}; known: {sorted(presets)}")
         return presets[name]

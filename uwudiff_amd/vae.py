@@ -31,10 +31,16 @@ SDXL_VAE_CONFIG = dict(
     act_fn="silu", mid_block_add_attention=True, scaling_factor=0.13025, sample_size=1024,
 )
 # hub names of the reference's YAMLs -> preset (random init: nothing is ever fetched)
+# Stable Diffusion 1.x: the same architecture, its own latent scale and training resolution
+SD_VAE_CONFIG = dict(SDXL_VAE_CONFIG, scaling_factor=0.18215, sample_size=512)
 PRESETS = {
     "madebyollin/sdxl-vae-fp16-fix": SDXL_VAE_CONFIG,
     "stabilityai/stable-diffusion-xl-base-1.0": SDXL_VAE_CONFIG,
     "sdxl-vae": SDXL_VAE_CONFIG,
+    "CompVis/stable-diffusion-v1-4": SD_VAE_CONFIG,
+    "runwayml/stable-diffusion-v1-5": SD_VAE_CONFIG,
+    "bdsqlsz/stable-diffusion-v1-5": SD_VAE_CONFIG,
+    "sd-vae": SD_VAE_CONFIG,
 }
 _EPS = 1e-6
 _ATTN_DIM = 512  # the one head width uwu_attention_d512_fwd is built for
