@@ -12,7 +12,7 @@ import torch.optim.lr_scheduler as lr_sch
 from duwu.loader import load_any
 from duwu.utils import instantiate_any
 from uwudiff_amd.engine import GradualWarmupScheduler
-from uwudiff_amd.optim import FusedAdamW
+from uwudiff_amd.optim import FusedAdamW, FusedAdamWFP16, flat_segments
 
 
 class BaseTrainer(nn.Module):
@@ -42,8 +42,14 @@ class BaseTrainer(nn.Module):
         opt_cls = self.optimizer
         if opt_cls is optim.AdamW and all(p.is_cuda for p in params):
             opt_cls = FusedAdamW  # same update rule, one HIP launch over the flat buffer
-        optimizer = opt_cls(params, lr=self.lr, **self.opt_config)
+        opt_config = dict(self.opt_config)
         lyc = getattr(self, "lycoris_model", None)
+        if isinstance(opt_cls, type) and issubclass(opt_cls, FusedAdamWFP16) and "segments" not in opt_config:
+            # optimizers.py:64-76 keeps one decay phase per parameter tensor: the tensors of the flat buffer that trains
+            owner = lyc if lyc is not None else getattr(self, "unet", None)
+            if owner is not None and (hasattr(owner, "offsets") or hasattr(owner, "P")):
+                opt_config["segments"] = flat_segments(owner)
+        optimizer = opt_cls(params, lr=self.lr, **opt_config)
         if lyc is not None:  # every step changes the adapters: the UNet merges them again before its next forward
             optimizer.register_step_post_hook(lambda opt, args, kwargs: lyc.mark_dirty())
         sched = self.lr_sch(optimizer, **self.lr_sch_config) if self.lr_sch is not None else None

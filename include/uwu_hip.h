@@ -199,6 +199,31 @@ int uwu_adamw_step(float* p, float* g, float* m, float* v, void* p_bf16, int64_t
                    float beta1, float beta2, float eps, float weight_decay, int step, float pre_scale,
                    const float* clip, int zero_grad, void* stream);
 
+/* lion_pytorch.Lion (the commented alternative of demo_training.yaml:48, demo_training_latent.yaml:31 and
+ * demo_training_lycoris.yaml:49; Chen et al. 2023, Algorithm 2) on flat buffers, in the package's order:
+ *   p *= 1 - lr*wd ; c = beta1*m + (1-beta1)*g ; p -= lr*sign(c), sign(0) = 0 ; m = beta2*m + (1-beta2)*g
+ * m is fp32.  g = g * pre_scale * clip[1] (clip may be NULL); p_bf16 (may be NULL) is refreshed; zero_grad leaves g
+ * zeroed.  p, g, m 16-byte aligned, p_bf16 8-byte aligned.  The hyper-parameters are doubles: 1 - beta and 1 - lr*wd are
+ * formed in double on the host as python does (1 - 0.999f is off by 1.3e-5 relative). */
+int uwu_lion_step(float* p, float* g, float* m, void* p_bf16, int64_t n, double lr, double beta1, double beta2,
+                  double weight_decay, float pre_scale, const float* clip, int zero_grad, void* stream);
+
+/* duwu.trainer.optimizers.AdamWFP16 (optimizers.py:96-120 as called from :78-92): AdamW with both moments in fp16
+ * (m16, v16: IEEE half), no first-moment bias correction, no weight decay (see uwu_param_decay):
+ *   m = float(m16)*beta1 + (1-beta1)*g ; v = float(v16)*beta2 + (1-beta2)*g*g
+ *   p -= lr*sqrt(1-beta2^step) * m / (sqrt(v) + eps)       (the unrounded fp32 m and v)
+ *   m16 = half(m) ; v16 = half(v)    round to nearest even, subnormals kept, overflow -> inf; nothing is clamped
+ * g, p_bf16, zero_grad, step as in uwu_adamw_step.  p, g 16-byte aligned; m16, v16, p_bf16 8-byte aligned, m16 and v16
+ * at the same offset within 16 bytes (chunk offsets are multiples of 4 elements). */
+int uwu_adamw_fp16_step(float* p, float* g, void* m16, void* v16, void* p_bf16, int64_t n, double lr, double beta1,
+                        double beta2, double eps, int step, float pre_scale, const float* clip, int zero_grad,
+                        void* stream);
+
+/* p *= factor over n elements, p_bf16 (may be NULL) refreshed: AdamWFP16's accumulated weight decay of one tensor,
+ * `p.add_(p, alpha=-decay_this_iteration)` (optimizers.py:117-118) with factor = 1 - decay_this_iteration.  Any
+ * element alignment. */
+int uwu_param_decay(float* p, void* p_bf16, int64_t n, double factor, void* stream);
+
 int uwu_cast_f32_to_bf16(const float* src, void* dst, int64_t n, void* stream);
 int uwu_cast_bf16_to_f32(const void* src, float* dst, int64_t n, void* stream);
 

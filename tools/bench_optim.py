@@ -1,0 +1,92 @@
+"""The three flat-buffer update kernels (AdamW, Lion, AdamWFP16: uwudiff_amd/csrc/optimizer.hip) alone, with the bf16 shadow and
+``zero_grad`` on, at DiT-S/2's parameter count and at the SDXL-shape UNet's 2.57 G: ms per launch, bytes moved per parameter
+and GB/s, and the optimizer-state bytes of the SDXL-shape UNet under each optimizer.  One JSON line.  DESIGN.md section 4.28.
+
+    python tools/bench_optim.py [--sizes 32966464,2570000000] [--reps 5] [--warmup 3]
+
+Bytes per parameter are derived from the update rule (reads + writes of p, g and the state, + 2 for the shadow, + 4 for the zeroed
+gradient); the times are device events around a window of launches, the three kernels alternating inside every repetition."""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+DIT_S2, SDXL_UNET = 32_966_464, 2_570_000_000
+# bytes per parameter: (read + written by the update rule, optimizer state held)
+KERNELS = {"adamw": (16 + 12, 8), "lion": (12 + 8, 4), "adamw_fp16": (12 + 8, 4)}
+EXTRA = 2 + 4  # bf16 shadow written, consumed gradient zeroed
+
+
+def bench_size(n, reps, warmup):
+    import torch
+
+    from uwudiff_amd import lib as L
+
+    dev = torch.device("cuda", 0)
+    f32 = lambda: torch.empty(n, device=dev, dtype=torch.float32)  # noqa: E731
+    p, g = f32().normal_(), f32().normal_().mul_(1e-3)
+    shadow = torch.empty(n, device=dev, dtype=torch.bfloat16)
+    st = {"adamw": (f32().zero_(), f32().zero_()), "lion": (f32().zero_(),),
+          "adamw_fp16": (torch.zeros(n, device=dev, dtype=torch.float16), torch.zeros(n, device=dev, dtype=torch.float16))}
+    s = L.stream()
+    launch = {
+        "adamw": lambda k: L.call("uwu_adamw_step", L.ptr(p), L.ptr(g), L.ptr(st["adamw"][0]), L.ptr(st["adamw"][1]),
+                                  L.ptr(shadow), n, 1e-6, 0.9, 0.999, 1e-8, 0.01, k, 1.0, None, 1, s),
+        "lion": lambda k: L.call("uwu_lion_step", L.ptr(p), L.ptr(g), L.ptr(st["lion"][0]), L.ptr(shadow), n, 1e-6, 0.9, 0.99,
+                                 0.01, 1.0, None, 1, s),
+        "adamw_fp16": lambda k: L.call("uwu_adamw_fp16_step", L.ptr(p), L.ptr(g), L.ptr(st["adamw_fp16"][0]),
+                                       L.ptr(st["adamw_fp16"][1]), L.ptr(shadow), n, 1e-6, 0.9, 0.999, 1e-8, k, 1.0, None, 1, s),
+    }
+    iters = max(4, min(200, int(2e11 / (34 * n))))  # a window of roughly 0.2 GB/param-byte: tens of ms at either size
+    for k in range(1, warmup + 1):
+        for fn in launch.values():
+            fn(k)
+    torch.cuda.synchronize()
+    ms = {name: [] for name in launch}
+    for _ in range(reps):
+        for name, fn in launch.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for k in range(iters):
+                fn(warmup + 1 + k)
+            e1.record()
+            e1.synchronize()
+            ms[name].append(e0.elapsed_time(e1) / iters)
+    out = {}
+    for name, times in ms.items():
+        times = sorted(times)
+        med = times[len(times) // 2]
+        bpp = KERNELS[name][0] + EXTRA
+        out[name] = {"ms": round(med, 4), "ms_min": round(times[0], 4), "ms_max": round(times[-1], 4),
+                     "bytes_per_param": bpp, "GBps": round(bpp * n / med / 1e6, 1),
+                     "GBps_min": round(bpp * n / times[-1] / 1e6, 1), "GBps_max": round(bpp * n / times[0] / 1e6, 1)}
+    return {"n": n, "launches_per_window": iters, "reps": reps, "kernels": out}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--sizes", default=f"{DIT_S2},{SDXL_UNET}")
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=3)
+    a = ap.parse_args()
+    import torch
+
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_optim.py measures on the GPU; there is no CPU path")
+    res = {"sizes": [bench_size(int(n), a.reps, a.warmup) for n in a.sizes.split(",")],
+           "state_bytes_sdxl_unet": {name: state * SDXL_UNET for name, (_, state) in KERNELS.items()},
+           "weights_bytes_sdxl_unet": 4 * SDXL_UNET}
+    for r in res["sizes"]:
+        for name, k in r["kernels"].items():
+            print(f"n = {r['n']:>13,}  {name:<11} {k['ms']:9.4f} ms ({k['ms_min']:.4f} .. {k['ms_max']:.4f})  "
+                  f"{k['bytes_per_param']} B/param  {k['GBps']:8.1f} GB/s ({k['GBps_min']:.1f} .. {k['GBps_max']:.1f})")
+    for name, b in res["state_bytes_sdxl_unet"].items():
+        print(f"SDXL-shape UNet optimizer state under {name:<11}: {b / 1e9:6.2f} GB (weights {4 * SDXL_UNET / 1e9:.2f} GB)")
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()

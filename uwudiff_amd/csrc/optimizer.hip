@@ -1,6 +1,8 @@
-// Flat-buffer optimizer kernels: global grad norm (+clip coefficient), fused AdamW with bf16 shadow
-// refresh, dtype casts.  HBM-bound: AdamW moves 28 B/param (+2 B/param for the bf16 shadow).
-// Reference: src/duwu/trainer/trainer.py:52-74 (torch.optim.AdamW + Lightning gradient_clip_val).
+// Flat-buffer optimizer kernels: global grad norm (+clip coefficient), fused AdamW / Lion / AdamWFP16 with bf16 shadow
+// refresh, dtype casts.  HBM-bound: AdamW moves 28 B/param, Lion and AdamWFP16 20 B/param (+2 B/param for the bf16
+// shadow, +4 B/param for the zeroed gradient).
+// Reference: src/duwu/trainer/trainer.py:52-74 (torch.optim.AdamW + Lightning gradient_clip_val),
+// src/duwu/trainer/optimizers.py (AdamWFP16), lion_pytorch.Lion (configs/demo_training*.yaml, commented alternative).
 #include "common.h"
 
 // stage 1: per-block partial sums (deterministic order), stage 2: one block folds the partials
@@ -91,6 +93,153 @@ __global__ void __launch_bounds__(256) adamw_kernel(float* __restrict__ p, float
   }
 }
 
+// lion_pytorch.Lion (Chen et al. 2023, Algorithm 2), in the package's order:
+//   p *= 1 - lr*wd ; c = b1*m + (1-b1) g ; p -= lr*sign(c) (sign(0) = 0) ; m = b2*m + (1-b2) g
+__device__ __forceinline__ void lion_elem(float& p, float g, float& m, float decay, float lr, float b1, float omb1,
+                                          float b2, float omb2) {
+  const float c = m * b1 + g * omb1;
+  const float s = c > 0.f ? 1.f : (c < 0.f ? -1.f : 0.f);
+  p = p * decay - lr * s;
+  m = m * b2 + g * omb2;
+}
+
+__global__ void __launch_bounds__(256) lion_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
+                                                   bf16_t* __restrict__ pbf, int64_t n, float lr, float b1, float omb1,
+                                                   float b2, float omb2, float decay, float pre_scale,
+                                                   const float* __restrict__ clip, int zero_grad) {
+  const float gscale = pre_scale * (clip ? clip[1] : 1.f);
+  const int64_t n4 = n >> 2;
+  const int64_t stride = (int64_t)gridDim.x * 256;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
+    f32x4 pv = load4(p + 4 * i), gv = load4(g + 4 * i), mv = load4(m + 4 * i);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      float pp = pv[j], mm = mv[j];
+      lion_elem(pp, gv[j] * gscale, mm, decay, lr, b1, omb1, b2, omb2);
+      pv[j] = pp;
+      mv[j] = mm;
+    }
+    store4(p + 4 * i, pv);
+    store4(m + 4 * i, mv);
+    if (pbf) store4(pbf + 4 * i, pv);
+    if (zero_grad) store4(g + 4 * i, f32x4{0.f, 0.f, 0.f, 0.f});
+  }
+  if (blockIdx.x == 0) {
+    for (int64_t i = (n4 << 2) + threadIdx.x; i < n; i += 256) {
+      float pp = p[i], mm = m[i];
+      lion_elem(pp, g[i] * gscale, mm, decay, lr, b1, omb1, b2, omb2);
+      p[i] = pp;
+      m[i] = mm;
+      if (pbf) pbf[i] = (bf16_t)pp;
+      if (zero_grad) g[i] = 0.f;
+    }
+  }
+}
+
+// AdamWFP16 (optimizers.py:96-120 as called from :78-92): both moments live in fp16, the update is computed in fp32 from
+// the widened moments and uses the UNROUNDED new moments; no first-moment bias correction, no weight decay here.
+//   m = float(m16)*b1 + (1-b1) g ; v = float(v16)*b2 + (1-b2) g^2 ; p -= lr*sqrt(1-b2^step) * m / (sqrt(v) + eps)
+//   m16 = half(m) ; v16 = half(v)   -- v_cvt_f16_f32: round to nearest even, subnormals kept, overflow -> inf (what
+//   torch.Tensor.half() does).  Nothing is clamped: a v that underflowed to 0 or sits at inf is the reference's behaviour.
+typedef _Float16 f16_t;
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+
+__device__ __forceinline__ void adamw16_elem(float& p, float g, f16_t& m16, f16_t& v16, float b1, float omb1, float b2,
+                                             float omb2, float eps, float step_size) {
+  const float m = (float)m16 * b1 + g * omb1;
+  const float v = (float)v16 * b2 + omb2 * g * g;
+  p = p - step_size * (m / (sqrtf(v) + eps));
+  m16 = (f16_t)m;
+  v16 = (f16_t)v;
+}
+
+// 8 elements per lane: the fp16 state goes through 16-byte accesses like the fp32 buffers (two of them per 8 elements).
+// m16 / v16 are only 8-byte aligned (chunk offsets are multiples of 4 elements): `head` (0 or up to 4) leading elements
+// are peeled off as scalars so that the body's fp16 accesses start on a 16-byte boundary; p and g stay 16-byte aligned.
+__global__ void __launch_bounds__(256) adamw16_kernel(float* __restrict__ p, float* __restrict__ g,
+                                                      f16_t* __restrict__ m16, f16_t* __restrict__ v16,
+                                                      bf16_t* __restrict__ pbf, int64_t n, int head, float b1, float omb1,
+                                                      float b2, float omb2, float eps, float step_size,
+                                                      float pre_scale, const float* __restrict__ clip, int zero_grad) {
+  const float gscale = pre_scale * (clip ? clip[1] : 1.f);
+  const int64_t n8 = (n - head) >> 3;
+  const int64_t stride = (int64_t)gridDim.x * 256;
+  const bool pbf16B = (((uintptr_t)(pbf + head)) & 15) == 0;  // wave-uniform
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n8; i += stride) {
+    const int64_t e = head + 8 * i;
+    f32x8 pv = load8(p + e), gv = load8(g + e);
+    f16x8 mv = *reinterpret_cast<const f16x8*>(m16 + e), vv = *reinterpret_cast<const f16x8*>(v16 + e);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      float pp = pv[j];
+      f16_t mm = mv[j], vn = vv[j];
+      adamw16_elem(pp, gv[j] * gscale, mm, vn, b1, omb1, b2, omb2, eps, step_size);
+      pv[j] = pp;
+      mv[j] = mm;
+      vv[j] = vn;
+    }
+    store8(p + e, pv);
+    *reinterpret_cast<f16x8*>(m16 + e) = mv;
+    *reinterpret_cast<f16x8*>(v16 + e) = vv;
+    if (pbf) {
+      if (pbf16B) {
+        store8(pbf + e, pv);
+      } else {
+        store4(pbf + e, f32x4{pv[0], pv[1], pv[2], pv[3]});
+        store4(pbf + e + 4, f32x4{pv[4], pv[5], pv[6], pv[7]});
+      }
+    }
+    if (zero_grad) store8(g + e, f32x8{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f});
+  }
+  if (blockIdx.x == 0) {  // the peeled head [0, head) and the tail [head + 8*n8, n): fewer than 12 elements
+    const int64_t tail0 = head + (n8 << 3);
+    const int64_t extra = head + (n - tail0);
+    for (int64_t k = threadIdx.x; k < extra; k += 256) {
+      const int64_t i = k < head ? k : tail0 + (k - head);
+      float pp = p[i];
+      f16_t mm = m16[i], vn = v16[i];
+      adamw16_elem(pp, g[i] * gscale, mm, vn, b1, omb1, b2, omb2, eps, step_size);
+      p[i] = pp;
+      m16[i] = mm;
+      v16[i] = vn;
+      if (pbf) pbf[i] = (bf16_t)pp;
+      if (zero_grad) g[i] = 0.f;
+    }
+  }
+}
+
+// p *= factor over one tensor's range (AdamWFP16's accumulated weight decay, optimizers.py:117-118), shadow refreshed
+__global__ void __launch_bounds__(256) param_decay_kernel(float* __restrict__ p, bf16_t* __restrict__ pbf, int64_t n,
+                                                          int head, float factor) {
+  const int64_t n4 = (n - head) >> 2;
+  const int64_t stride = (int64_t)gridDim.x * 256;
+  const bool pbf8B = (((uintptr_t)(pbf + head)) & 7) == 0;  // wave-uniform
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
+    const int64_t e = head + 4 * i;
+    f32x4 pv = load4(p + e);
+    pv *= factor;
+    store4(p + e, pv);
+    if (pbf) {
+      if (pbf8B) {
+        store4(pbf + e, pv);
+      } else {  // a tensor may start on any even byte of the shadow
+#pragma unroll
+        for (int j = 0; j < 4; ++j) pbf[e + j] = (bf16_t)pv[j];
+      }
+    }
+  }
+  if (blockIdx.x == 0) {
+    const int64_t tail0 = head + (n4 << 2);
+    const int64_t extra = head + (n - tail0);
+    for (int64_t k = threadIdx.x; k < extra; k += 256) {
+      const int64_t i = k < head ? k : tail0 + (k - head);
+      const float pp = p[i] * factor;
+      p[i] = pp;
+      if (pbf) pbf[i] = (bf16_t)pp;
+    }
+  }
+}
+
 template <typename TS, typename TD>
 __global__ void __launch_bounds__(256) cast_kernel(const TS* __restrict__ s, TD* __restrict__ d, int64_t n) {
   const int64_t n4 = n >> 2;
@@ -131,6 +280,52 @@ extern "C" int uwu_adamw_step(float* p, float* g, float* m, float* v, void* p_bf
                      (bf16_t*)p_bf16, n, lr, beta1, beta2, eps, weight_decay, step_size, inv_bc2_sqrt, pre_scale,
                      clip, zero_grad);
   UWU_LAUNCH_CHECK("adamw_step");
+  return UWU_OK;
+}
+
+extern "C" int uwu_lion_step(float* p, float* g, float* m, void* p_bf16, int64_t n, double lr, double beta1, double beta2,
+                             double weight_decay, float pre_scale, const float* clip, int zero_grad, void* stream) {
+  UWU_CHECK_ARG(p && g && m && n > 0, "lion_step: bad args");
+  UWU_CHECK_ARG((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m) & 15) == 0, "lion_step: buffers must be 16-byte aligned");
+  UWU_CHECK_ARG(p_bf16 == nullptr || ((uintptr_t)p_bf16 & 7) == 0, "lion_step: bf16 shadow must be 8-byte aligned");
+  // 1 - beta and 1 - lr*wd in double on the host, as lion_pytorch does with python floats
+  hipLaunchKernelGGL(lion_kernel, dim3(ew_grid(n / 4, 256)), dim3(256), 0, (hipStream_t)stream, p, g, m, (bf16_t*)p_bf16,
+                     n, (float)lr, (float)beta1, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2),
+                     (float)(1.0 - lr * weight_decay), pre_scale, clip, zero_grad);
+  UWU_LAUNCH_CHECK("lion_step");
+  return UWU_OK;
+}
+
+extern "C" int uwu_adamw_fp16_step(float* p, float* g, void* m16, void* v16, void* p_bf16, int64_t n, double lr,
+                                   double beta1, double beta2, double eps, int step, float pre_scale, const float* clip,
+                                   int zero_grad, void* stream) {
+  UWU_CHECK_ARG(p && g && m16 && v16 && n > 0 && step >= 1, "adamw_fp16_step: bad args");
+  UWU_CHECK_ARG((((uintptr_t)p | (uintptr_t)g) & 15) == 0, "adamw_fp16_step: p and g must be 16-byte aligned");
+  UWU_CHECK_ARG((((uintptr_t)m16 | (uintptr_t)v16) & 7) == 0, "adamw_fp16_step: fp16 moments must be 8-byte aligned");
+  UWU_CHECK_ARG((((uintptr_t)m16 ^ (uintptr_t)v16) & 15) == 0,
+                "adamw_fp16_step: both fp16 moments must sit at the same offset within 16 bytes");
+  UWU_CHECK_ARG(p_bf16 == nullptr || ((uintptr_t)p_bf16 & 7) == 0, "adamw_fp16_step: bf16 shadow must be 8-byte aligned");
+  // the peel moves the fp16 state by 8 bytes and p / g by 16: everything the body touches 16 bytes at a time stays aligned
+  int head = ((uintptr_t)m16 & 15) ? 4 : 0;
+  if (head > n) head = (int)n;
+  // optimizers.py:111-115: value = -lr * (1 - beta2**step) ** 0.5 as a python float
+  const double step_size = lr * sqrt(1.0 - pow(beta2, (double)step));
+  hipLaunchKernelGGL(adamw16_kernel, dim3(ew_grid(n / 8, 256)), dim3(256), 0, (hipStream_t)stream, p, g, (f16_t*)m16,
+                     (f16_t*)v16, (bf16_t*)p_bf16, n, head, (float)beta1, (float)(1.0 - beta1), (float)beta2,
+                     (float)(1.0 - beta2), (float)eps, (float)step_size, pre_scale, clip, zero_grad);
+  UWU_LAUNCH_CHECK("adamw_fp16_step");
+  return UWU_OK;
+}
+
+extern "C" int uwu_param_decay(float* p, void* p_bf16, int64_t n, double factor, void* stream) {
+  UWU_CHECK_ARG(p && n > 0, "param_decay: bad args");
+  UWU_CHECK_ARG(((uintptr_t)p & 3) == 0 && ((uintptr_t)p_bf16 & 1) == 0, "param_decay: misaligned buffers");
+  // a tensor of the flat buffer may start anywhere: peel up to 3 elements to reach a 16-byte boundary of p
+  int head = (int)(((16 - ((uintptr_t)p & 15)) & 15) >> 2);
+  if (head > n) head = (int)n;
+  hipLaunchKernelGGL(param_decay_kernel, dim3(ew_grid(n / 4, 256)), dim3(256), 0, (hipStream_t)stream, p,
+                     (bf16_t*)p_bf16, n, head, (float)factor);
+  UWU_LAUNCH_CHECK("param_decay");
   return UWU_OK;
 }
 

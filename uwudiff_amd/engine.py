@@ -16,7 +16,7 @@ import torch
 import torch.distributed as dist
 
 from .gradsync import FlatGradSync
-from .optim import FusedAdamW
+from .optim import FlatFusedOptimizer
 
 
 def seed_everything(seed: int):
@@ -227,10 +227,10 @@ class Fitter:
         cfg = module.configure_optimizers()
         opt = cfg["optimizer"] if isinstance(cfg, dict) else cfg
         sched = cfg["lr_scheduler"]["scheduler"] if isinstance(cfg, dict) and "lr_scheduler" in cfg else None
-        fused = isinstance(opt, FusedAdamW)
+        fused = isinstance(opt, FlatFusedOptimizer)
         sync = FlatGradSync(self.world_size)
         lyc = getattr(module, "lycoris_model", None)  # adapter training: the UNet is frozen, the adapter buffer trains
-        if fused and lyc is None:  # the early (inside-backward) reduction is consumed by FusedAdamW's per-chunk waits only; a foreign
+        if fused and lyc is None:  # the early (inside-backward) reduction is consumed by the fused optimizers' per-chunk waits only; a foreign
             sync.attach(module.unet)  # optimizer takes the plain whole-buffer exchange below
         elif hasattr(module.unet, "set_grad_ready_hook"):
             module.unet.set_grad_ready_hook(None)
@@ -276,7 +276,7 @@ class Fitter:
                     done, finished_epoch = True, False
                     break
                 module.global_step = self.global_step
-                if not grads_zeroed:  # (a fused step leaves the gradients zeroed: FusedAdamW.step(zero_grad=True))
+                if not grads_zeroed:  # (a fused step leaves the gradients zeroed: FlatFusedOptimizer.step(zero_grad=True))
                     for p in params:
                         if p.grad is not None:
                             p.grad.zero_()
@@ -286,7 +286,7 @@ class Fitter:
                     one = torch.ones_like(loss)  # (kept: autograd's own ones_like(loss) is a fill launch per step)
                 loss.backward(one)
                 clip = None
-                if isinstance(opt, FusedAdamW):
+                if isinstance(opt, FlatFusedOptimizer):
                     chunks = sync.all_reduce(params[0].grad)
                     if self.gradient_clip_val:
                         sync.wait_all()

@@ -5,7 +5,7 @@ PyTorch is only the owner of device memory and streams -- every entry takes raw 
 """
 import ctypes
 import os
-from ctypes import c_char_p, c_float, c_int, c_int32, c_int64, c_size_t, c_void_p
+from ctypes import c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_size_t, c_void_p
 
 import torch
 
@@ -75,6 +75,10 @@ _SIGS = {
     "uwu_grad_sqnorm_clip": (c_int, [P, c_int64, c_float, c_float, P, P, P]),
     "uwu_adamw_step": (c_int, [P, P, P, P, P, c_int64, c_float, c_float, c_float, c_float, c_float, c_int, c_float,
                                P, c_int, P]),
+    "uwu_lion_step": (c_int, [P, P, P, P, c_int64, c_double, c_double, c_double, c_double, c_float, P, c_int, P]),
+    "uwu_adamw_fp16_step": (c_int, [P, P, P, P, P, c_int64, c_double, c_double, c_double, c_double, c_int, c_float, P,
+                                    c_int, P]),
+    "uwu_param_decay": (c_int, [P, P, c_int64, c_double, P]),
     "uwu_cast_f32_to_bf16": (c_int, [P, P, c_int64, P]),
     "uwu_cast_bf16_to_f32": (c_int, [P, P, c_int64, P]),
     "uwu_adapter_merge": (c_int, [P, P, P, P, c_int, c_int64, P, P, P]),

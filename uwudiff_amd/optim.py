@@ -1,29 +1,36 @@
-"""Fused flat-buffer AdamW + global-norm clip on the HIP kernels (csrc/optimizer.hip).
+"""Fused flat-buffer optimizers + global-norm clip on the HIP kernels (csrc/optimizer.hip).
 
-Mirrors ``torch.optim.AdamW`` single-tensor semantics (the reference instantiates ``torch.optim.AdamW`` from YAML,
-reference src/duwu/trainer/trainer.py:52-74, configs/demo_training_latent.yaml:30-39) and Lightning's
-``gradient_clip_val`` (global L2 norm, demo_training.yaml:12).  One launch per flat parameter buffer; the bf16
-shadow of the parameters (MFMA operands) is refreshed by the same kernel.
+``FusedAdamW`` mirrors ``torch.optim.AdamW`` single-tensor semantics (the reference instantiates ``torch.optim.AdamW`` from
+YAML, reference src/duwu/trainer/trainer.py:52-74, configs/demo_training_latent.yaml:30-39), ``FusedLion`` is
+``lion_pytorch.Lion`` (the commented alternative of the reference's training YAMLs) and ``FusedAdamWFP16`` the reference's own
+``duwu.trainer.optimizers.AdamWFP16`` (src/duwu/trainer/optimizers.py).  ``FlatFusedOptimizer`` is what they share and what
+the trainer's fused path asks for: Lightning's ``gradient_clip_val`` (global L2 norm, demo_training.yaml:12) as a device
+coefficient, one launch per flat parameter buffer (or per reduced chunk of it), the consumed gradient zeroed and the bf16
+shadow of the parameters (MFMA operands) refreshed by the same kernel.
 """
 import math
 
 import torch
+import torch.distributed as dist
 
 from . import lib as L
 
 
-def _zeros_like(t):
+def _zeros_like(t, dtype=None):
     """torch.zeros_like for the flat buffers; on the HIP device the fill is the library's (hipMemsetAsync on the current stream)."""
     if not (t.is_cuda and t.is_contiguous()):
-        return torch.zeros_like(t)
-    z = torch.empty_like(t)
+        return torch.zeros_like(t, dtype=dtype)
+    z = torch.empty_like(t, dtype=dtype)
     L.call("uwu_memset_zero", L.ptr(z), z.numel() * z.element_size(), L.stream())
     return z
 
 
-class FusedAdamW(torch.optim.Optimizer):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
-        defaults = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay)
+class FlatFusedOptimizer(torch.optim.Optimizer):
+    """Base of the optimizers that update a flat fp32 parameter buffer with one HIP kernel.  A subclass gives the state
+    (``_init_state``) and the launch over one sub-range (``_launch``); ``_finish`` runs once per parameter after the
+    launches of all chunks."""
+
+    def __init__(self, params, defaults):
         super().__init__(params, defaults)
         self._norm_ws = {}
 
@@ -47,37 +54,172 @@ class FusedAdamW(torch.optim.Optimizer):
                L.ptr(out), L.stream())
         return out
 
+    def _init_state(self, p, st):
+        raise NotImplementedError
+
+    def _launch(self, group, st, p_ptr, g_ptr, shadow_ptr, off, ln, pre_scale, clip_ptr, zero_grad):
+        raise NotImplementedError
+
+    def _finish(self, group, p, st, shadow):
+        pass
+
     @torch.no_grad()
     def step(self, closure=None, clip=None, pre_scale=1.0, chunks=None, before_chunk=None, zero_grad=False):
-        """One AdamW update.  ``chunks`` = [(offset, length), ...] splits the launch over sub-ranges of the flat
+        """One update.  ``chunks`` = [(offset, length), ...] splits the launch over sub-ranges of the flat
         buffer (16-byte aligned offsets); ``before_chunk(i)`` is called first (waits for chunk i's all-reduce).
         ``zero_grad``: the kernel leaves the consumed gradient zeroed (the flat gradient buffer is accumulated into by the
         next backward: no separate fill launch; ``p.grad`` stays allocated -- the ``zero_grad(set_to_none=False)`` state)."""
         loss = closure() if closure is not None else None
         for group in self.param_groups:
-            b1, b2 = group["betas"]
             for p in group["params"]:
                 if p.grad is None:
                     continue
+                p_ptr, g_ptr = L.ptr(p.data), L.ptr(p.grad)  # (a CPU parameter is refused here: there is no CPU path)
                 st = self.state[p]
                 if not st:
-                    st["step"] = 0
-                    st["exp_avg"] = _zeros_like(p.data)
-                    st["exp_avg_sq"] = _zeros_like(p.data)
-                st["step"] += 1
+                    self._init_state(p, st)
+                if "step" in st:
+                    st["step"] += 1
                 shadow = getattr(p, "_uwu_bf16_shadow", None)
                 if shadow is not None and shadow.numel() != p.numel():
                     shadow = None
-                flat = [p.data.view(-1), p.grad.view(-1), st["exp_avg"].view(-1), st["exp_avg_sq"].view(-1)]
+                clip_ptr = L.ptr(clip) if clip is not None else None
                 for i, (off, ln) in enumerate(chunks or [(0, p.numel())]):
                     if before_chunk is not None:
                         before_chunk(i)
-                    ptrs = [t.data_ptr() + 4 * off for t in flat]
                     sp = shadow.data_ptr() + 2 * off if shadow is not None else None
-                    L.call("uwu_adamw_step", ptrs[0], ptrs[1], ptrs[2], ptrs[3], sp, ln, float(group["lr"]), b1, b2,
-                           group["eps"], group["weight_decay"], st["step"], float(pre_scale),
-                           L.ptr(clip) if clip is not None else None, int(bool(zero_grad)), L.stream())
+                    self._launch(group, st, p_ptr + 4 * off, g_ptr + 4 * off, sp, off, ln, float(pre_scale), clip_ptr,
+                                 int(bool(zero_grad)))
+                self._finish(group, p, st, shadow)
         return loss
+
+
+class FusedAdamW(FlatFusedOptimizer):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
+        defaults = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay)
+        super().__init__(params, defaults)
+
+    def _init_state(self, p, st):
+        st["step"] = 0
+        st["exp_avg"] = _zeros_like(p.data)
+        st["exp_avg_sq"] = _zeros_like(p.data)
+
+    def _launch(self, group, st, p_ptr, g_ptr, shadow_ptr, off, ln, pre_scale, clip_ptr, zero_grad):
+        b1, b2 = group["betas"]
+        L.call("uwu_adamw_step", p_ptr, g_ptr, st["exp_avg"].data_ptr() + 4 * off, st["exp_avg_sq"].data_ptr() + 4 * off,
+               shadow_ptr, ln, float(group["lr"]), b1, b2, group["eps"], group["weight_decay"], st["step"], pre_scale,
+               clip_ptr, zero_grad, L.stream())
+
+
+class FusedLion(FlatFusedOptimizer):
+    """``lion_pytorch.Lion`` (Chen et al. 2023) on a flat buffer: one fp32 moment, the update is ``lr * sign(...)``.
+    ``use_triton`` is accepted for the package's signature and ignored (the kernel is HIP either way)."""
+
+    def __init__(self, params, lr=1e-4, betas=(0.9, 0.99), weight_decay=0.0, use_triton=False,
+                 decoupled_weight_decay=False):
+        if not lr > 0.0:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if not all(0.0 <= b <= 1.0 for b in betas):
+            raise ValueError(f"Invalid beta parameters: {betas}")
+        if decoupled_weight_decay:
+            raise NotImplementedError("FusedLion: decoupled_weight_decay is not implemented")
+        super().__init__(params, dict(lr=lr, betas=tuple(betas), weight_decay=weight_decay))
+
+    def _init_state(self, p, st):
+        st["exp_avg"] = _zeros_like(p.data)
+
+    def _launch(self, group, st, p_ptr, g_ptr, shadow_ptr, off, ln, pre_scale, clip_ptr, zero_grad):
+        b1, b2 = group["betas"]
+        L.call("uwu_lion_step", p_ptr, g_ptr, st["exp_avg"].data_ptr() + 4 * off, shadow_ptr, ln, float(group["lr"]),
+               b1, b2, group["weight_decay"], pre_scale, clip_ptr, zero_grad, L.stream())
+
+
+def draw_decay_phases(n, threshold):
+    """AdamWFP16's starting points of the accumulated weight decay (reference optimizers.py:64-66): one
+    ``float(torch.rand([]) * threshold)`` per tensor, in order, from torch's global CPU generator.  The reference draws them
+    per rank; here rank 0's draws are broadcast when a process group is initialised, so that data-parallel replicas decay
+    on the same steps.  Host only: needs no GPU."""
+    phases = [float(torch.rand([]) * threshold) for _ in range(n)]
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        box = [phases]
+        dist.broadcast_object_list(box, src=0)
+        phases = [float(x) for x in box[0]]
+    return phases
+
+
+def flat_segments(module):
+    """[(offset, length), ...] of the tensors a flat-buffer module (``FlatModule``, ``LycorisNetwork``) keeps in ``flat``"""
+    layout = module.offsets if hasattr(module, "offsets") else module.P.registry
+    return [(off, math.prod(shape)) for off, shape in layout.values()]
+
+
+class FusedAdamWFP16(FlatFusedOptimizer):
+    """The reference's ``duwu.trainer.optimizers.AdamWFP16`` on a flat buffer: both moments in fp16, no first-moment bias
+    correction, weight decay accumulated per tensor and applied when it crosses ``decay_threshold``.
+
+    ``segments`` = [(offset, length), ...]: the tensors of the flat buffer, each with a decay phase of its own (the reference
+    keeps one per parameter tensor); without it the whole buffer is one segment.  ``accumulated_decay`` is a list of python
+    floats (a tensor in optimizer state would be cast to the parameter's dtype and device by ``load_state_dict``)."""
+
+    decay_threshold = 1e-2
+
+    def __init__(self, params, *, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, differentiable=False,
+                 segments=None):
+        if not 0.0 <= eps:
+            raise ValueError(f"Invalid epsilon value: {eps}")
+        if not 0.0 <= betas[0] < 1.0:
+            raise ValueError(f"Invalid beta parameter at index 0: {betas[0]}")
+        if not 0.0 <= betas[1] < 1.0:
+            raise ValueError(f"Invalid beta parameter at index 1: {betas[1]}")
+        if not 0.0 <= weight_decay:
+            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+        if differentiable:
+            raise NotImplementedError("FusedAdamWFP16: differentiable=True is not implemented")
+        super().__init__(params, dict(betas=tuple(betas), eps=eps, weight_decay=weight_decay, lr=lr,
+                                      differentiable=differentiable))
+        self.segments = [(int(o), int(n)) for o, n in segments] if segments is not None else None
+        if self.segments is not None and sum(len(g["params"]) for g in self.param_groups) != 1:
+            raise ValueError("segments describe one flat parameter buffer")
+        self.register_load_state_dict_post_hook(FusedAdamWFP16._moments_to_fp16)
+
+    def _moments_to_fp16(self):
+        """torch's ``load_state_dict`` casts floating-point state to the parameter's dtype: the restored fp16 moments arrive as
+        fp32 holding fp16 values, so the way back is lossless"""
+        for st in self.state.values():
+            for k in ("exp_avg", "exp_avg_sq"):
+                if k in st and st[k].dtype != torch.float16:
+                    st[k] = st[k].to(torch.float16)
+
+    def _segments_of(self, p):
+        segs = self.segments if self.segments is not None else [(0, p.numel())]
+        if any(o < 0 or n <= 0 or o + n > p.numel() for o, n in segs):
+            raise ValueError("segments reach outside the parameter buffer")
+        return segs
+
+    def _init_state(self, p, st):
+        st["step"] = 0
+        st["exp_avg"] = _zeros_like(p.data, dtype=torch.float16)
+        st["exp_avg_sq"] = _zeros_like(p.data, dtype=torch.float16)
+        st["accumulated_decay"] = draw_decay_phases(len(self._segments_of(p)), self.decay_threshold)
+
+    def _launch(self, group, st, p_ptr, g_ptr, shadow_ptr, off, ln, pre_scale, clip_ptr, zero_grad):
+        b1, b2 = group["betas"]
+        L.call("uwu_adamw_fp16_step", p_ptr, g_ptr, st["exp_avg"].data_ptr() + 2 * off,
+               st["exp_avg_sq"].data_ptr() + 2 * off, shadow_ptr, ln, float(group["lr"]), b1, b2, group["eps"], st["step"],
+               pre_scale, clip_ptr, zero_grad, L.stream())
+
+    def _finish(self, group, p, st, shadow):
+        # optimizers.py:71-76 per tensor; the decay launches follow the step launches of all chunks on the same stream
+        acc = st["accumulated_decay"]
+        segs = self._segments_of(p)
+        if len(acc) != len(segs):
+            raise ValueError(f"accumulated_decay has {len(acc)} entries, the buffer has {len(segs)} segments")
+        for i, (off, ln) in enumerate(segs):
+            acc[i] += group["weight_decay"] * float(group["lr"])
+            if acc[i] > self.decay_threshold:
+                sp = shadow.data_ptr() + 2 * off if shadow is not None else None
+                L.call("uwu_param_decay", p.data_ptr() + 4 * off, sp, ln, 1.0 - acc[i], L.stream())
+                acc[i] -= acc[i]
 
 
 def cosine_lr(base_lr, step, T_max, eta_min):
