@@ -490,6 +490,40 @@ int uwu_text_pool(const int64_t* ids, const void* h, void* pooled, int B, int T,
  * inside the kernel); fp32: exact-fp32 VALU kernel. */
 int uwu_attention_relbias_fwd(const void* q, const void* k, const void* v, const float* rel_bias, const int64_t* key_mask, void* o,
                               int B, int T, int H, int d, int ldq, int ldk, int ldv, int ldo, float scale, int dtype, void* stream);
+/* Bidirectional self-attention without a bias, forward only, no lse (the CLIP image tower, transformers CLIPAttention with no
+ * mask):  o = softmax(scale * Q K^T + M) V.  key_mask: int64 [B, T] or NULL (the ViT passes NULL); key j is visible iff key_mask ==
+ * NULL or key_mask[b, j] != 0.  A hidden key never contributes, whatever its K / V rows hold (NaN included).  Precondition: every
+ * sequence has at least one visible key; a sequence without one gives rows of zeros, not NaN.  Addressing, alignment and refusals
+ * as uwu_attention_relbias_fwd (packed [B*T, 3*H*64] projections are read in place: strides in elements, multiples of 8 (bf16) /
+ * 4 (fp32), 16-byte aligned bases).  d == 64, 1 <= T <= 1024, B * H <= 65535; anything else is refused -- d == 80 (ViT-H/14,
+ * apple/DFN5B-CLIP-ViT-H-14-378) is not built.  bf16: the MFMA kernel of uwu_attention_relbias_fwd compiled a second time without its
+ * bias row (one template, two instantiations: 64-query blocks, 64-key chunks, online softmax, T padded to the tile inside the
+ * kernel; without the bias row nothing in it depends on T, hence the higher cap); fp32: the same exact-fp32 VALU kernel with the bias read switched off. */
+int uwu_attention_bidir_fwd(const void* q, const void* k, const void* v, const int64_t* key_mask, void* o, int B, int T, int H, int d,
+                            int ldq, int ldk, int ldv, int ldo, float scale, int dtype, void* stream);
+/* The A operand of a ViT's patch-embedding GEMM.  images: [B, 3, S, S] contiguous, fp32 (in_u8 == 0) or uint8 (in_u8 != 0); out:
+ * [B * (S/p)^2, ld] in `dtype`, row b (S/p)^2 + py (S/p) + px holding patch (py, px) of image b in the column order (c, i, j) =
+ * c p p + i p + j, so that patch_embedding.weight viewed as [D, 3 p p] is the B operand unchanged; columns 3 p p .. ld - 1 are
+ * written as zeros (ld pads the row to what uwu_gemm takes: 3 * 14 * 14 = 588 is no multiple of 8).  normalize != 0 fuses CLIP's
+ * preprocessing of a [0, 255] image:  v = clamp(x, 0, 255) (NaN -> 0),  out = (v / 255 - mean[c]) / std[c]  in fp32, each step
+ * rounded once; mean and std are HOST pointers to three floats each (std > 0), read before the call returns.  normalize == 0
+ * copies x as it is (pixel_values that were normalised elsewhere; mean / std may be NULL; fp32 input only).  S % p == 0. */
+int uwu_clip_patches(const void* images, int in_u8, void* out, int B, int S, int p, int ld, int normalize, const float* mean,
+                     const float* std, int dtype, void* stream);
+/* CLIPVisionEmbeddings after the patch GEMM:  out[b, 0, :] = class_embedding + pos_table[0],  out[b, 1 + i, :] = patch_out[b Np +
+ * i, :] + pos_table[1 + i]  with Np = T - 1 (the patch convolution has no bias in CLIP).  patch_out [B * Np, D], class_embedding
+ * [D], pos_table [T, D], out [B * T, D], all contiguous in `dtype`; the sum is taken in fp32 and rounded once; D a multiple of 8,
+ * 16-byte aligned. */
+int uwu_vit_embed(const void* patch_out, const void* class_embedding, const void* pos_table, void* out, int B, int T, int D, int dtype,
+                  void* stream);
+/* CLIP score of B (image, text) pairs, accumulated on the device:  scores[b] = 100 cos(image_embeds[b], text_embeds[b])  (fp32
+ * dot product and norms; a zero embedding gives NaN, as the division it stands for does),  acc[0] += sum_b scores[b],  acc[1] += B.
+ * image_embeds, text_embeds [B, P] contiguous in `dtype`; scores fp32 [B]; acc: two doubles on the device, zeroed by the caller
+ * before the first batch.  The sum runs in ONE workgroup in an order fixed by B, in double, and only one thread touches acc: no
+ * floating-point atomics, the same batches in the same order give the same bits.  No host synchronisation: the caller reads acc
+ * when it wants the mean. */
+int uwu_clip_score_accum(const void* image_embeds, const void* text_embeds, float* scores, double* acc, int B, int P, int dtype,
+                         void* stream);
 /* T5LayerNorm with the previous sublayer's residual add fused in:  x_out = x_in + y (y may be NULL: x_out is then not written and
  * may be NULL),  n_out = x_out * rsqrt(mean(x_out^2) + eps) * weight -- no mean subtraction, no bias.  x_in, y, x_out, n_out [M, D]
  * contiguous in `dtype`, weight fp32 [D]; D a multiple of 8, 16-byte aligned; statistics in fp32, taken of x_out as stored.

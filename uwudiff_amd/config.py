@@ -20,6 +20,11 @@ ALIASES = {
     "transformers.CLIPTextModel": "uwudiff_amd.conditioning.SyntheticCLIPTextModel",  # kind "clip_sd1": normed ctx = LN(layer_idx)
     "transformers.CLIPTextModelWithProjection": "uwudiff_amd.conditioning.SyntheticTextModel",
     "transformers.T5EncoderModel": "uwudiff_amd.text_model.T5EncoderModel",  # native: never the hub
+    "transformers.CLIPVisionModelWithProjection": "uwudiff_amd.vision_model.CLIPVisionModelWithProjection",  # native
+    "torchmetrics.multimodal.CLIPScore": "uwudiff_amd.metrics.CLIPScore",
+    "torchvision.transforms.Compose": "uwudiff_amd.transforms.Compose",  # PIL-based stand-ins: torchvision is not installable offline
+    "torchvision.transforms.Resize": "uwudiff_amd.transforms.Resize",
+    "torchvision.transforms.ToTensor": "uwudiff_amd.transforms.ToTensor",
     "lion_pytorch.Lion": "uwudiff_amd.optim.FusedLion",  # the commented alternative of the reference's training YAMLs
     "lightning.pytorch.callbacks.ModelCheckpoint": "uwudiff_amd.engine.ModelCheckpoint",
     "lightning.pytorch.callbacks.LearningRateMonitor": "uwudiff_amd.engine.LearningRateMonitor",

@@ -1,16 +1,18 @@
-// Self-attention of the two text encoders at head width 64 (uwudiff_amd/text_model.py; DESIGN.md sections 4.23 and 4.25),
-// forward only: the encoders are frozen.  Two entry points, one bf16 MFMA kernel each and one exact-fp32 kernel between them.
+// Self-attention of the frozen encoders at head width 64 (uwudiff_amd/text_model.py, uwudiff_amd/vision_model.py; DESIGN.md
+// sections 4.23, 4.25 and 4.29), forward only.  Three entry points, two bf16 MFMA kernels (one of them in two instantiations) and
+// one exact-fp32 kernel between them.
 //
 //   uwu_attention_causal_fwd      o = softmax(scale Q K^T + causal mask + M) V, T <= 128 (the CLIP text transformer)
 //   uwu_attention_relbias_fwd     o = softmax(scale Q K^T + rel_bias[h, j - i + T - 1] + M) V, T <= 512 (the T5 encoder)
+//   uwu_attention_bidir_fwd       o = softmax(scale Q K^T + M) V, T <= 1024 (the CLIP image tower: T = 50, 197, 257, 577)
 //
-// M hides the keys key_mask marks as padding.  PRECONDITION of both: key 0 of every sequence is visible (causal), at least one
-// key of every sequence is visible (relative bias).  A row that sees no key at all comes out as zeros, never NaN.  Where the
+// M hides the keys key_mask marks as padding.  PRECONDITION: key 0 of every sequence is visible (causal), at least one
+// key of every sequence is visible (relative bias, bidirectional).  A row that sees no key at all comes out as zeros, never NaN.  Where the
 // causal precondition is broken the fp32 path carries its running maximum over wholly hidden tiles by the rule the relative-bias
 // path always had (a hidden tile leaves it alone); before the two were one kernel it reset the maximum to 0 there, so such rows
 // may differ from earlier builds in the last bits.  Every input that meets the precondition gives the same bits as before.
 //
-// What the two bf16 kernels share (the helpers below): in both everything is computed TRANSPOSED.  S^T = K Q^T on
+// What the bf16 kernels share (the helpers below): in both everything is computed TRANSPOSED.  S^T = K Q^T on
 // v_mfma_f32_16x16x32_bf16 leaves (query = lane % 16, keys 16 kt + 4 (lane / 16) .. + 3) in each lane, which is the B-operand
 // layout of O^T += V^T P^T once two key tiles share one K = 32 step (k slot 8 g + j <-> key 16 (2 kp + j / 4) + 4 g + j % 4; V^T
 // is read with the same permutation, two ds_read_b64).  K rows and V^T rows are staged in LDS; rows of keys the key mask hides,
@@ -35,9 +37,12 @@
 //           and 768 workgroups for 256 CUs at B H = 768 whatever T is -- while 23 KB let several workgroups share a CU and
 //           T = 512 brings eight times as many of them; the K / V re-reads hit the L2.  Every query sees the same keys, so no
 //           tile needs the VALU path the causal kernel has for its diagonal.
+//     attn_relbias_mfma<false> -- the same kernel without the bias (uwu_attention_bidir_fwd): no bias row is staged and none is
+//           added to the scores.  The bias row was the only thing in the kernel whose size depends on T, so this instantiation
+//           takes any T the grid can hold; the entry point stops at BT_MAX = 1024.
 //     attn_text_valu<CAUSAL> -- the exact-fp32 parity path of both in the manner of attention_simple.hip: two lanes per query
 //           row, K / V tiles of 32 keys staged as fp32, online softmax; the causal bound and the key mask are selects, the bias
-//           is read per (query, key) from global memory.
+//           is read per (query, key) from global memory, or not at all (BIAS = false: the bidirectional entry point).
 #include <math.h>
 
 #include "common.h"
@@ -58,6 +63,7 @@ constexpr int CT_MAX = 128;        // longest causal sequence
 constexpr int C_KLD = HD + 8;      // causal: K row stride in LDS (elements): 144 B
 constexpr int C_VLD = CT_MAX + 8;  // causal: V^T row stride (elements): 272 B
 constexpr int RT_MAX = 512;        // longest relative-bias sequence (T5_T_MAX in text.hip is the same number)
+constexpr int BT_MAX = 1024;       // longest bidirectional sequence without a bias (ViT-L/14 at 336 x 336 has 577 tokens)
 constexpr int R_QB = 64;           // relative bias: queries per workgroup
 constexpr int R_KC = 64;           // keys per chunk
 constexpr int R_LD = HD + 8;       // row stride of both LDS tiles (elements): 144 B
@@ -235,11 +241,12 @@ __global__ void __launch_bounds__(256) attn_causal_mfma(const AttnArgs a) {
   }
 }
 
-// ---- relative bias, bf16 ----------------------------------------------------------------------------------------------------------
+// ---- relative bias (BIAS), or bidirectional with no bias at all, bf16 ---------------------------------------------------------------
+template <bool BIAS>
 __global__ void __launch_bounds__(256) attn_relbias_mfma(const AttnArgs a) {
   __shared__ __attribute__((aligned(16))) bf16_t Ks[R_KC * R_LD];
   __shared__ __attribute__((aligned(16))) bf16_t Vt[HD * R_LD];
-  __shared__ __attribute__((aligned(16))) float bs[R_BN];
+  __shared__ __attribute__((aligned(16))) float bs[BIAS ? R_BN : 4];  // without a bias: not used
   __shared__ __attribute__((aligned(16))) int kvis[R_KC];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int n = lane & 15, g = lane >> 4;
@@ -250,13 +257,15 @@ __global__ void __launch_bounds__(256) attn_relbias_mfma(const AttnArgs a) {
   const bf16_t* K = static_cast<const bf16_t*>(a.k) + (int64_t)b * T * a.ldk + h * HD;
   const bf16_t* V = static_cast<const bf16_t*>(a.v) + (int64_t)b * T * a.ldv + h * HD;
   const int64_t* mk = a.mask ? a.mask + (int64_t)b * T : nullptr;
-  const float* bias = a.bias + (int64_t)h * (2 * T - 1);
   const float LOG2E = 1.4426950408889634f;
 
   // bs[R_BM + o] = log2(e) rel_bias[h, o] for 0 <= o < 2 T - 1, zero around it
-  for (int c = tid; c < R_BN; c += 256) {
-    const int o = c - R_BM;
-    bs[c] = (o >= 0 && o < 2 * T - 1) ? bias[o] * LOG2E : 0.f;
+  if constexpr (BIAS) {
+    const float* bias = a.bias + (int64_t)h * (2 * T - 1);
+    for (int c = tid; c < R_BN; c += 256) {
+      const int o = c - R_BM;
+      bs[c] = (o >= 0 && o < 2 * T - 1) ? bias[o] * LOG2E : 0.f;
+    }
   }
   const int tq = q0 + 16 * wave + n;  // this lane's query
   const bool qok = tq < T;
@@ -301,10 +310,13 @@ __global__ void __launch_bounds__(256) attn_relbias_mfma(const AttnArgs a) {
       if (kt < nkt) {
         const f32x4 acc = score_tile<R_LD>(Ks, kt, n, g, qf);
         const i32x4 vis = *reinterpret_cast<const i32x4*>(kvis + 16 * kt + 4 * g);
-        const float* br = bs + boff + k0 + 16 * kt;
+        const float* br = BIAS ? bs + boff + k0 + 16 * kt : nullptr;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          s[kt][r] = vis[r] ? fmaf(acc[r], sc, br[r]) : -INFINITY;  // a select: nothing of a hidden key goes further
+          if constexpr (BIAS)
+            s[kt][r] = vis[r] ? fmaf(acc[r], sc, br[r]) : -INFINITY;  // a select: nothing of a hidden key goes further
+          else
+            s[kt][r] = vis[r] ? acc[r] * sc : -INFINITY;
           cmax = fmaxf(cmax, s[kt][r]);
         }
       }
@@ -343,12 +355,12 @@ __global__ void __launch_bounds__(256) attn_relbias_mfma(const AttnArgs a) {
   if (qok) store_o(static_cast<bf16_t*>(a.o) + ((int64_t)b * T + tq) * a.ldo + h * HD + 4 * g, o, l);
 }
 
-// ---- exact fp32, both ---------------------------------------------------------------------------------------------------------------
+// ---- exact fp32, all three ---------------------------------------------------------------------------------------------------------------
 // 64 query rows per workgroup (two lanes per row, 32 head dims each), keys walked 32 at a time -- all of them, or under the causal
 // mask up to the block's last row; online softmax as attn_fwd_simple
 constexpr int V_ROWS = 64, V_TILE = 32, V_HALF = HD / 2;
 
-template <bool CAUSAL>
+template <bool CAUSAL, bool BIAS = !CAUSAL>
 __global__ void __launch_bounds__(128) attn_text_valu(const AttnArgs a) {
   __shared__ __attribute__((aligned(16))) float Ks[V_TILE * HD];
   __shared__ __attribute__((aligned(16))) float Vs[V_TILE * HD];
@@ -363,7 +375,7 @@ __global__ void __launch_bounds__(128) attn_text_valu(const AttnArgs a) {
   const float* v = static_cast<const float*>(a.v) + (int64_t)b * T * a.ldv + h * HD;
   const int64_t* mk = a.mask ? a.mask + (int64_t)b * T : nullptr;
   const float* bias = nullptr;
-  if constexpr (!CAUSAL) bias = a.bias + (int64_t)h * (2 * T - 1) + (T - 1 - t);  // + key; read for valid rows and keys below T only
+  if constexpr (BIAS) bias = a.bias + (int64_t)h * (2 * T - 1) + (T - 1 - t);  // + key; read for valid rows and keys below T only
   float qr[V_HALF], oa[V_HALF];
 #pragma unroll
   for (int i = 0; i < V_HALF; i += 4) {
@@ -402,8 +414,10 @@ __global__ void __launch_bounds__(128) attn_text_valu(const AttnArgs a) {
       p += __shfl_xor(p, 1, 64);
       if constexpr (CAUSAL)
         s[j] = (k0 + j <= t && kvis[j]) ? p : -INFINITY;
-      else
+      else if constexpr (BIAS)
         s[j] = (valid && kvis[j]) ? p + bias[k0 + j] : -INFINITY;
+      else
+        s[j] = (valid && kvis[j]) ? p : -INFINITY;
       tmax = fmaxf(tmax, s[j]);
     }
     const float mx = fmaxf(m, tmax);
@@ -437,14 +451,14 @@ __global__ void __launch_bounds__(128) attn_text_valu(const AttnArgs a) {
   }
 }
 
-// what both entry points refuse; `fn` opens every message.  rel_bias may be null only where the entry point has none
+// what the entry points refuse; `fn` opens every message.  rel_bias may be null only where the entry point has none
 int check_args(const char* fn, const AttnArgs& a, bool has_bias, int d, int dtype, int t_max, int64_t bh_max) {
   UWU_CHECK_ARG(a.q && a.k && a.v && a.o && (!has_bias || a.bias), "%s: null pointer", fn);
   UWU_CHECK_ARG(dtype == UWU_F32 || dtype == UWU_BF16, "%s: bad dtype %d", fn, dtype);
   UWU_CHECK_ARG(d == HD, "%s: head dim %d (built for 64)", fn, d);
   UWU_CHECK_ARG(a.T >= 1 && a.T <= t_max, "%s: T = %d outside [1, %d]", fn, a.T, t_max);
   UWU_CHECK_ARG(a.B > 0 && a.H > 0 && (int64_t)a.B * a.H <= bh_max, "%s: bad B = %d, H = %d%s", fn, a.B, a.H,
-                has_bias ? " (B * H <= 65535)" : "");
+                bh_max == 65535 ? " (B * H <= 65535)" : "");
   const int hd = a.H * HD;
   UWU_CHECK_ARG(a.ldq >= hd && a.ldk >= hd && a.ldv >= hd && a.ldo >= hd, "%s: row stride < H*d", fn);
   const int al = dtype == UWU_BF16 ? 8 : 4;
@@ -483,10 +497,26 @@ extern "C" int uwu_attention_relbias_fwd(const void* q, const void* k, const voi
   hipStream_t st = (hipStream_t)stream;
   UwuProfScope prof(stream);
   if (dtype == UWU_BF16)
-    hipLaunchKernelGGL(attn_relbias_mfma, dim3(cdiv(T, R_QB), B * H), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(attn_relbias_mfma<true>, dim3(cdiv(T, R_QB), B * H), dim3(256), 0, st, a);
   else
-    hipLaunchKernelGGL(attn_text_valu<false>, dim3(cdiv(T, V_ROWS), B * H), dim3(128), 0, st, a);
+    hipLaunchKernelGGL((attn_text_valu<false, true>), dim3(cdiv(T, V_ROWS), B * H), dim3(128), 0, st, a);
   prof.done(UWU_PROF_ATTN_FWD, dtype == UWU_BF16 ? 0 : 1, 4.0 * B * H * HD * T * (double)T, 4.0 * B * H * HD * T * (dtype == UWU_BF16 ? 2 : 4));
   UWU_LAUNCH_CHECK("attention_relbias_fwd");
+  return UWU_OK;
+}
+
+extern "C" int uwu_attention_bidir_fwd(const void* q, const void* k, const void* v, const int64_t* key_mask, void* o, int B, int T,
+                                       int H, int d, int ldq, int ldk, int ldv, int ldo, float scale, int dtype, void* stream) {
+  UWU_CHECK_ARG(d != 80, "attention_bidir_fwd: head dim 80 is not built (ViT-H/14, apple/DFN5B-CLIP-ViT-H-14-378 included): built for 64");
+  const AttnArgs a{q, k, v, key_mask, o, B, T, H, ldq, ldk, ldv, ldo, scale, nullptr};
+  if (const int e = check_args("attention_bidir_fwd", a, false, d, dtype, BT_MAX, 65535)) return e;
+  hipStream_t st = (hipStream_t)stream;
+  UwuProfScope prof(stream);
+  if (dtype == UWU_BF16)
+    hipLaunchKernelGGL(attn_relbias_mfma<false>, dim3(cdiv(T, R_QB), B * H), dim3(256), 0, st, a);
+  else
+    hipLaunchKernelGGL((attn_text_valu<false, false>), dim3(cdiv(T, V_ROWS), B * H), dim3(128), 0, st, a);
+  prof.done(UWU_PROF_ATTN_FWD, dtype == UWU_BF16 ? 0 : 1, 4.0 * B * H * HD * T * (double)T, 4.0 * B * H * HD * T * (dtype == UWU_BF16 ? 2 : 4));
+  UWU_LAUNCH_CHECK("attention_bidir_fwd");
   return UWU_OK;
 }

@@ -120,6 +120,10 @@ _SIGS = {
     "uwu_bias_act_fwd": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, P]),
     "uwu_text_pool": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, P]),
     "uwu_attention_relbias_fwd": (c_int, [P] * 6 + [c_int] * 8 + [c_float, c_int, P]),
+    "uwu_attention_bidir_fwd": (c_int, [P] * 5 + [c_int] * 8 + [c_float, c_int, P]),
+    "uwu_clip_patches": (c_int, [P, c_int, P] + [c_int] * 5 + [P, P, c_int, P]),
+    "uwu_vit_embed": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, P]),
+    "uwu_clip_score_accum": (c_int, [P, P, P, P, c_int, c_int, c_int, P]),
     "uwu_add_rmsnorm_fwd": (c_int, [P] * 5 + [c_int, c_int, c_float, c_int, P]),
     "uwu_gated_act_fwd": (c_int, [P, P] + [c_int] * 6 + [P]),
     "uwu_t5_rel_bias": (c_int, [P, P, P, c_int, c_int, c_int, P]),

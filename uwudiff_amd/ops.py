@@ -1,4 +1,6 @@
 """Thin tensor-level wrappers over the C ABI (shape checks on the host, raw pointers to the kernels)."""
+import ctypes
+
 import torch
 
 from . import lib as L
@@ -223,6 +225,63 @@ def attention_relbias_fwd(q, k, v, rel_bias, B, T, H, d=64, scale=1.0, key_mask=
     L.call("uwu_attention_relbias_fwd", _p(q), _p(k), _p(v), L.ptr(rel_bias), None if key_mask is None else _ids(key_mask, B, T, "key_mask"),
            L.ptr(o), B, T, H, d, q.stride(0), k.stride(0), v.stride(0), o.stride(0), scale, L.dt(q), L.stream())
     return o
+
+
+def attention_bidir_fwd(q, k, v, B, T, H, d=64, scale=None, key_mask=None):
+    """Bidirectional self-attention without a bias (the CLIP image tower), forward only: q / k / v 2-D views [B*T, >= H*d] with unit
+    inner stride (column slices of the packed projection) -> o [B*T, H*d].  d = 64, T <= 1024.  key_mask: optional int64 [B, T]."""
+    scale = scale if scale is not None else d ** -0.5
+    o = torch.empty(B * T, H * d, device=q.device, dtype=q.dtype)
+    L.call("uwu_attention_bidir_fwd", _p(q), _p(k), _p(v), None if key_mask is None else _ids(key_mask, B, T, "key_mask"), L.ptr(o),
+           B, T, H, d, q.stride(0), k.stride(0), v.stride(0), o.stride(0), scale, L.dt(q), L.stream())
+    return o
+
+
+def clip_patches(images, patch, dtype, ld=None, mean=None, std=None):
+    """images [B, 3, S, S] (fp32, or uint8 with mean / std) -> [B * (S/patch)^2, ld] in `dtype`: the A operand of the patch-embedding
+    GEMM, columns (c, i, j), zeros from 3 patch^2 up to ld (default: the next multiple of 8).  With mean / std (three numbers each)
+    the images are [0, 255] and CLIP's preprocessing is fused in; without, they are copied as they are."""
+    if images.dim() != 4 or images.shape[1] != 3 or images.shape[2] != images.shape[3]:
+        raise L.UwuError(f"clip_patches: images must be [B, 3, S, S], got {tuple(images.shape)}")
+    if images.dtype not in (torch.float32, torch.uint8) or (mean is None) != (std is None):
+        raise L.UwuError(f"clip_patches: fp32 or uint8 images and mean / std together, got {images.dtype}")
+    B, _, S, _ = images.shape
+    if S % patch:
+        raise L.UwuError(f"clip_patches: image size {S} is not a multiple of the patch size {patch}")
+    K = 3 * patch * patch
+    ld = ld if ld is not None else (K + 7) // 8 * 8
+    out = torch.empty(B * (S // patch) ** 2, ld, device=images.device, dtype=dtype)
+    F3 = ctypes.c_float * 3
+    m, s = (F3(*mean), F3(*std)) if mean is not None else (None, None)
+    L.call("uwu_clip_patches", L.ptr(images), int(images.dtype == torch.uint8), L.ptr(out), B, S, patch, ld, int(mean is not None), m, s,
+           L.dt(out), L.stream())
+    return out
+
+
+def vit_embed(patch_out, class_embedding, pos_table, B):
+    """patch_out [B*Np, D], class_embedding [D], pos_table [Np + 1, D] -> [B * (Np + 1), D]: the class token first, positions added."""
+    M, D = patch_out.shape
+    T = pos_table.shape[0]
+    if M != B * (T - 1) or tuple(class_embedding.shape) != (D,) or pos_table.shape[1] != D or not (
+            patch_out.dtype == class_embedding.dtype == pos_table.dtype):
+        raise L.UwuError(f"vit_embed: patch_out {tuple(patch_out.shape)}, class_embedding {tuple(class_embedding.shape)} and pos_table "
+                         f"{tuple(pos_table.shape)} do not fit B = {B}")
+    out = torch.empty(B * T, D, device=patch_out.device, dtype=patch_out.dtype)
+    L.call("uwu_vit_embed", L.ptr(patch_out), L.ptr(class_embedding), L.ptr(pos_table), L.ptr(out), B, T, D, L.dt(out), L.stream())
+    return out
+
+
+def clip_score_accum(image_embeds, text_embeds, acc):
+    """-> scores fp32 [B] = 100 cos(image_b, text_b); acc (float64 [2] on the device) += (their sum, B), in a fixed order."""
+    if image_embeds.dim() != 2 or image_embeds.shape != text_embeds.shape or image_embeds.dtype != text_embeds.dtype:
+        raise L.UwuError(f"clip_score_accum: embeddings must be two [B, P] tensors of one dtype, got {tuple(image_embeds.shape)} "
+                         f"{image_embeds.dtype} and {tuple(text_embeds.shape)} {text_embeds.dtype}")
+    if acc.dtype != torch.float64 or acc.numel() != 2:
+        raise L.UwuError("clip_score_accum: acc must be float64 [2]")
+    B, P = image_embeds.shape
+    scores = torch.empty(B, device=image_embeds.device, dtype=torch.float32)
+    L.call("uwu_clip_score_accum", L.ptr(image_embeds), L.ptr(text_embeds), L.ptr(scores), L.ptr(acc), B, P, L.dt(image_embeds), L.stream())
+    return scores
 
 
 def add_rmsnorm_fwd(x_in, weight, eps, y=None):

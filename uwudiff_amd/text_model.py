@@ -107,7 +107,59 @@ class _TextEncoder(FlatModule):
         return cls(dict(config), **kw)
 
 
-class CLIPTextModel(_TextEncoder):
+class _CLIPTower(_TextEncoder):
+    """What the CLIP text transformer and the CLIP image tower (uwudiff_amd/vision_model.py) share: the parameters of a pre-LN
+    encoder layer with q, k, v stored back to back, and the layer stack itself.  The attention operator is the caller's."""
+
+    def _add_param(self, name, shape, alias=None):
+        self.P.add(name, shape)
+        if alias is None:
+            self._names[name] = (name, 0, None)
+
+    def _add_layers(self, prefix, n_layers, D, F):
+        """``<prefix>encoder.layers.N.*`` under transformers' names, in the order the flat buffer keeps them"""
+        add = self._add_param
+        for i in range(n_layers):
+            p = f"{prefix}encoder.layers.{i}."
+            for sfx, shape in ((".weight", (3 * D, D)), (".bias", (3 * D,))):  # q, k, v back to back: one GEMM operand
+                add(p + "self_attn.qkv_proj" + sfx, shape, alias=True)
+                for c, row in (("k", D), ("v", 2 * D), ("q", 0)):  # (transformers lists k, v, q)
+                    self._names[f"{p}self_attn.{c}_proj{sfx}"] = (p + "self_attn.qkv_proj" + sfx, row, D)
+            for name, shape in (("self_attn.out_proj", (D, D)), ("layer_norm1", None), ("mlp.fc1", (F, D)), ("mlp.fc2", (D, F)),
+                                ("layer_norm2", None)):
+                add(p + name + ".weight", shape or (D,))
+                add(p + name + ".bias", (shape[0],) if shape else (D,))
+
+    def _ln(self, x, name, y=None):
+        """(x + y, LayerNorm(x + y)): the residual add of the sublayer that produced y happens here"""
+        return ops.add_ln_modulate_fwd(x, 1, x.shape[0], y=y, gate=self.ones if y is not None else None, shift=self.w32(name + ".bias"),
+                                       scale=self.w32(name + ".weight"), mod_ld=0, eps=float(self.config["layer_norm_eps"]),
+                                       affine=True)[:2]
+
+    def _lin(self, x, name):
+        return ops.gemm(x, self.w(name + ".weight"), bias=self.w32(name + ".bias"), epilogue=L.EPI_BIAS)
+
+    def _run_layers(self, x, prefix, attn):
+        """x [B*T, D] through every layer; ``attn(q, k, v)`` is the tower's attention on column slices of the packed projection ->
+        (x, y, inputs): the stream before the last feed-forward's residual add, that feed-forward's output (the caller's next
+        LayerNorm adds it), and the input of every layer"""
+        cfg = self.config
+        D = cfg["hidden_size"]
+        inputs, y = [], None
+        for i in range(cfg["num_hidden_layers"]):
+            p = f"{prefix}encoder.layers.{i}."
+            x, n = self._ln(x, p + "layer_norm1", y)  # x: the input of layer i = the output of layer i - 1
+            inputs.append(x)
+            qkv = self._lin(n, p + "self_attn.qkv_proj")
+            o = attn(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:])
+            x, n = self._ln(x, p + "layer_norm2", self._lin(o, p + "self_attn.out_proj"))
+            u = self._lin(n, p + "mlp.fc1")
+            ops.bias_act_fwd(u, cfg["hidden_act"], out=u)
+            y = self._lin(u, p + "mlp.fc2")
+        return x, y, inputs
+
+
+class CLIPTextModel(_CLIPTower):
     """``transformers.CLIPTextModel``: ``forward(...) -> (last_hidden_state, pooled[, hidden_states])``."""
 
     kind = "clip_sd1"  # ConcatTextEncoders recomputes normed = final_layer_norm(hidden_states[layer_idx]) for this class
@@ -127,24 +179,11 @@ class CLIPTextModel(_TextEncoder):
         if D % 8 or cfg["intermediate_size"] % 8 or (self._with_projection and cfg["projection_dim"] % 8):
             raise ValueError("CLIPTextModel: widths must be multiples of 8")
 
-        def add(name, shape, alias=None):
-            self.P.add(name, shape)
-            if alias is None:
-                self._names[name] = (name, 0, None)
-
+        add = self._add_param
         F = int(cfg["intermediate_size"])
         add("embeddings.token_embedding.weight", (cfg["vocab_size"], D))
         add("embeddings.position_embedding.weight", (cfg["max_position_embeddings"], D))
-        for i in range(cfg["num_hidden_layers"]):
-            p = f"encoder.layers.{i}."
-            for sfx, shape in ((".weight", (3 * D, D)), (".bias", (3 * D,))):  # q, k, v back to back: one GEMM operand
-                add(p + "self_attn.qkv_proj" + sfx, shape, alias=True)
-                for c, row in (("k", D), ("v", 2 * D), ("q", 0)):  # (transformers lists k, v, q)
-                    self._names[f"{p}self_attn.{c}_proj{sfx}"] = (p + "self_attn.qkv_proj" + sfx, row, D)
-            for name, shape in (("self_attn.out_proj", (D, D)), ("layer_norm1", None), ("mlp.fc1", (F, D)), ("mlp.fc2", (D, F)),
-                                ("layer_norm2", None)):
-                add(p + name + ".weight", shape or (D,))
-                add(p + name + ".bias", (shape[0],) if shape else (D,))
+        self._add_layers("", cfg["num_hidden_layers"], D, F)
         add("final_layer_norm.weight", (D,))
         add("final_layer_norm.bias", (D,))
         if self._with_projection:
@@ -165,8 +204,10 @@ class CLIPTextModel(_TextEncoder):
 
     def _load_key(self, key):
         """transformers name, flat or in the ``text_model.``-prefixed layout of hub checkpoints; ``position_ids`` is a buffer older
-        checkpoints carry"""
-        return None if key.endswith("position_ids") else self._public(key.removeprefix("text_model."))
+        checkpoints carry, and a ``CLIPModel`` checkpoint holds the image tower and ``logit_scale`` next to the text model"""
+        if key.endswith("position_ids") or key.startswith(("vision_model.", "visual_projection.")) or key == "logit_scale":
+            return None
+        return self._public(key.removeprefix("text_model."))
 
     @torch.no_grad()
     def reset_parameters(self, seed=None):
@@ -188,15 +229,6 @@ class CLIPTextModel(_TextEncoder):
         self.refresh_shadow()
 
     # ------------------------------------------------------------------ forward
-    def _ln(self, x, name, y=None):
-        """(x + y, LayerNorm(x + y)): the residual add of the sublayer that produced y happens here"""
-        return ops.add_ln_modulate_fwd(x, 1, x.shape[0], y=y, gate=self.ones if y is not None else None, shift=self.w32(name + ".bias"),
-                                       scale=self.w32(name + ".weight"), mod_ld=0, eps=float(self.config["layer_norm_eps"]),
-                                       affine=True)[:2]
-
-    def _lin(self, x, name):
-        return ops.gemm(x, self.w(name + ".weight"), bias=self.w32(name + ".bias"), epilogue=L.EPI_BIAS)
-
     @torch.no_grad()
     def _encode(self, input_ids, attention_mask):
         """-> (last_hidden_state [B, T, D], pooled [B, D], hidden_states: L + 1 tensors [B, T, D], embeddings first)"""
@@ -205,17 +237,8 @@ class CLIPTextModel(_TextEncoder):
         B, T = ids.shape
         D, H = cfg["hidden_size"], cfg["num_attention_heads"]
         x = ops.text_embed(ids, self.w("embeddings.token_embedding.weight"), self.w("embeddings.position_embedding.weight"))
-        hidden, y = [], None
-        for i in range(cfg["num_hidden_layers"]):
-            p = f"encoder.layers.{i}."
-            x, n = self._ln(x, p + "layer_norm1", y)  # x: the input of layer i = the output of layer i - 1
-            hidden.append(x)
-            qkv = self._lin(n, p + "self_attn.qkv_proj")
-            o = ops.attention_causal_fwd(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], B, T, H, _HEAD_DIM, _HEAD_DIM ** -0.5, key_mask=mask)
-            x, n = self._ln(x, p + "layer_norm2", self._lin(o, p + "self_attn.out_proj"))
-            u = self._lin(n, p + "mlp.fc1")
-            ops.bias_act_fwd(u, cfg["hidden_act"], out=u)
-            y = self._lin(u, p + "mlp.fc2")
+        x, y, hidden = self._run_layers(
+            x, "", lambda q, k, v: ops.attention_causal_fwd(q, k, v, B, T, H, _HEAD_DIM, _HEAD_DIM ** -0.5, key_mask=mask))
         x, last = self._ln(x, "final_layer_norm", y)
         hidden.append(x)
         pooled = ops.text_pool(ids, last, cfg["eos_token_id"])
