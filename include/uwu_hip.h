@@ -351,7 +351,9 @@ int uwu_fp8_quantize(const void* x, int dtype, int M, int K, int ldx, const floa
  * uwu_gemm(transA=1, transB=1, UWU_EPI_ACCUM) with `blocks` workgroups as the split-K target.
  * bias_grad (optional, fp32[M]) += column sums of A = the Linear's bias gradient; the streaming kernel computes it
  * with extra MFMAs against an all-ones fragment instead of a separate pass over dY.
- * Results differ only in summation order. */
+ * Results differ only in summation order.
+ * The 192 x 384 / 384 x 192 kernel (M or N a multiple of 384, K >= 32768) runs its K loop as two wave groups one barrier
+ * apart; UWU_TRW_GROUPS=0 keeps its eight waves in phase instead -- the same result bit for bit (tools/README.md). */
 size_t uwu_gemm_wgrad_scratch_bytes(int M, int N, int K);
 int uwu_gemm_wgrad(const void* A, const void* B, float* C, float* bias_grad, int M, int N, int K, int lda, int ldb,
                    int ldc, int dtype, int blocks, void* scratch, size_t scratch_bytes, void* stream);

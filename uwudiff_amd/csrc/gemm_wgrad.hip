@@ -299,7 +299,9 @@ struct TrwPair {
   const float* bias;
   int M, N, lda, ldb, tiles, tiles_n;  // tiles = member b's tile count, tiles_n = its tile columns
 };
-template <int WM, int WN, int FI, int FJ, int NST>
+// GRP: the K loop as two wave groups one barrier apart (below); GRP = false keeps all eight waves in phase, one barrier per
+// K-step (UWU_TRW_GROUPS=0).  Both run the same MFMAs on the same fragments in the same order per accumulator.
+template <int WM, int WN, int FI, int FJ, int NST, bool GRP>
 __global__ void __launch_bounds__(512, 2) gemm_trw_kernel(const GemmArgs g, const TrwPair p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   typedef bf16_t T;
@@ -395,34 +397,101 @@ __global__ void __launch_bounds__(512, 2) gemm_trw_kernel(const GemmArgs g, cons
   for (int s = 0; s < AHEAD; ++s)
     if (s < ns) issue(s);
   constexpr int GI = FI / 2;  // A fragments per half
-  for (int s = 0; s < ns; ++s) {
-    // K-step s has landed once at most the pieces of the (up to AHEAD - 1) younger steps are outstanding
-    const int younger = ns - 1 - s < AHEAD - 1 ? ns - 1 - s : AHEAD - 1;
+  // this wave's pieces of K-step t have landed once at most the pieces of the younger ISSUED steps are outstanding.  Wherever it
+  // is called below, the steps issued so far are 0 .. min(t + AHEAD - 1, ns - 1): up to AHEAD - 1 younger ones
+  auto wait_step = [&](int t) __attribute__((always_inline)) {
+    const int younger = ns - 1 - t < AHEAD - 1 ? ns - 1 - t : AHEAD - 1;
     if (younger >= 2) r_wait_vm<2 * W_NSUB>();
     else if (younger == 1) r_wait_vm<W_NSUB>();
     else r_wait_vm<0>();
-    __syncthreads();  // everybody's pieces of step s; everybody is done reading stage (s - 1) % NST
-    if (s + AHEAD < ns) issue(s + AHEAD);
-    const unsigned so = (unsigned)((s % NST) * W_STAGE);
-    uint4 bf[FJ], af[GI];
+  };
+  if constexpr (!GRP) {
+    for (int s = 0; s < ns; ++s) {
+      wait_step(s);
+      __syncthreads();  // everybody's pieces of step s; everybody is done reading stage (s - 1) % NST
+      if (s + AHEAD < ns) issue(s + AHEAD);
+      const unsigned so = (unsigned)((s % NST) * W_STAGE);
+      uint4 bf[FJ], af[GI];
 #pragma unroll
-    for (int j = 0; j < FJ; ++j) bf[j] = frag(so, gb0 + j);
+      for (int j = 0; j < FJ; ++j) bf[j] = frag(so, gb0 + j);
 #pragma unroll
-    for (int hh = 0; hh < 2; ++hh) {
+      for (int hh = 0; hh < 2; ++hh) {
 #pragma unroll
-      for (int i = 0; i < GI; ++i) af[i] = frag(so, ga0 + GI * hh + i);
+        for (int i = 0; i < GI; ++i) af[i] = frag(so, ga0 + GI * hh + i);
 #pragma unroll
-      for (int i = 0; i < GI; ++i)
+        for (int i = 0; i < GI; ++i)
 #pragma unroll
-        for (int j = 0; j < FJ; ++j) mma_frag<T>(bf[j], af[i], acc[GI * hh + i][j]);
-      if (do_sum) {
+          for (int j = 0; j < FJ; ++j) mma_frag<T>(bf[j], af[i], acc[GI * hh + i][j]);
+        if (do_sum) {
 #pragma unroll
-        for (int i = 0; i < GI; ++i) {
-          const int fi = GI * hh + i;
-          if (fi % WN == wn) mma_frag<T>(ones, af[i], sacc[fi / WN]);
+          for (int i = 0; i < GI; ++i) {
+            const int fi = GI * hh + i;
+            if (fi % WN == wn) mma_frag<T>(ones, af[i], sacc[fi / WN]);
+          }
         }
       }
     }
+  } else {
+    // Two wave groups ONE BARRIER APART, as gemm_p8_kernel (gemm_p8.hip): group 0 = waves 0-3 (one per SIMD), group 1 = their
+    // SIMD partners 4-7 (WM x WN = 2 x 4: wave rows 0 / 1; 4 x 2: wave rows 0-1 / 2-3; partners share their B columns).  A K-step
+    // is { DMA issue + 12 fragment reads | barrier | 36 (+ bias) MFMAs | barrier }, and group 1 passes one extra barrier before
+    // its first step: while one wave of a SIMD issues MFMAs its partner reads the fragments of its own next MFMA interval, so the
+    // matrix pipe does not wait for LDS and the two waves never read LDS or want the pipe at the same time.
+    //
+    // Ordering argument.  B(k) = the k-th workgroup barrier, B(0) the one in front of the loop; interval k lies between B(k) and
+    // B(k+1).  Group 0 reads K-step s in interval 2s and multiplies it in 2s+1; group 1 reads it in 2s+1 and multiplies in 2s+2.
+    // Every wave executes 2 ns + 2 barriers: B(0), [group 1: its idle interval 0], two per K-step, [group 0: one at the end].
+    //   RAW  every wave retires its own pieces of step s by wait_step(s) in front of B(2s): both groups in interval 2s-1 --
+    //        group 0 behind its MFMAs of step s-1, group 1 at the end of its reads of step s-1 (behind its issue of step s+2), step
+    //        0 in front of B(0).  Group 0 reads step s behind B(2s), group 1 behind B(2s+1).  At either wait the issued steps
+    //        are 0 .. min(s+2, ns-1), so the count is the one of the in-phase loop: the pieces of min(ns-1-s, 2) younger steps.
+    //   WAR  step s+3 lands in stage (s-1) % 4.  Group 0 read that stage in interval 2s-2, group 1 in interval 2s-1, and each
+    //        retired its reads (lgkmcnt(0)) in front of the barrier that closed the interval: B(2s) is the barrier that proves both
+    //        groups done with it.  Group 0 issues step s+3 behind B(2s) (interval 2s), group 1 behind B(2s+1).
+    // So a piece is 6 (group 0) or 5 (group 1) intervals = 3 or 2.5 K-steps ahead of its wait; the in-phase loop has 3.  Group 1
+    // issuing in front of its MFMAs instead (interval 2s, the full 3 K-steps) gave the whole gain back: the five
+    // DMA instructions then delay the MFMAs of a SIMD whose other wave is reading, and all eight waves request at once again.
+    const int grp = wave >> 2;  // scalar
+    auto bar = [&]() __attribute__((always_inline)) {
+      __builtin_amdgcn_s_barrier();
+      __builtin_amdgcn_sched_barrier(0);
+    };
+    wait_step(0);
+    bar();                // B(0)
+    if (grp == 1) bar();  // B(1): waves 4-7 run one barrier behind their SIMD partners
+    for (int s = 0; s < ns; ++s) {
+      // read interval
+      if (s + AHEAD < ns) issue(s + AHEAD);
+      const unsigned so = (unsigned)((s % NST) * W_STAGE);
+      uint4 bf[FJ], af[FI];
+#pragma unroll
+      for (int j = 0; j < FJ; ++j) bf[j] = frag(so, gb0 + j);
+#pragma unroll
+      for (int i = 0; i < FI; ++i) af[i] = frag(so, ga0 + i);
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the stage is free for the DMA issued behind the next barrier (WAR)
+      if (grp == 1 && s + 1 < ns) wait_step(s + 1);
+      bar();
+      // MFMA interval (the order per accumulator is the in-phase loop's: one MFMA per K-step)
+      __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+      for (int hh = 0; hh < 2; ++hh) {
+#pragma unroll
+        for (int i = 0; i < GI; ++i)
+#pragma unroll
+          for (int j = 0; j < FJ; ++j) mma_frag<T>(bf[j], af[GI * hh + i], acc[GI * hh + i][j]);
+        if (do_sum) {
+#pragma unroll
+          for (int i = 0; i < GI; ++i) {
+            const int fi = GI * hh + i;
+            if (fi % WN == wn) mma_frag<T>(ones, af[fi], sacc[fi / WN]);
+          }
+        }
+      }
+      __builtin_amdgcn_s_setprio(0);
+      if (grp == 0 && s + 1 < ns) wait_step(s + 1);
+      bar();
+    }
+    if (grp == 0) bar();  // every wave has passed the same number of barriers
   }
   if (do_sum) {
     float* bg = const_cast<float*>(bias);
@@ -579,11 +648,11 @@ size_t trw_pair_scratch_bytes(int Ma, int Na, int Mb, int Nb, int K) {
   return (size_t)trw_split(tiles, K / 32) * ((size_t)Ma * Na + (size_t)Mb * Nb) * sizeof(float);
 }
 // b != NULL: the second member of a grouped launch (its A, B, C, bias, M, N and leading dimensions; K is g's)
-template <int WM, int WN, int FI, int FJ>
+template <int WM, int WN, int FI, int FJ, bool GRP>
 int launch_trw(GemmArgs g, const GemmArgs* b, void* scratch, hipStream_t st) {
   constexpr int NST = 4;
   constexpr int TBM = 16 * FI * WM, TBN = 16 * FJ * WN;
-  constexpr auto kern = gemm_trw_kernel<WM, WN, FI, FJ, NST>;
+  constexpr auto kern = gemm_trw_kernel<WM, WN, FI, FJ, NST, GRP>;
   RETURN_IF(gemm_lds_optin<kern>("gemm_trw", NST * W_STAGE));
   g.tiles_m = (g.M + TBM - 1) / TBM;
   g.tiles_n = (g.N + TBN - 1) / TBN;
@@ -614,6 +683,15 @@ int launch_trw(GemmArgs g, const GemmArgs* b, void* scratch, hipStream_t st) {
   prof.done(UWU_PROF_GEMM_WGRAD, 0, flops, bytes);  // (one record per launch: a grouped one carries both members' work)
   UWU_LAUNCH_CHECK("gemm_trw");
   return UWU_OK;
+}
+
+// The K loop's schedule: two wave groups one barrier apart; UWU_TRW_GROUPS=0 keeps the eight waves in phase (same results bit for
+// bit: tests/test_wgrad_groups_gpu.py).  kind = trw_kind()'s tile orientation.
+int launch_trw_kind(int kind, const GemmArgs& g, const GemmArgs* b, void* scratch, hipStream_t st) {
+  static UwuEnv groups("UWU_TRW_GROUPS");
+  if (groups.get().is('0'))
+    return kind == 1 ? launch_trw<2, 4, 6, 6, false>(g, b, scratch, st) : launch_trw<4, 2, 6, 6, false>(g, b, scratch, st);
+  return kind == 1 ? launch_trw<2, 4, 6, 6, true>(g, b, scratch, st) : launch_trw<4, 2, 6, 6, true>(g, b, scratch, st);
 }
 
 }  // namespace
@@ -735,8 +813,7 @@ extern "C" int uwu_gemm_wgrad(const void* A, const void* B, float* C, float* bia
     const int trw = pick_trw(g);
     if (trw && scratch && (((uintptr_t)C | (uintptr_t)scratch) & 15) == 0 && ldc % 4 == 0 &&
         scratch_bytes >= trw_scratch_bytes(M, N, K, trw)) {
-      if (trw == 1) return launch_trw<2, 4, 6, 6>(g, nullptr, scratch, (hipStream_t)stream);
-      return launch_trw<4, 2, 6, 6>(g, nullptr, scratch, (hipStream_t)stream);
+      return launch_trw_kind(trw, g, nullptr, scratch, (hipStream_t)stream);
     }
     const int tr = uwu_gemm_pick_tr(g);
     if (tr == 1) return uwu_launch_gemm_tr<8, 4>(g, scratch, scratch_bytes, (hipStream_t)stream);
@@ -783,8 +860,7 @@ extern "C" int uwu_gemm_wgrad_pair(const void* A_a, const void* B_a, float* C_a,
     const int kind = pick_trw(a);
     if (need && need <= scratch_bytes && kind && pick_trw(b) == kind && ldc_a % 4 == 0 && ldc_b % 4 == 0 &&
         (((uintptr_t)C_a | (uintptr_t)C_b | (uintptr_t)scratch) & 15) == 0) {
-      if (kind == 1) return launch_trw<2, 4, 6, 6>(a, &b, scratch, (hipStream_t)stream);
-      return launch_trw<4, 2, 6, 6>(a, &b, scratch, (hipStream_t)stream);
+      return launch_trw_kind(kind, a, &b, scratch, (hipStream_t)stream);
     }
   }
   RETURN_IF(uwu_gemm_wgrad(A_a, B_a, C_a, bias_grad_a, M_a, N_a, K, lda_a, ldb_a, ldc_a, dtype, blocks, scratch, scratch_bytes, stream));
