@@ -46,20 +46,42 @@ class DummyDataset(UwUBaseDataset):
 
 
 class TrainDataModule:
-    def __init__(self, dataset_config, dataloader_config):
+    def __init__(self, dataset_config, dataloader_config, val_dataset_config=None, val_dataloader_config=None):
         self.dataset_config = dataset_config
         self.dataloader_config = dict(dataloader_config)
+        # validation: its own dataset; the loader is the training one without shuffling and without dropping the ragged last batch
+        self.val_dataset_config = val_dataset_config
+        if val_dataloader_config is None:
+            val_dataloader_config = {**self.dataloader_config, "shuffle": False, "drop_last": False}
+        self.val_dataloader_config = dict(val_dataloader_config)
+        self.val_dataset = None
 
     def setup(self, stage: str = "fit"):
         self.dataset = load_any(self.dataset_config)
+        if self.val_dataset_config is not None:
+            # built beside the CPU generator, which is put back: a run with a validation set continues from the state a run without has
+            state = torch.get_rng_state()
+            self.val_dataset = load_any(self.val_dataset_config)
+            torch.set_rng_state(state)
         if hasattr(self, "tokenizers"):
             self.dataset.set_tokenizers(self.tokenizers)
+            if self.val_dataset is not None:
+                self.val_dataset.set_tokenizers(self.tokenizers)
 
-    def train_dataloader(self):
-        cfg = dict(self.dataloader_config)
+    def _loader(self, dataset, config):
+        cfg = dict(config)
         # the synthetic samples are in-memory tensors: worker processes would only add IPC copies
         cfg["num_workers"] = 0
-        return Data.DataLoader(self.dataset, collate_fn=self.dataset.collate, **cfg)
+        return Data.DataLoader(dataset, collate_fn=dataset.collate, **cfg)
+
+    def train_dataloader(self):
+        return self._loader(self.dataset, self.dataloader_config)
+
+    def val_dataloader(self):
+        """None without a ``val_dataset_config``: the fit loop then runs no validation"""
+        if self.val_dataset is None:
+            return None
+        return self._loader(self.val_dataset, self.val_dataloader_config)
 
     def set_tokenizers(self, tokenizers):
         self.tokenizers = tokenizers

@@ -28,6 +28,7 @@ extern "C" {
 
 #define UWU_F32 0
 #define UWU_BF16 1
+#define UWU_I64 2 /* int64 indices: only where an entry says it takes them (uwu_timestep_stats_accum) */
 
 #define UWU_OK 0
 #define UWU_EINVAL (-1)   /* bad argument / unsupported shape */
@@ -526,6 +527,18 @@ int uwu_vit_embed(const void* patch_out, const void* class_embedding, const void
  * when it wants the mean. */
 int uwu_clip_score_accum(const void* image_embeds, const void* text_embeds, float* scores, double* acc, int B, int P, int dtype,
                          void* stream);
+/* Per-timestep statistics of a validation batch, accumulated on the device (reference src/duwu/trainer/callbacks.py:76-91: a Python
+ * loop over all n_steps timesteps with three masked reductions each).  For every sample b whose bucket k = trunc(timesteps[b]) (toward
+ * zero, as `.long()`: 3.9 -> 3, -0.5 -> 0) lies in [0, n_steps):  stats[0][k] += 1,  stats[1][k] += losses[b],  stats[2][k] += losses[b]^2.
+ * A sample with a bucket outside that range or a NaN timestep is ignored; a NaN or inf loss reaches its own bucket only.  losses fp32
+ * [B]; timesteps [B], int64 (t_dtype = UWU_I64) or fp32 (UWU_F32); stats: 3 * n_steps doubles, zeroed by the caller before the first
+ * batch.  With loss_mean (ONE fp32 on the device, the batch's scalar loss):  totals[0] += B * *loss_mean,  totals[1] += B  (two
+ * doubles; the sample-weighted mean of an epoch is totals[0] / totals[1]); loss_mean == NULL skips that, and totals may then be NULL.
+ * Everything is accumulated in double, the square is formed in double.  Each bucket is owned by one thread, which adds its samples in
+ * ascending b, and one thread writes totals: no atomics, bits independent of the launch geometry, and two calls give what one call on
+ * the concatenation gives.  B > 0, 1 <= n_steps <= 65536.  No host synchronisation. */
+int uwu_timestep_stats_accum(const float* losses, const void* timesteps, int t_dtype, const float* loss_mean, int B, int n_steps,
+                             double* stats, double* totals, void* stream);
 /* T5LayerNorm with the previous sublayer's residual add fused in:  x_out = x_in + y (y may be NULL: x_out is then not written and
  * may be NULL),  n_out = x_out * rsqrt(mean(x_out^2) + eps) * weight -- no mean subtraction, no bias.  x_in, y, x_out, n_out [M, D]
  * contiguous in `dtype`, weight fp32 [D]; D a multiple of 8, 16-byte aligned; statistics in fp32, taken of x_out as stored.

@@ -1,6 +1,7 @@
 """Step driver that replaces the subset of ``lightning.Trainer`` the reference's launcher uses
 (test_scripts/test_train.py:43-77): device placement, the fit loop, backward, data-parallel gradient exchange,
-global-norm clipping, optimizer + per-step LR schedule, rank-aware seeding, periodic logging.
+global-norm clipping, optimizer + per-step LR schedule, rank-aware seeding, periodic logging, and the validation schedule
+(``val_check_interval`` and its companions; a pass is :meth:`Fitter.validate`).
 
 Lightning's loop is third-party control plane; the hot path it drives (loss -> denoiser fwd/bwd -> all-reduce ->
 clip -> AdamW) is the part this build implements natively.  Checkpoint / resume follow Lightning's file layout
@@ -29,10 +30,14 @@ def seed_everything(seed: int):
 class ModelCheckpoint:
     """``lightning.pytorch.callbacks.ModelCheckpoint`` subset the reference configs use (configs/demo_training.yaml:14-19):
     ``dirpath``, ``filename``, ``every_n_train_steps`` (or ``every_n_epochs``), ``save_last``.  Registered by
-    :meth:`Fitter.fit` as a step hook that calls :meth:`Fitter.save_checkpoint` (Lightning checkpoint layout)."""
+    :meth:`Fitter.fit` as a step hook that calls :meth:`Fitter.save_checkpoint` (Lightning checkpoint layout).
+
+    ``monitor`` naming a key of the validation record (``val/loss``) switches to "the best k by that value": one file at the end of
+    every validation pass that is no sanity pass, the best ``save_top_k`` (default 1, Lightning's) by ``mode`` kept, the others removed;
+    the periodic triggers are then off (``save_last`` still writes).  ``monitor: step`` or none: the newest k files, as before."""
 
     def __init__(self, dirpath=None, filename=None, every_n_train_steps=None, every_n_epochs=None, save_last=False,
-                 save_top_k=None, **kw):
+                 save_top_k=None, monitor=None, mode="min", **kw):
         self.dirpath = dirpath or "checkpoints"
         self.filename = filename or "epoch={epoch}-step={step}"  # Lightning's default name
         self.every_n_train_steps = int(every_n_train_steps) if every_n_train_steps else None
@@ -41,6 +46,38 @@ class ModelCheckpoint:
         self.save_top_k = save_top_k  # monitor: step / mode: max (the reference YAML) == keep the newest k files
         self.kw = kw
         self.saved = []
+        self.monitor = None if monitor in (None, "step") else str(monitor)
+        if mode not in ("min", "max"):
+            raise ValueError(f"ModelCheckpoint: mode must be 'min' or 'max', got {mode!r}")
+        self.mode = mode
+        self.best = []  # (path, score) of the files kept for `monitor`, best first
+
+    def _rank(self, score):
+        """sort key, best first; a NaN score is the worst in either mode"""
+        if score != score:
+            return float("inf")
+        return score if self.mode == "min" else -score
+
+    def on_validation_end(self, fitter, module=None):
+        if self.monitor is None or fitter.sanity_checking or fitter.fast_dev_run or not fitter.val_history:
+            return  # (Lightning's fast_dev_run disables checkpoint callbacks)
+        rec = fitter.val_history[-1]
+        if self.monitor not in rec:
+            raise KeyError(f"ModelCheckpoint: monitor {self.monitor!r} is no key of the validation record {sorted(rec)}")
+        k = 1 if self.save_top_k is None else int(self.save_top_k)
+        if k == 0:
+            return
+        path, score = self._path(fitter), float(rec[self.monitor])
+        ranked = sorted([(p, s) for p, s in self.best if p != path] + [(path, score)], key=lambda e: self._rank(e[1]))
+        keep = ranked if k < 0 else ranked[:k]
+        if (path, score) not in keep:  # (not among the best k: nothing is written)
+            return
+        fitter.save_checkpoint(path, callbacks={"ModelCheckpoint": {"saved": list(self.saved), "best": [[p, s] for p, s in keep]}})
+        if fitter.global_rank == 0:
+            for old, _ in ranked[len(keep):]:
+                if os.path.exists(old):
+                    os.remove(old)
+        self.best = keep
 
     def _save(self, fitter, path):
         k = self.save_top_k
@@ -59,16 +96,17 @@ class ModelCheckpoint:
         return os.path.join(self.dirpath, name + ".ckpt")
 
     def on_step(self, fitter):
-        if self.every_n_train_steps and fitter.global_step % self.every_n_train_steps == 0:
+        if self.monitor is None and self.every_n_train_steps and fitter.global_step % self.every_n_train_steps == 0:
             self._save(fitter, self._path(fitter))
 
     def on_epoch_end(self, fitter):
-        if self.every_n_epochs and (fitter.current_epoch + 1) % self.every_n_epochs == 0:
+        if self.monitor is None and self.every_n_epochs and (fitter.current_epoch + 1) % self.every_n_epochs == 0:
             self._save(fitter, self._path(fitter))
 
     def on_fit_end(self, fitter):
         if self.save_last:
-            fitter.save_checkpoint(self._path(fitter, "last"))
+            fitter.save_checkpoint(self._path(fitter, "last"), callbacks={"ModelCheckpoint": {
+                "saved": list(self.saved), "best": [[p, s] for p, s in self.best]}} if self.monitor is not None else None)
 
 
 class LearningRateMonitor:
@@ -123,7 +161,8 @@ def _dist_env():
 class Fitter:
     def __init__(self, max_steps=-1, precision="bf16-mixed", gradient_clip_val=None, fast_dev_run=False,
                  log_every_n_steps=10, accelerator="gpu", devices=1, strategy=None, callbacks=(), logger=(),
-                 max_epochs=None, default_root_dir=None, **ignored):
+                 max_epochs=None, default_root_dir=None, val_check_interval=1.0, check_val_every_n_epoch=1, limit_val_batches=1.0,
+                 num_sanity_val_steps=2, val_seed=0, **ignored):
         self.max_steps = max_steps
         self.default_root_dir = os.fspath(default_root_dir) if default_root_dir is not None else os.getcwd()
         self.precision = str(precision)
@@ -135,6 +174,21 @@ class Fitter:
         self.global_step = 0
         self.current_epoch = 0
         self.history = []
+        self.val_history = []  # one record per validation pass (the sanity pass leaves none)
+        for name, v in (("val_check_interval", val_check_interval), ("limit_val_batches", limit_val_batches)):
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or v < 0 or (isinstance(v, float) and v > 1.0):
+                raise ValueError(f"{name} must be a float in [0, 1] or a non-negative int, got {v!r}")
+        if isinstance(val_check_interval, float) and val_check_interval == 0.0:
+            raise ValueError("val_check_interval must be a float in (0, 1] or a positive int, got 0.0")
+        if check_val_every_n_epoch is not None and (isinstance(check_val_every_n_epoch, bool) or int(check_val_every_n_epoch) < 1):
+            raise ValueError(f"check_val_every_n_epoch must be a positive int or None, got {check_val_every_n_epoch!r}")
+        self.val_check_interval = val_check_interval
+        self.check_val_every_n_epoch = None if check_val_every_n_epoch is None else int(check_val_every_n_epoch)
+        self.limit_val_batches = limit_val_batches
+        self.num_sanity_val_steps = int(num_sanity_val_steps)
+        self.val_seed = int(val_seed)
+        self.sanity_checking = False
+        self.val_stats = None
         self.step_hooks = []  # callables(fitter) run after every optimizer step (e.g. periodic save_checkpoint)
         self.callbacks = list(callbacks or [])
         use_gpu = torch.cuda.is_available() and str(accelerator) != "cpu"
@@ -201,11 +255,14 @@ class Fitter:
         self.global_step = int(ckpt["global_step"])
         self.current_epoch = int(ckpt.get("epoch", 0))
         self._resume_batches = ckpt.get("batches_in_epoch")  # None: a checkpoint of an earlier version
-        saved = (ckpt.get("callbacks") or {}).get("ModelCheckpoint", {}).get("saved")
-        if saved is not None:  # top-k pruning continues over the files the interrupted run had written
-            for cb in self.callbacks:
-                if isinstance(cb, ModelCheckpoint):
+        state = (ckpt.get("callbacks") or {}).get("ModelCheckpoint", {})
+        saved, best = state.get("saved"), state.get("best")
+        for cb in self.callbacks:  # top-k pruning continues over the files the interrupted run had written
+            if isinstance(cb, ModelCheckpoint):
+                if saved is not None:
                     cb.saved = list(saved)
+                if best is not None:
+                    cb.best = [(p, float(s)) for p, s in best]
         return ckpt
 
     def _to_device(self, batch):
@@ -214,6 +271,100 @@ class Fitter:
         tok = [{k: v.to(self.device, non_blocking=True) for k, v in t.items()} for t in tok]
         added = {k: v.to(self.device, non_blocking=True) for k, v in added.items()}
         return x, captions, tok, added, ca
+
+    # ------------------------------------------------------------------ validation
+    def _hook(self, name, *args):
+        for cb in self.callbacks:
+            fn = getattr(cb, name, None)
+            if fn is not None:
+                fn(self, *args)
+
+    def _n_val_batches(self, loader):
+        n = len(loader)
+        if self.fast_dev_run:
+            return min(1, n)
+        lim = self.limit_val_batches
+        return int(n * lim) if isinstance(lim, float) else min(int(lim), n)
+
+    def _val_due(self, k, n_batches, epoch):
+        """validate after training batch k (1-based) of `epoch`?  Lightning's rules, as its documentation states them."""
+        if self.fast_dev_run:
+            return True
+        vci, every = self.val_check_interval, self.check_val_every_n_epoch
+        if every is None:
+            if isinstance(vci, float):
+                raise ValueError("check_val_every_n_epoch: null needs an int val_check_interval (a number of training batches)")
+            return self.global_step % vci == 0
+        if (epoch + 1) % every != 0:
+            return False
+        period = max(1, int(n_batches * vci)) if isinstance(vci, float) else vci
+        return k % period == 0
+
+    def validate(self, module, loader, limit=None, sanity=False):
+        """One validation pass over (the first ``limit`` batches of) ``loader``: ``module.validation_step(batch, idx) -> (loss, aux)``
+        under ``no_grad`` in eval mode, ``aux.losses`` / ``aux.timesteps`` / ``loss`` into a :class:`TimestepLossStats`, one all-reduce
+        and ONE device-to-host read at the end.  Returns the record that is appended to ``val_history`` (a sanity pass appends nothing).
+
+        The pass draws from its own random stream (``val_seed``: every pass sees the same timesteps and noise) and leaves training where
+        it was: the device generator's (seed, offset), the CPU generator (a DataLoader iterator draws from it), every sub-module's
+        train / eval flag and the DiT's fp8 step counters are saved before and put back after.  It takes no optimizer step, calls no
+        backward and does not write ``ema_loss`` or ``global_step``."""
+        from .validation import TimestepLossStats
+
+        t_start = time.time()
+        cuda_gen = None
+        if self.device.type == "cuda":
+            cuda_gen = torch.cuda.default_generators[self.device.index if self.device.index is not None else torch.cuda.current_device()]
+            cuda_state = cuda_gen.get_state()
+        cpu_state = torch.get_rng_state()
+        modes = [(m, m.training) for m in module.modules()]
+        unet = getattr(module, "unet", None)
+        f8 = {k: getattr(unet, k) for k in ("_f8_steps", "_f8_mode") if hasattr(unet, k)}
+        self.sanity_checking = bool(sanity)
+        n_seen = 0
+        try:
+            if cuda_gen is not None:
+                cuda_gen.manual_seed(self.val_seed)
+            torch.default_generator.manual_seed(self.val_seed)
+            module.eval()
+            stats = None
+            with torch.no_grad():
+                self._hook("on_validation_epoch_start", module)
+                for idx, batch in enumerate(loader):
+                    if limit is not None and idx >= limit:
+                        break
+                    batch = self._to_device(batch)
+                    out = module.validation_step(batch, idx)
+                    loss, aux = out
+                    if stats is None:
+                        stats = self.val_stats
+                        if stats is None or stats.n_steps != int(module.n_diffusion_time_steps) or stats.device != aux.losses.device:
+                            stats = self.val_stats = TimestepLossStats(module.n_diffusion_time_steps, aux.losses.device)
+                        stats.reset()
+                    stats.update(aux.losses, aux.timesteps, loss)
+                    self._hook("on_validation_batch_end", module, out, batch, idx)
+                    n_seen += 1
+                res = stats.reduce().compute() if stats is not None else {"loss": float("nan"), "n_samples": 0}
+                rec = {"step": self.global_step, "epoch": self.current_epoch, "val/loss": res["loss"],
+                       "val_samples": int(res["n_samples"]), "elapsed_s": round(time.time() - getattr(self, "_t0", t_start), 3)}
+                if not sanity:
+                    self.val_history.append(rec)
+                    if self.global_rank == 0:
+                        print(json.dumps(rec), flush=True)
+                self._hook("on_validation_epoch_end", module)
+        finally:
+            for m, was in modes:
+                m.training = was
+            for k, v in f8.items():
+                setattr(unet, k, v)
+            torch.set_rng_state(cpu_state)
+            if cuda_gen is not None:
+                cuda_gen.set_state(cuda_state)
+        try:
+            self._hook("on_validation_end", module)
+        finally:
+            self.sanity_checking = False
+        return rec
 
     def fit(self, module, datamodule, ckpt_path=None):
         if hasattr(module.unet, "cfg"):
@@ -224,6 +375,10 @@ class Fitter:
         module._trainer = self
         datamodule.setup("fit")
         loader = datamodule.train_dataloader()
+        val_loader = datamodule.val_dataloader() if hasattr(datamodule, "val_dataloader") else None
+        n_val = 0
+        if val_loader is not None and hasattr(module, "validation_step"):
+            n_val = self._n_val_batches(val_loader)  # 0 (limit_val_batches = 0, an empty loader): validation is off
         cfg = module.configure_optimizers()
         opt = cfg["optimizer"] if isinstance(cfg, dict) else cfg
         sched = cfg["lr_scheduler"]["scheduler"] if isinstance(cfg, dict) and "lr_scheduler" in cfg else None
@@ -249,11 +404,20 @@ class Fitter:
         ckpt_cbs = [] if self.fast_dev_run else [cb for cb in self.callbacks if isinstance(cb, ModelCheckpoint)]
         params = [p for g in opt.param_groups for p in g["params"]]
         max_steps = 1 if self.fast_dev_run else self.max_steps
-        t0 = time.time()
+        t0 = self._t0 = time.time()
         epoch = self.current_epoch if ckpt_path is not None else 0  # a resumed run continues its epoch count (max_epochs, {epoch})
         done = False
         # resume mid-epoch like Lightning does: skip the batches the interrupted epoch had already consumed
         n_batches = max(len(loader), 1)
+        if n_val and not self.fast_dev_run:
+            vci = self.val_check_interval
+            if self.check_val_every_n_epoch is None and isinstance(vci, float):
+                raise ValueError("check_val_every_n_epoch: null needs an int val_check_interval (a number of training batches)")
+            if self.check_val_every_n_epoch is not None and not isinstance(vci, float) and vci > n_batches:
+                raise ValueError(f"val_check_interval ({vci}) is larger than the number of training batches of an epoch ({n_batches}); "
+                                 f"set check_val_every_n_epoch: null to count batches across epochs")
+            if isinstance(vci, int) and vci < 1:
+                raise ValueError("val_check_interval must be a float in (0, 1] or a positive int, got 0")
         resume_skip = 0
         if ckpt_path is not None:
             rb = getattr(self, "_resume_batches", None)
@@ -267,6 +431,11 @@ class Fitter:
         self.batches_in_epoch = resume_skip
         grads_zeroed = False
         one = None
+        if n_val and ckpt_path is None and not self.fast_dev_run and self.num_sanity_val_steps != 0:
+            # Lightning's sanity check: a few validation batches before the first training step (not on a resume: the interrupted run
+            # had none at this point); its results reach the callbacks only
+            ns = self.num_sanity_val_steps
+            self.validate(module, val_loader, limit=n_val if ns < 0 else min(ns, n_val), sanity=True)
         while not done:
             finished_epoch, ran = True, 0
             for bi, batch in enumerate(loader):
@@ -326,6 +495,8 @@ class Fitter:
                     self.history.append(rec)
                     if self.global_rank == 0:
                         print(json.dumps(rec), flush=True)
+                if n_val and self._val_due(bi + 1, n_batches, epoch):
+                    self.validate(module, val_loader, limit=n_val)
                 if done:
                     break
             if not finished_epoch or (ran == 0 and resume_skip == 0 and done):

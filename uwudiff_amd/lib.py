@@ -12,7 +12,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libuwu_hip.so")
 
-F32, BF16 = 0, 1
+F32, BF16, I64 = 0, 1, 2
 PT = {"epsilon": 0, "v_prediction": 1, "sample": 2, "rectified_flow": 3}
 EPI_NONE, EPI_BIAS, EPI_BIAS_GELU, EPI_DGELU, EPI_BIAS_SILU, EPI_ACCUM = 0, 1, 2, 3, 4, 5
 ACT = {"quick_gelu": 0, "gelu": 1}  # UWU_ACT_QUICK_GELU, UWU_ACT_GELU_ERF
@@ -124,6 +124,7 @@ _SIGS = {
     "uwu_clip_patches": (c_int, [P, c_int, P] + [c_int] * 5 + [P, P, c_int, P]),
     "uwu_vit_embed": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, P]),
     "uwu_clip_score_accum": (c_int, [P, P, P, P, c_int, c_int, c_int, P]),
+    "uwu_timestep_stats_accum": (c_int, [P, P, c_int, P, c_int, c_int, P, P, P]),
     "uwu_add_rmsnorm_fwd": (c_int, [P] * 5 + [c_int, c_int, c_float, c_int, P]),
     "uwu_gated_act_fwd": (c_int, [P, P] + [c_int] * 6 + [P]),
     "uwu_t5_rel_bias": (c_int, [P, P, P, c_int, c_int, c_int, P]),
