@@ -1,7 +1,8 @@
 """Step driver that replaces the subset of ``lightning.Trainer`` the reference's launcher uses
 (test_scripts/test_train.py:43-77): device placement, the fit loop, backward, data-parallel gradient exchange,
 global-norm clipping, optimizer + per-step LR schedule, rank-aware seeding, periodic logging, and the validation schedule
-(``val_check_interval`` and its companions; a pass is :meth:`Fitter.validate`).
+(``val_check_interval`` and its companions; a pass is :meth:`Fitter.validate`), and gradient accumulation
+(``accumulate_grad_batches``: an optimizer step every N-th batch on the summed gradient / N).
 
 Lightning's loop is third-party control plane; the hot path it drives (loss -> denoiser fwd/bwd -> all-reduce ->
 clip -> AdamW) is the part this build implements natively.  Checkpoint / resume follow Lightning's file layout
@@ -162,8 +163,17 @@ class Fitter:
     def __init__(self, max_steps=-1, precision="bf16-mixed", gradient_clip_val=None, fast_dev_run=False,
                  log_every_n_steps=10, accelerator="gpu", devices=1, strategy=None, callbacks=(), logger=(),
                  max_epochs=None, default_root_dir=None, val_check_interval=1.0, check_val_every_n_epoch=1, limit_val_batches=1.0,
-                 num_sanity_val_steps=2, val_seed=0, **ignored):
+                 num_sanity_val_steps=2, val_seed=0, accumulate_grad_batches=1, **ignored):
         self.max_steps = max_steps
+        n_acc = accumulate_grad_batches
+        if isinstance(n_acc, dict):
+            raise TypeError(f"accumulate_grad_batches must be an int >= 1, got the dict {n_acc!r}: a per-epoch schedule is Lightning's "
+                            f"GradientAccumulationScheduler callback, which is not built")
+        if isinstance(n_acc, bool) or not isinstance(n_acc, int) or n_acc < 1:
+            raise TypeError(f"accumulate_grad_batches must be an int >= 1, got {n_acc!r}")
+        self.accumulate_grad_batches = n_acc
+        self.accum_pending = 0  # micro-batches summed into the gradient and not yet applied (0 at every optimizer step)
+        self.train_batches = 0  # training batches consumed over all epochs (== global_step when accumulate_grad_batches is 1)
         self.default_root_dir = os.fspath(default_root_dir) if default_root_dir is not None else os.getcwd()
         self.precision = str(precision)
         self.gradient_clip_val = gradient_clip_val
@@ -226,6 +236,9 @@ class Fitter:
         # which is wrong once an epoch was cut short by max_steps or the loader length changes)
         ckpt = {"epoch": self.current_epoch, "global_step": self.global_step, "pytorch-lightning_version": "uwudiff_amd",
                 "batches_in_epoch": int(getattr(self, "batches_in_epoch", 0)),
+                # the batch counter of its own (val_check_interval counts batches, global_step optimizer steps) and how many of those
+                # batches sit in the gradient unapplied: a resume replays them
+                "train_batches": int(self.train_batches), "accum_pending": int(self.accum_pending),
                 "callbacks": callbacks or {},
                 "state_dict": snap(dict(module.state_dict())),
                 "optimizer_states": [snap(opt.state_dict())],
@@ -255,6 +268,8 @@ class Fitter:
         self.global_step = int(ckpt["global_step"])
         self.current_epoch = int(ckpt.get("epoch", 0))
         self._resume_batches = ckpt.get("batches_in_epoch")  # None: a checkpoint of an earlier version
+        self._resume_pending = int(ckpt.get("accum_pending", 0))
+        self.train_batches = int(ckpt.get("train_batches", self.global_step))  # (earlier versions: one step per batch)
         state = (ckpt.get("callbacks") or {}).get("ModelCheckpoint", {})
         saved, best = state.get("saved"), state.get("best")
         for cb in self.callbacks:  # top-k pruning continues over the files the interrupted run had written
@@ -294,7 +309,7 @@ class Fitter:
         if every is None:
             if isinstance(vci, float):
                 raise ValueError("check_val_every_n_epoch: null needs an int val_check_interval (a number of training batches)")
-            return self.global_step % vci == 0
+            return self.train_batches % vci == 0
         if (epoch + 1) % every != 0:
             return False
         period = max(1, int(n_batches * vci)) if isinstance(vci, float) else vci
@@ -418,17 +433,29 @@ class Fitter:
                                  f"set check_val_every_n_epoch: null to count batches across epochs")
             if isinstance(vci, int) and vci < 1:
                 raise ValueError("val_check_interval must be a float in (0, 1] or a positive int, got 0")
+        n_acc = self.accumulate_grad_batches
         resume_skip = 0
         if ckpt_path is not None:
             rb = getattr(self, "_resume_batches", None)
+            if rb is None and n_acc > 1:
+                raise ValueError("this checkpoint does not say how far into its epoch it was written, and global_step counts optimizer "
+                                 "steps, not batches, when accumulate_grad_batches > 1: resume it with accumulate_grad_batches = 1")
             resume_skip = int(rb) if rb is not None else (self.global_step % n_batches)
             if rb is None and resume_skip == 0 and self.global_step > 0:
                 resume_skip = n_batches  # (old checkpoints: written after the last batch of their epoch)
             if resume_skip >= n_batches:
                 epoch += 1  # the checkpoint was written after the last batch of its epoch: that epoch is complete
                 resume_skip = 0
+            pending = min(getattr(self, "_resume_pending", 0), resume_skip)
+            if pending:  # written inside a window (a validation-triggered save): the partial sum is not stored, the window starts again
+                resume_skip -= pending
+                self.train_batches -= pending
+                if self.global_rank == 0:
+                    print(f"resume: the checkpoint was written {pending} batch(es) into an accumulation window; replaying them "
+                          f"from batch {resume_skip + 1} of epoch {epoch}", flush=True)
         self.current_epoch = epoch
         self.batches_in_epoch = resume_skip
+        self.accum_pending = 0
         grads_zeroed = False
         one = None
         if n_val and ckpt_path is None and not self.fast_dev_run and self.num_sanity_val_steps != 0:
@@ -445,31 +472,50 @@ class Fitter:
                     done, finished_epoch = True, False
                     break
                 module.global_step = self.global_step
-                if not grads_zeroed:  # (a fused step leaves the gradients zeroed: FlatFusedOptimizer.step(zero_grad=True))
+                # an optimizer step follows batch k (1-based) of the epoch when k % N == 0 or k is the epoch's last: windows never
+                # span epochs.  Every other batch only adds into the gradient.
+                boundary = n_acc == 1 or (bi + 1) % n_acc == 0 or bi + 1 >= n_batches or bool(self.fast_dev_run)
+                # (a fused step leaves the gradients zeroed: FlatFusedOptimizer.step(zero_grad=True); inside a window nothing is zeroed)
+                if not grads_zeroed and self.accum_pending == 0:
                     for p in params:
                         if p.grad is not None:
                             p.grad.zero_()
+                sync.defer(not boundary)  # no exchange inside a window: the boundary's backward and all_reduce carry the whole sum
                 out = module.training_step(self._to_device(batch), self.global_step)
                 loss = out["loss"]
                 if one is None or one.device != loss.device or one.dtype != loss.dtype:
                     one = torch.ones_like(loss)  # (kept: autograd's own ones_like(loss) is a fill launch per step)
                 loss.backward(one)
+                self.accum_pending += 1
+                self.train_batches += 1
+                ran += 1
+                self.batches_in_epoch = bi + 1
+                if not boundary:
+                    grads_zeroed = False  # (what the last step zeroed now holds a partial sum)
+                    if n_val and self._val_due(bi + 1, n_batches, epoch):
+                        self.validate(module, val_loader, limit=n_val)  # (writes no gradient: the partial sum survives the pass)
+                    continue
+                window, self.accum_pending = self.accum_pending, 0
+                # the gradient used is (sum over the window) / N, also in a short last window (Lightning divides every loss by N);
+                # 1/N rides on the factor that already carries 1/world into the norm and update kernels
+                scale = sync.pre_scale / n_acc
                 clip = None
                 if isinstance(opt, FlatFusedOptimizer):
                     chunks = sync.all_reduce(params[0].grad)
                     if self.gradient_clip_val:
                         sync.wait_all()
-                        clip = opt.grad_norm_clip(self.gradient_clip_val, pre_scale=sync.pre_scale)
-                        opt.step(clip=clip, pre_scale=sync.pre_scale, zero_grad=True)
+                        clip = opt.grad_norm_clip(self.gradient_clip_val, pre_scale=scale)
+                        opt.step(clip=clip, pre_scale=scale, zero_grad=True)
                     else:
-                        opt.step(pre_scale=sync.pre_scale, chunks=chunks, before_chunk=sync.wait_chunk, zero_grad=True)
+                        opt.step(pre_scale=scale, chunks=chunks, before_chunk=sync.wait_chunk, zero_grad=True)
                     grads_zeroed = True
                 else:  # foreign optimizer (e.g. lion): plain torch path on the flat buffer
                     for p in params:
                         if self.world_size > 1:
                             sync.all_reduce(p.grad)  # same chunked exchange; nothing was reduced early (no hook)
                             sync.wait_all()
-                            p.grad.mul_(sync.pre_scale)
+                        if self.world_size > 1 or n_acc > 1:
+                            p.grad.mul_(scale)
                     if self.gradient_clip_val:
                         torch.nn.utils.clip_grad_norm_(params, self.gradient_clip_val)
                     opt.step()
@@ -480,8 +526,6 @@ class Fitter:
                 if sched is not None:
                     sched.step()
                 self.global_step += 1
-                ran += 1
-                self.batches_in_epoch = bi + 1
                 if 0 <= max_steps <= self.global_step:  # checked at the END of the step: no empty extra epoch afterwards
                     done = True
                     finished_epoch = bi + 1 >= n_batches
@@ -492,6 +536,8 @@ class Fitter:
                 if self.global_step % self.log_every_n_steps == 0 or self.fast_dev_run or done:
                     rec = {"step": self.global_step, "loss": float(loss.detach()), "ema_loss": float(module.ema_loss),
                            "lr": opt.param_groups[0]["lr"], "elapsed_s": round(time.time() - t0, 3)}
+                    if n_acc > 1:
+                        rec["accum"] = window  # micro-batches in this window (`loss` is the last one's, as Lightning's on_step log)
                     self.history.append(rec)
                     if self.global_rank == 0:
                         print(json.dumps(rec), flush=True)

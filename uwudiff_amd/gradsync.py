@@ -17,6 +17,9 @@ records one event per group of transformer blocks, ``DiT.set_grad_ready_hook``) 
 those slices (2/3 of DiT-S/2's gradient bytes) are reduced on the communication stream behind their event while the
 rest of the backward still runs, and :meth:`all_reduce` afterwards only reduces what is left.  Every rank issues the
 same collectives in the same order (block groups last-to-first, then the remainder in offset order).
+
+Gradient accumulation (``Fitter(accumulate_grad_batches=N)``): inside a window the buffer holds a partial sum and nothing is
+exchanged (:meth:`FlatGradSync.defer`); the batch that ends the window exchanges the whole sum once, as above.
 """
 import ctypes
 import os
@@ -68,6 +71,7 @@ class FlatGradSync:
         self._direct = None  # _DirectRccl when UWU_RCCL_DIRECT=1 (device tensors, world > 1)
         self.events = []
         self._early = []  # [(offset, length, event)] reduced from inside the backward of the current step
+        self.deferred = False  # inside a gradient-accumulation window: the buffer holds a partial sum, nothing is exchanged
 
     @property
     def pre_scale(self):
@@ -100,9 +104,16 @@ class FlatGradSync:
             model.set_grad_ready_hook(self._on_ready)
         return self
 
+    def defer(self, flag=True):
+        """Gradient accumulation: while deferred the backward's ready slices are not reduced (:meth:`_on_ready` returns at once and
+        records nothing) and :meth:`all_reduce` must not be called.  The batch that ends the window runs with ``defer(False)``:
+        its backward and its :meth:`all_reduce` then exchange the whole accumulated sum once, exactly as a step without a window."""
+        self.deferred = bool(flag)
+        return self
+
     def _on_ready(self, flat_grad, ranges):
         """Called by the model between enqueueing its backward launches and returning to autograd."""
-        if self.world == 1:
+        if self.world == 1 or self.deferred:
             return
         if not flat_grad.is_cuda:  # gloo on CPU tensors (tests): synchronous
             for off, ln, _ in ranges:
@@ -123,6 +134,9 @@ class FlatGradSync:
         reduced already during this step's backward.  Returns the chunk list [(offset, length), ...] covering the whole
         buffer; on CUDA the work is asynchronous on the communication stream and ``self.events[i]`` marks chunk i
         reduced."""
+        if self.deferred:
+            raise RuntimeError("FlatGradSync.all_reduce inside a deferred (gradient accumulation) window: the partial sum would be "
+                               "summed over the ranks now and again at the boundary")
         n = flat_grad.numel()
         early, self._early = sorted(self._early), []
         self.events = []
