@@ -225,6 +225,21 @@ int uwu_adamw_fp16_step(float* p, float* g, void* m16, void* v16, void* p_bf16, 
  * element alignment. */
 int uwu_param_decay(float* p, void* p_bf16, int64_t n, double factor, void* stream);
 
+/* Weight averaging on flat buffers (torch.optim.swa_utils.AveragedModel as lightning.pytorch.callbacks.WeightAveraging /
+ * EMAWeightAveraging drive it; uwudiff_amd/averaging.py):
+ *   avg[i] = fma(keep, avg[i], take * p[i])      fp32: two roundings per element, 8 B read and 4 B written per parameter
+ * keep and take are formed in double on the host and rounded once (an EMA: keep = decay, take = 1 - decay; 1 - 0.999f is off
+ * by 1.3e-5 relative; the running mean after n updates: keep = n / (n + 1), take = 1 / (n + 1)).  avg and p 16-byte aligned,
+ * n > 0.  p is only read. */
+int uwu_ema_update(float* avg, const float* p, int64_t n, float keep, float take, void* stream);
+
+/* The average put in place of the weights, no pointer moved, one pass, no third buffer:
+ *   mode 0:  avg[i] <-> p[i]      bit for bit (NaN payloads, -0.0 and subnormals survive: the words travel as integers)
+ *   mode 1:  p[i] = avg[i]        avg is only read
+ * and p_bf16[i] (may be NULL) = the bf16 rounding of the new p[i], as uwu_cast_f32_to_bf16 rounds.  Mode 0 is its own inverse.
+ * avg and p 16-byte aligned, p_bf16 8-byte aligned, n > 0; avg == p and overlapping [avg, avg + n) / [p, p + n) are refused. */
+int uwu_ema_swap(float* avg, float* p, void* p_bf16, int64_t n, int mode, void* stream);
+
 int uwu_cast_f32_to_bf16(const float* src, void* dst, int64_t n, void* stream);
 int uwu_cast_bf16_to_f32(const void* src, float* dst, int64_t n, void* stream);
 

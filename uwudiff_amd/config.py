@@ -28,6 +28,8 @@ ALIASES = {
     "lion_pytorch.Lion": "uwudiff_amd.optim.FusedLion",  # the commented alternative of the reference's training YAMLs
     "lightning.pytorch.callbacks.ModelCheckpoint": "uwudiff_amd.engine.ModelCheckpoint",
     "lightning.pytorch.callbacks.LearningRateMonitor": "uwudiff_amd.engine.LearningRateMonitor",
+    "lightning.pytorch.callbacks.WeightAveraging": "uwudiff_amd.averaging.WeightAveraging",  # on the flat buffer
+    "lightning.pytorch.callbacks.EMAWeightAveraging": "uwudiff_amd.averaging.EMAWeightAveraging",
 }
 
 

@@ -1,6 +1,6 @@
 // Flat-buffer optimizer kernels: global grad norm (+clip coefficient), fused AdamW / Lion / AdamWFP16 with bf16 shadow
-// refresh, dtype casts.  HBM-bound: AdamW moves 28 B/param, Lion and AdamWFP16 20 B/param (+2 B/param for the bf16
-// shadow, +4 B/param for the zeroed gradient).
+// refresh, the weight average (update, exchange with the weights), dtype casts.  HBM-bound: AdamW moves 28 B/param, Lion and
+// AdamWFP16 20 B/param (+2 B/param for the bf16 shadow, +4 B/param for the zeroed gradient), the average's update 12 B/param.
 // Reference: src/duwu/trainer/trainer.py:52-74 (torch.optim.AdamW + Lightning gradient_clip_val),
 // src/duwu/trainer/optimizers.py (AdamWFP16), lion_pytorch.Lion (configs/demo_training*.yaml, commented alternative).
 #include "common.h"
@@ -240,6 +240,52 @@ __global__ void __launch_bounds__(256) param_decay_kernel(float* __restrict__ p,
   }
 }
 
+// Weight averaging (uwudiff_amd/averaging.py; torch.optim.swa_utils.AveragedModel as Lightning's WeightAveraging drives it):
+//   avg = keep * avg + take * p      one multiply and one fused multiply-add per element, 8 B read + 4 B written per parameter
+__global__ void __launch_bounds__(256) ema_update_kernel(float* __restrict__ avg, const float* __restrict__ p, int64_t n,
+                                                         float keep, float take) {
+  const int64_t n4 = n >> 2;
+  const int64_t stride = (int64_t)gridDim.x * 256;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
+    f32x4 av = load4(avg + 4 * i), pv = load4(p + 4 * i);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) av[j] = __builtin_fmaf(keep, av[j], take * pv[j]);
+    store4(avg + 4 * i, av);
+  }
+  if (blockIdx.x == 0) {
+    for (int64_t i = (n4 << 2) + threadIdx.x; i < n; i += 256) avg[i] = __builtin_fmaf(keep, avg[i], take * p[i]);
+  }
+}
+
+// The average put in place of the weights without moving a pointer: p <- avg (and the bf16 shadow of the new p, rounded as
+// cast_kernel rounds), avg <- the old p when `exchange`.  The fp32 words travel as integers: every bit pattern survives.
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ float bits_f32(uint32_t u) { return __builtin_bit_cast(float, u); }
+
+__global__ void __launch_bounds__(256) ema_swap_kernel(uint32_t* __restrict__ avg, uint32_t* __restrict__ p,
+                                                       bf16_t* __restrict__ pbf, int64_t n, int exchange) {
+  const int64_t n4 = n >> 2;
+  const int64_t stride = (int64_t)gridDim.x * 256;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
+    const u32x4 av = *reinterpret_cast<const u32x4*>(avg + 4 * i);
+    if (exchange) {
+      const u32x4 pv = *reinterpret_cast<const u32x4*>(p + 4 * i);
+      *reinterpret_cast<u32x4*>(avg + 4 * i) = pv;
+    }
+    *reinterpret_cast<u32x4*>(p + 4 * i) = av;
+    if (pbf) store4(pbf + 4 * i, f32x4{bits_f32(av[0]), bits_f32(av[1]), bits_f32(av[2]), bits_f32(av[3])});
+  }
+  if (blockIdx.x == 0) {
+    for (int64_t i = (n4 << 2) + threadIdx.x; i < n; i += 256) {
+      const uint32_t a = avg[i];
+      if (exchange) avg[i] = p[i];
+      p[i] = a;
+      if (pbf) pbf[i] = from_f32<bf16_t>(bits_f32(a));
+    }
+  }
+}
+
 template <typename TS, typename TD>
 __global__ void __launch_bounds__(256) cast_kernel(const TS* __restrict__ s, TD* __restrict__ d, int64_t n) {
   const int64_t n4 = n >> 2;
@@ -326,6 +372,27 @@ extern "C" int uwu_param_decay(float* p, void* p_bf16, int64_t n, double factor,
   hipLaunchKernelGGL(param_decay_kernel, dim3(ew_grid(n / 4, 256)), dim3(256), 0, (hipStream_t)stream, p,
                      (bf16_t*)p_bf16, n, head, (float)factor);
   UWU_LAUNCH_CHECK("param_decay");
+  return UWU_OK;
+}
+
+extern "C" int uwu_ema_update(float* avg, const float* p, int64_t n, float keep, float take, void* stream) {
+  UWU_CHECK_ARG(avg && p && n > 0, "ema_update: bad args");
+  UWU_CHECK_ARG((((uintptr_t)avg | (uintptr_t)p) & 15) == 0, "ema_update: buffers must be 16-byte aligned");
+  hipLaunchKernelGGL(ema_update_kernel, dim3(ew_grid(n / 4, 256)), dim3(256), 0, (hipStream_t)stream, avg, p, n, keep, take);
+  UWU_LAUNCH_CHECK("ema_update");
+  return UWU_OK;
+}
+
+extern "C" int uwu_ema_swap(float* avg, float* p, void* p_bf16, int64_t n, int mode, void* stream) {
+  UWU_CHECK_ARG(avg && p && n > 0 && (mode == 0 || mode == 1), "ema_swap: bad args");
+  UWU_CHECK_ARG((((uintptr_t)avg | (uintptr_t)p) & 15) == 0, "ema_swap: buffers must be 16-byte aligned");
+  UWU_CHECK_ARG(p_bf16 == nullptr || ((uintptr_t)p_bf16 & 7) == 0, "ema_swap: bf16 shadow must be 8-byte aligned");
+  const uintptr_t lo = (uintptr_t)avg < (uintptr_t)p ? (uintptr_t)avg : (uintptr_t)p;
+  const uintptr_t hi = (uintptr_t)avg < (uintptr_t)p ? (uintptr_t)p : (uintptr_t)avg;
+  UWU_CHECK_ARG((hi - lo) / 4 >= (uint64_t)n, "ema_swap: avg and p must not overlap");
+  hipLaunchKernelGGL(ema_swap_kernel, dim3(ew_grid(n / 4, 256)), dim3(256), 0, (hipStream_t)stream, (uint32_t*)avg,
+                     (uint32_t*)p, (bf16_t*)p_bf16, n, mode == 0);
+  UWU_LAUNCH_CHECK("ema_swap");
   return UWU_OK;
 }
 

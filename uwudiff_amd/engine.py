@@ -2,7 +2,9 @@
 (test_scripts/test_train.py:43-77): device placement, the fit loop, backward, data-parallel gradient exchange,
 global-norm clipping, optimizer + per-step LR schedule, rank-aware seeding, periodic logging, and the validation schedule
 (``val_check_interval`` and its companions; a pass is :meth:`Fitter.validate`), and gradient accumulation
-(``accumulate_grad_batches``: an optimizer step every N-th batch on the summed gradient / N).
+(``accumulate_grad_batches``: an optimizer step every N-th batch on the summed gradient / N), and the callback
+hooks a weight average needs (``setup``, ``on_train_batch_end``, ``on_train_epoch_end``, ``on_train_end``, ``on_save_checkpoint``,
+``on_load_checkpoint``, ``on_exception``, a callback's own ``state_dict``: uwudiff_amd/averaging.py).
 
 Lightning's loop is third-party control plane; the hot path it drives (loss -> denoiser fwd/bwd -> all-reduce ->
 clip -> AdamW) is the part this build implements natively.  Checkpoint / resume follow Lightning's file layout
@@ -17,6 +19,7 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
+from .averaging import WeightAveraging
 from .gradsync import FlatGradSync
 from .optim import FlatFusedOptimizer
 
@@ -201,6 +204,8 @@ class Fitter:
         self.val_stats = None
         self.step_hooks = []  # callables(fitter) run after every optimizer step (e.g. periodic save_checkpoint)
         self.callbacks = list(callbacks or [])
+        if sum(isinstance(cb, WeightAveraging) for cb in self.callbacks) > 1:
+            raise ValueError("more than one weight-averaging callback: one average is kept per fit (averaging.py)")
         use_gpu = torch.cuda.is_available() and str(accelerator) != "cpu"
         if self.world_size > 1 and not dist.is_initialized():
             os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
@@ -239,10 +244,14 @@ class Fitter:
                 # the batch counter of its own (val_check_interval counts batches, global_step optimizer steps) and how many of those
                 # batches sit in the gradient unapplied: a resume replays them
                 "train_batches": int(self.train_batches), "accum_pending": int(self.accum_pending),
-                "callbacks": callbacks or {},
+                "callbacks": dict(callbacks or {}),
                 "state_dict": snap(dict(module.state_dict())),
                 "optimizer_states": [snap(opt.state_dict())],
                 "lr_schedulers": [sched.state_dict()] if sched is not None and hasattr(sched, "state_dict") else []}
+        for cb in self.callbacks:  # a callback with state of its own (Lightning's Callback.state_dict / state_key)
+            if callable(getattr(cb, "state_dict", None)):
+                ckpt["callbacks"][getattr(cb, "state_key", type(cb).__name__)] = cb.state_dict()
+        self._hook("on_save_checkpoint", module, ckpt)
         if self.global_rank == 0:
             os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
             torch.save(ckpt, path)
@@ -252,6 +261,10 @@ class Fitter:
         """Resume: parameters (+ bf16 shadow), optimizer moments / step count, scheduler, global_step."""
         module, opt, sched = self._fit_state
         ckpt = torch.load(path, map_location="cpu", weights_only=True)
+        if "current_model_state" in ckpt and not any(isinstance(cb, WeightAveraging) for cb in self.callbacks) and self.global_rank == 0:
+            print("resume: the checkpoint was written with weight averaging and this run has no such callback: the averaged weights "
+                  "of state_dict are loaded, the trained weights under current_model_state were not used", flush=True)
+        self._hook("on_load_checkpoint", module, ckpt)  # (may redirect ckpt["state_dict"])
         sd = ckpt["state_dict"]
         # the denoiser keeps ONE flat parameter and exposes named views: it restores itself from the `unet.*` entries;
         # everything else (buffers such as ema_loss, other sub-modules) goes through the generic loader
@@ -278,6 +291,10 @@ class Fitter:
                     cb.saved = list(saved)
                 if best is not None:
                     cb.best = [(p, float(s)) for p, s in best]
+            else:
+                own = (ckpt.get("callbacks") or {}).get(getattr(cb, "state_key", type(cb).__name__))
+                if own is not None and callable(getattr(cb, "load_state_dict", None)):
+                    cb.load_state_dict(own)
         return ckpt
 
     def _to_device(self, batch):
@@ -367,6 +384,9 @@ class Fitter:
                     if self.global_rank == 0:
                         print(json.dumps(rec), flush=True)
                 self._hook("on_validation_epoch_end", module)
+        except BaseException as e:  # (a callback that changed something for the pass puts it back: the weight average does)
+            self._hook("on_exception", module, e)
+            raise
         finally:
             for m, was in modes:
                 m.training = was
@@ -415,6 +435,7 @@ class Fitter:
                 lyc.mark_dirty()
             if hasattr(module.unet, "refresh_shadow"):
                 module.unet.refresh_shadow()
+        self._hook("setup", module, "fit")  # the weights are what training starts from (a weight average is created here)
         # Lightning's fast_dev_run disables checkpoint callbacks and loggers
         ckpt_cbs = [] if self.fast_dev_run else [cb for cb in self.callbacks if isinstance(cb, ModelCheckpoint)]
         params = [p for g in opt.param_groups for p in g["params"]]
@@ -481,7 +502,8 @@ class Fitter:
                         if p.grad is not None:
                             p.grad.zero_()
                 sync.defer(not boundary)  # no exchange inside a window: the boundary's backward and all_reduce carry the whole sum
-                out = module.training_step(self._to_device(batch), self.global_step)
+                batch = self._to_device(batch)
+                out = module.training_step(batch, self.global_step)
                 loss = out["loss"]
                 if one is None or one.device != loss.device or one.dtype != loss.dtype:
                     one = torch.ones_like(loss)  # (kept: autograd's own ones_like(loss) is a fill launch per step)
@@ -492,6 +514,7 @@ class Fitter:
                 self.batches_in_epoch = bi + 1
                 if not boundary:
                     grads_zeroed = False  # (what the last step zeroed now holds a partial sum)
+                    self._hook("on_train_batch_end", module, out, batch, bi)
                     if n_val and self._val_due(bi + 1, n_batches, epoch):
                         self.validate(module, val_loader, limit=n_val)  # (writes no gradient: the partial sum survives the pass)
                     continue
@@ -529,6 +552,7 @@ class Fitter:
                 if 0 <= max_steps <= self.global_step:  # checked at the END of the step: no empty extra epoch afterwards
                     done = True
                     finished_epoch = bi + 1 >= n_batches
+                self._hook("on_train_batch_end", module, out, batch, bi)
                 for hook in self.step_hooks:
                     hook(self)
                 for cb in ckpt_cbs:
@@ -549,6 +573,7 @@ class Fitter:
                 break  # cut short by max_steps: the epoch is partial -- no epoch-end hooks, no epoch count
             if hasattr(module, "on_train_epoch_end"):
                 module.on_train_epoch_end()
+            self._hook("on_train_epoch_end", module)
             for cb in ckpt_cbs:
                 cb.on_epoch_end(self)
             epoch += 1
@@ -561,6 +586,7 @@ class Fitter:
                 break  # one pass when neither bound is given
         for cb in ckpt_cbs:
             cb.on_fit_end(self)
+        self._hook("on_train_end", module)  # (after the `last` checkpoint: that file resumes; the module returned holds the average)
         if self.device.type == "cuda":
             torch.cuda.synchronize()
         return self.history
