@@ -448,7 +448,13 @@ int uwu_add_ln_modulate_fwd_q8(const void* x_in, const void* y, const float* gat
  *   dx_out = dx_in + LN_bwd(dh * (1+scale_b))        (dx_in may be NULL for the last norm)
  *   dy     = gate_b * dx_out                          (if y given)
  *   dshift_b += sum_t dh ; dscale_b += sum_t dh*xhat ; dgate_b += sum_t dx_out*y   (fp32 atomics)
- * dmod rows live in a zero-initialised [B, mod_ld] fp32 buffer. */
+ * mean / rstd are used exactly as given (normally the forward's).  dmod rows live in a [B, mod_ld] fp32 buffer; the sums are
+ * ADDED to its contents (zero it for plain gradients) in arbitrary order, so two runs agree to fp32 rounding, not bit for
+ * bit; nothing outside the three D-wide slices is written, and a NULL dshift / dscale / dgate skips that sum.
+ * D: a multiple of 8 up to 3072 -- narrower than the forward, which takes D <= 4096; a wider D is refused with
+ * UWU_EINVAL before anything is launched.  affine = 1 with mod_ld = 0, no y, dshift and dscale given and D <= 2048 runs the
+ * one-vector kernel (8 waves, 16 / 32 / 64 rows per workgroup by M); every other call runs the per-sample kernel, whose rows
+ * per workgroup (32 down to 1) follow the powers of two that divide T. */
 int uwu_add_ln_modulate_bwd(const void* dh, const void* x, const float* mean, const float* rstd,
                             const float* scale, const void* dx_in, const void* y, const float* gate,
                             int mod_ld, void* dx_out, void* dy, float* dshift, float* dscale, float* dgate,
