@@ -185,6 +185,43 @@ int uwu_latent_finish(const float* x, float* y, int B, int64_t n, int rescale, f
                       size_t ws_bytes, void* stream);
 int uwu_image_u8(const void* x, int dtype, void* y, int B, int H, int W, void* stream);
 
+/* ------------------------------------------------------------------ training images
+ * resize_and_crop_image (data/utils.py:25-58) for a batch of decoded pictures: Pillow's 8-bit resampler, byte for byte, then the crop,
+ * ToTensor and Normalize(0.5, 0.5).
+ *
+ * The rule for one axis with `in` source pixels, `out` output pixels and a filter of support S (doubles, libm's sin):
+ *   scale = in / out; fs = max(scale, 1); support = S * fs; ksize = ceil(support) * 2 + 1
+ *   output xx: center = (xx + 0.5) * scale; xmin = max((int)(center - support + 0.5), 0); n = min((int)(center + support + 0.5), in) - xmin
+ *              w[x] = filter((x + xmin - center + 0.5) / fs), x < n; k[x] = w[x] / (sum of w, ascending x)
+ *              K[x] = (int)(k < 0 ? k * 2^22 - 0.5 : k * 2^22 + 0.5)
+ *   pixel   = clamp((2^21 + sum_x src[xmin + x] * K[x]) >> 22, 0, 255)   (int32 accumulator, arithmetic shift, per channel)
+ * The horizontal pass runs first and writes uint8; the vertical pass reads that; a pass whose axis keeps its size is skipped.
+ *
+ * uwu_resample_ksize / uwu_resample_coeffs: HOST-ONLY (no device call, usable without a GPU; the pointers are HOST pointers).
+ *   coeffs int32 [count, ksize] (entries past n are 0) and bounds int32 [count, 2] = (xmin, n) for the output indices
+ *   first .. first + count - 1 of one axis.  ksize: the row length, or UWU_EINVAL for a bad size / filter.
+ * uwu_image_resize_crop: src is ONE device buffer of src_bytes bytes holding B uint8 [h, w, 3] pictures.  HOST arrays describe them:
+ *   src_off int64 [B]    byte offset of picture b
+ *   meta    int32 [B, 6] (src_h, src_w, new_h, new_w, top, left): its size, the size it is resized to, its window in the resized picture
+ *   tab_off int64 [B, 4] offsets (int32 elements) into the DEVICE buffer `tables` (tables_len elements) of: the horizontal coeffs
+ *                        [Wt, ksize] and bounds [Wt, 2] of output columns left .. left + Wt - 1, the vertical coeffs [Ht, ksize] and
+ *                        bounds [Ht, 2] of output rows top .. top + Ht - 1 (uwu_resample_coeffs's layout; ignored for a skipped pass)
+ *   out [B, 3, Ht, Wt] (UWU_F32 / UWU_BF16): normalize = 1 writes (u / 255 - 0.5) / 0.5, normalize = 0 writes u / 255, each the fp32
+ *   value of that chain of IEEE operations (bf16: its round-to-nearest-even).  Two launches per group of 16 pictures: the horizontal
+ *   pass writes only the source rows the window's output rows touch into ws (uwu_image_resize_crop_ws_bytes), the vertical pass
+ *   reads them.  Every argument is checked on the host before anything is launched (window inside the resized picture, resized
+ *   size >= target, B / Ht / Wt >= 1, pointers non-null and 16-byte aligned, offsets inside src and tables, dtype, filter); a bound
+ *   read from `tables` is clamped to the rows / columns the picture has, so a wrong table gives wrong pixels, never a stray read. */
+#define UWU_FILTER_BILINEAR 0 /* support 1 */
+#define UWU_FILTER_BICUBIC 1  /* support 2, a = -0.5 */
+#define UWU_FILTER_LANCZOS 2  /* support 3 */
+int uwu_resample_ksize(int in_size, int out_size, int filter);
+int uwu_resample_coeffs(int in_size, int out_size, int filter, int first, int count, int32_t* coeffs, int32_t* bounds);
+size_t uwu_image_resize_crop_ws_bytes(int B, const int32_t* meta, int Ht, int Wt, int filter);
+int uwu_image_resize_crop(const void* src, int64_t src_bytes, const int64_t* src_off, const int32_t* meta, const int32_t* tables,
+                          int64_t tables_len, const int64_t* tab_off, void* out, int dtype, int B, int Ht, int Wt, int filter,
+                          int normalize, void* ws, size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------ optimizer (a15) */
 
 /* Global L2 norm of a flat fp32 buffer (Lightning gradient_clip_val, demo_training.yaml:12):

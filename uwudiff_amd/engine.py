@@ -22,6 +22,7 @@ import torch.distributed as dist
 from .averaging import WeightAveraging
 from .gradsync import FlatGradSync
 from .optim import FlatFusedOptimizer
+from .preprocess import RaggedImages, ragged_to_device
 
 
 def seed_everything(seed: int):
@@ -299,7 +300,10 @@ class Fitter:
 
     def _to_device(self, batch):
         x, captions, tok, added, ca = batch
-        x = x.to(self.device, non_blocking=True)
+        if isinstance(x, RaggedImages):  # decoded pictures of a folder dataset: resized, cropped and normalised on the device
+            x = ragged_to_device(x, self.device)
+        else:
+            x = x.to(self.device, non_blocking=True)
         tok = [{k: v.to(self.device, non_blocking=True) for k, v in t.items()} for t in tok]
         added = {k: v.to(self.device, non_blocking=True) for k, v in added.items()}
         return x, captions, tok, added, ca

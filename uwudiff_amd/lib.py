@@ -17,6 +17,7 @@ PT = {"epsilon": 0, "v_prediction": 1, "sample": 2, "rectified_flow": 3}
 EPI_NONE, EPI_BIAS, EPI_BIAS_GELU, EPI_DGELU, EPI_BIAS_SILU, EPI_ACCUM = 0, 1, 2, 3, 4, 5
 ACT = {"quick_gelu": 0, "gelu": 1}  # UWU_ACT_QUICK_GELU, UWU_ACT_GELU_ERF
 GATE = {"gated-gelu": 0}  # UWU_GATE_GELU_TANH
+FILTER = {"bilinear": 0, "bicubic": 1, "lanczos": 2}  # UWU_FILTER_*
 
 
 class UwuError(RuntimeError):
@@ -72,6 +73,10 @@ _SIGS = {
     "uwu_latent_finish_ws_bytes": (ctypes.c_size_t, [c_int, c_int64]),
     "uwu_latent_finish": (c_int, [P, P, c_int, c_int64, c_int, c_float, c_float, P, ctypes.c_size_t, P]),
     "uwu_image_u8": (c_int, [P, c_int, P, c_int, c_int, c_int, P]),
+    "uwu_resample_ksize": (c_int, [c_int, c_int, c_int]),
+    "uwu_resample_coeffs": (c_int, [c_int, c_int, c_int, c_int, c_int, P, P]),
+    "uwu_image_resize_crop_ws_bytes": (ctypes.c_size_t, [c_int, P, c_int, c_int, c_int]),
+    "uwu_image_resize_crop": (c_int, [P, c_int64, P, P, P, c_int64, P, P] + [c_int] * 6 + [P, ctypes.c_size_t, P]),
     "uwu_grad_sqnorm_clip": (c_int, [P, c_int64, c_float, c_float, P, P, P]),
     "uwu_adamw_step": (c_int, [P, P, P, P, P, c_int64, c_float, c_float, c_float, c_float, c_float, c_int, c_float,
                                P, c_int, P]),

@@ -16,11 +16,17 @@ class Compose:
         return x
 
 
-class Resize:
-    """Bilinear resize of a PIL image to ``size`` = (height, width); an int resizes the SHORTER side to it and keeps the aspect ratio,
-    as torchvision does."""
+INTERPOLATION = {"nearest": Image.NEAREST, "bilinear": Image.BILINEAR, "bicubic": Image.BICUBIC, "lanczos": Image.LANCZOS}
 
-    def __init__(self, size):
+
+class Resize:
+    """Resize of a PIL image to ``size`` = (height, width); an int resizes the SHORTER side to it and keeps the aspect ratio, as
+    torchvision does.  ``interpolation``: a name of ``INTERPOLATION`` or a PIL resampling constant; bilinear by default."""
+
+    def __init__(self, size, interpolation="bilinear"):
+        if isinstance(interpolation, str) and interpolation.lower() not in INTERPOLATION:
+            raise ValueError(f"Resize: interpolation must be one of {sorted(INTERPOLATION)}, got {interpolation!r}")
+        self.interpolation = INTERPOLATION[interpolation.lower()] if isinstance(interpolation, str) else interpolation
         self.size = int(size) if isinstance(size, int) else tuple(int(s) for s in size)
         if not isinstance(self.size, int) and len(self.size) not in (1, 2):
             raise ValueError(f"Resize: size must be an int or (height, width), got {size!r}")
@@ -35,7 +41,7 @@ class Resize:
             wh = (size, max(1, int(size * h / w))) if w == short else (max(1, int(size * w / h)), size)
         else:
             wh = (size[1], size[0])
-        return img.resize(wh, Image.BILINEAR)
+        return img.resize(wh, self.interpolation)
 
 
 class ToTensor:
