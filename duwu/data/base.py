@@ -72,6 +72,10 @@ class TrainDataModule:
         cfg = dict(config)
         # the synthetic samples are in-memory tensors: worker processes would only add IPC copies
         cfg["num_workers"] = 0
+        if getattr(dataset, "buckets", None) is not None:
+            # aspect-ratio buckets: every batch from one bucket; batch_size / shuffle / drop_last go to the batch sampler, not twice
+            sampler = dataset.batch_sampler(cfg.pop("batch_size", 1), cfg.pop("shuffle", False), cfg.pop("drop_last", False))
+            return Data.DataLoader(dataset, collate_fn=dataset.collate, batch_sampler=sampler, **cfg)
         return Data.DataLoader(dataset, collate_fn=dataset.collate, **cfg)
 
     def train_dataloader(self):

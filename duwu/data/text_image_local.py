@@ -12,7 +12,7 @@ from PIL import Image
 from torch.utils.data import Dataset
 
 from duwu.data.base import UwUBaseDataset
-from duwu.data.utils import plan_resize_and_crop, resize_and_crop_image
+from duwu.data.utils import BucketBatchSampler, assign_bucket, make_buckets, plan_resize_and_crop, resize_and_crop_image
 from duwu.utils import get_images_recursively
 from uwudiff_amd.preprocess import RaggedImages
 from uwudiff_amd.transforms import ToTensor
@@ -64,10 +64,16 @@ class LocalTextImageTrainDataset(UwUBaseDataset):
     ``add_time_ids = [orig_h, orig_w, top, left, target_h, target_w]``, SDXL's micro-conditioning: the size of the FILE, the crop's
     offset in the resized picture, and the target.  The file's size rather than the resized one: SDXL conditions on the
     resolution the picture had before any resizing, so that low-resolution sources can be told from sharp ones at sampling time;
-    the resized size says nothing the target does not."""
+    the resized size says nothing the target does not.
+
+    ``buckets`` (aspect-ratio buckets): ``None`` -- every picture takes ``target_size``; a mapping -- the keyword
+    arguments of ``duwu.data.utils.make_buckets``; a list of ``[width, height]`` pairs -- taken as given.  The constructor then reads
+    every file's size (its header, no decode) and assigns the file to the bucket of the nearest aspect ratio; that bucket is the
+    index's target in ``__getitem__`` and in ``add_time_ids``.  A batch must come from one bucket: ``batch_sampler`` gives such
+    batches, ``collate`` refuses any other, and ``TrainDataModule`` builds its loader from ``batch_sampler``."""
 
     def __init__(self, image_dir: str | None = None, image_paths: list[str] | None = None, target_size=(256, 256), random_crop=True,
-                 resize_on_device=True, filter="lanczos", tokenizers=(), **kwargs):
+                 resize_on_device=True, filter="lanczos", tokenizers=(), buckets=None, **kwargs):
         if (image_dir is None) == (image_paths is None):
             raise ValueError("LocalTextImageTrainDataset: give image_dir or image_paths (one of them)")
         if filter not in ("lanczos", "bicubic", "bilinear"):
@@ -78,6 +84,19 @@ class LocalTextImageTrainDataset(UwUBaseDataset):
         self.resize_on_device = bool(resize_on_device)
         self.filter = filter
         self.tokenizers = list(tokenizers) if isinstance(tokenizers, (list, tuple)) else [tokenizers]
+        self.buckets, self.bucket_of = None, None
+        if buckets is not None:
+            if hasattr(buckets, "keys"):
+                self.buckets = make_buckets(**{str(k): buckets[k] for k in buckets.keys()})
+            else:
+                self.buckets = [(int(b[0]), int(b[1])) for b in buckets]
+            if not self.buckets:
+                raise ValueError("LocalTextImageTrainDataset: buckets is empty")
+            self.bucket_of = []
+            for path in self.image_paths:
+                with Image.open(path) as raw:  # the header only: no pixel is decoded
+                    width, height = raw.size
+                self.bucket_of.append(assign_bucket(width, height, self.buckets))
 
     def set_tokenizers(self, tokenizers):
         self.tokenizers = tokenizers
@@ -85,7 +104,18 @@ class LocalTextImageTrainDataset(UwUBaseDataset):
     def __len__(self):
         return len(self.image_paths)
 
+    def target_of(self, index):
+        """(width, height) the picture at ``index`` is resized and cropped to"""
+        return self.target_size if self.buckets is None else self.buckets[self.bucket_of[index]]
+
+    def batch_sampler(self, batch_size, shuffle=False, drop_last=False):
+        """batches of one bucket each, for ``DataLoader(batch_sampler=...)``"""
+        if self.buckets is None:
+            raise ValueError("LocalTextImageTrainDataset.batch_sampler: the dataset has no buckets")
+        return BucketBatchSampler(self.bucket_of, batch_size, shuffle, drop_last)
+
     def __getitem__(self, index):
+        target = self.target_of(index)
         path = self.image_paths[index]
         txt = Path(path).with_suffix(".txt")
         if not txt.exists():
@@ -95,21 +125,26 @@ class LocalTextImageTrainDataset(UwUBaseDataset):
             image = raw.convert("RGB")
         width, height = image.size
         if self.resize_on_device:
-            new_size, (left, top) = plan_resize_and_crop(width, height, self.target_size, self.random_crop)
+            new_size, (left, top) = plan_resize_and_crop(width, height, target, self.random_crop)
             sample = {"image": torch.from_numpy(np.array(image, dtype=np.uint8)), "plan": (new_size, (left, top))}
         else:
-            sample, new_size, (left, top) = resize_and_crop_image(image, self.target_size, self.random_crop, self.filter)
+            sample, new_size, (left, top) = resize_and_crop_image(image, target, self.random_crop, self.filter)
         return {
             "sample": sample,
             "caption": caption,
             "tokenizer_out": [t(caption, padding="max_length", truncation=True, return_tensors="pt") for t in self.tokenizers],
-            "add_time_ids": torch.tensor([height, width, top, left, self.target_size[1], self.target_size[0]]),
+            "add_time_ids": torch.tensor([height, width, top, left, target[1], target[0]]),
         }
 
     def collate(self, batch):
+        # the target of the batch: what every item's add_time_ids[4:6] = (height, width) says (one bucket per batch)
+        targets = {(int(x["add_time_ids"][5]), int(x["add_time_ids"][4])) for x in batch}
+        if len(targets) != 1:
+            raise ValueError(f"LocalTextImageTrainDataset.collate: a batch mixes the targets {sorted(targets)}; draw batches of one "
+                             f"bucket with batch_sampler()")
         if not self.resize_on_device:
             return UwUBaseDataset.collate(batch)
-        ragged = RaggedImages.pack([x["sample"]["image"] for x in batch], [x["sample"]["plan"] for x in batch], self.target_size,
+        ragged = RaggedImages.pack([x["sample"]["image"] for x in batch], [x["sample"]["plan"] for x in batch], targets.pop(),
                                    self.filter)
         # the other four slots as the inherited collate makes them
         _, caption, tokenizer_outputs, added, ca = UwUBaseDataset.collate([{**x, "sample": torch.empty(0)} for x in batch])

@@ -631,6 +631,11 @@ int uwu_attention_bias_bwd(const void* q, const void* k, const void* v, const fl
                            const void* dO, const float* lse, float* delta, void* dq, void* dk, void* dv, int B,
                            int Tq, int Tk, int H, int d, int ldq, int ldk, int ldv, int ldo, float scale, int dtype,
                            void* stream);
+/* Which kernels uwu_attention_fwd (pass = 0) / uwu_attention_bwd (pass = 1) and their key-bias forms run on this shape: 1 = the MFMA
+ * kernels (bf16; head dim 40 / 64 / 72 / 80 / 128; row strides multiples of 8; Tq a multiple of 64, or -- at head dim 40 / 64 / 80 -- any Tq
+ * above 256, whose last query tile is guarded), 0 = the generic ones.  HOST-ONLY (no device call, usable without a GPU).  It is the predicate the dispatch
+ * itself evaluates; the dispatch also wants every tensor 16-byte aligned, which this query assumes. */
+int uwu_attention_route(int pass, int Tq, int Tk, int d, int ldq, int ldk, int ldv, int ldo, int dtype);
 
 /* Axial RoPE with learnable per-head log-frequencies, exactly as the reference writes it (src/duwu/modules/rope.py:
  * 56-71, 83-108; applied to q and k at rope_unet.py:143-147).  x/y: [rows, ldx] token-major with H heads of width d;

@@ -5,6 +5,8 @@
 // contraction steps and NDT = ceil(DH/32) output tiles (d = 72: 5 and 3 instead of 4.5 and 2.25 -- the MFMAs are not
 // the bound here, the softmax VALU work is, and that does not depend on DH).
 // Replaces F.scaled_dot_product_attention fwd/bwd (reference src/duwu/modules/rope_unet.py:151-153).
+// Query counts: whole 64-row tiles, or (QTAIL instantiations, head dim 40 / 64 / 80, launched for T > 256 with T % 64 != 0) a ragged
+// last tile whose rows at or past T are clamped on load, contribute exact zeros and are never stored.
 //
 // All products use v_mfma_f32_32x32x16_bf16.  Lane maps (cdna_hip_programming.md section 3):
 //   A: lane (r=l&31, h=l>>5) holds A[row r][k=8h+j];  B: holds B[k=8h+j][col r];
@@ -136,8 +138,11 @@ __device__ __forceinline__ uint4 load16_or_zero(const bf16_t* p, bool ok) {
 }
 extern __shared__ __attribute__((aligned(16))) char dyn_smem[];
 
-template <bool BIAS, int DH, bool ROPE = false>
+// QTAIL (T no multiple of 64, launched for T > 256 only): the rows of the last query tile at or past T read row T - 1 (row T
+// of this batch is row 0 of the next one, or nobody's memory) and store nothing.  The key loop does not depend on the query.
+template <bool BIAS, int DH, bool ROPE = false, bool QTAIL = false>
 __global__ void __launch_bounds__(256, 2) attn_fwd_mfma(const MArgs a) {
+  static_assert(!(ROPE && QTAIL), "the RoPE variant takes whole query tiles");
   using G = HeadGeom<DH>;
   constexpr int NB = G::NB, NKS = G::NKS, NDT = G::NDT;
   constexpr int STAGE = 2 * NB * 8192;  // K blocks | V^T blocks
@@ -168,7 +173,10 @@ __global__ void __launch_bounds__(256, 2) attn_fwd_mfma(const MArgs a) {
   if (active) {
 #pragma unroll
     for (int s = 0; s < NKS; ++s) {
-      qf[s] = load16_or_zero(qb + (int64_t)(q0 + r) * a.ldq + 16 * s + 8 * h, 16 * s + 8 * h < DH);
+      if constexpr (QTAIL)
+        qf[s] = load16_or_zero(qb + (int64_t)min(q0 + r, a.T - 1) * a.ldq + 16 * s + 8 * h, 16 * s + 8 * h < DH);
+      else
+        qf[s] = load16_or_zero(qb + (int64_t)(q0 + r) * a.ldq + 16 * s + 8 * h, 16 * s + 8 * h < DH);
       if constexpr (ROPE) qf[s] = rope8(qf[s], a.rope + (int64_t)(q0 + r) * a.ldt + hd * DH + 16 * s + 8 * h);
     }
   }
@@ -287,6 +295,8 @@ __global__ void __launch_bounds__(256, 2) attn_fwd_mfma(const MArgs a) {
   if (active) {
     const float lt = l + __shfl_xor(l, 32, 64);
     const float inv = 1.f / lt;
+    if constexpr (QTAIL)
+      if (q0 + r >= a.T) return;  // this lane's query does not exist (after the last barrier and the last shuffle)
     bf16_t* ob = a.out + (int64_t)b * a.T * a.ldo + hd * DH + (int64_t)(q0 + r) * a.ldo;
 #pragma unroll
     for (int dt = 0; dt < NDT; ++dt)
@@ -320,9 +330,13 @@ __device__ __forceinline__ int off512(int row, int chunk) { return row * 512 + (
 // only dK / dV for its keys (no dS image, no K^T image: 65 KB of LDS, two workgroups per CU); dQ comes from
 // attn_bwd_dq_mfma.  The key blocks of a head sit next to each other in an XCD-aware 1-D grid (they read the same Q / dO).
 // BIAS (key-block variant only): the lane's key bias / scale is the initial value of the S accumulator.
-template <bool DQ, bool BIAS, int DH, bool ROPE = false>
+// QTAIL (key-block variant, T no multiple of 64): the last query tile is staged with its rows at or past T as zeros (Q, dO, O),
+// as copies of row T - 1 in the two transposed images, and with S starting at -inf: P = exp2(-inf) = 0 exactly, dP = 0 - 0, so
+// dS = 0 and such a row adds exact zeros to dK and dV; nothing of it is multiplied by anything but 0.  No read leaves [0, T).
+template <bool DQ, bool BIAS, int DH, bool ROPE = false, bool QTAIL = false>
 __global__ void __launch_bounds__(512, 2) attn_bwd_mfma(const MArgs a) {
   static_assert(!(DQ && BIAS), "a key bias runs through the key-block variant");
+  static_assert(!QTAIL || (!DQ && !ROPE), "a ragged query count runs through the key-block variant");
   static_assert(!ROPE || (DQ && DH == 64), "the RoPE variant is the one-kernel head-dim-64 case");
   static_assert(!DQ || DH == 64, "the one-kernel variant is the head-dim-64 case");
   using G = HeadGeom<DH>;
@@ -410,16 +424,28 @@ __global__ void __launch_bounds__(512, 2) attn_bwd_mfma(const MArgs a) {
   const float inv_scale = 1.f / a.scale;
   auto load_tile = [&](int q0) {
     const int row = tid >> 3, ch = tid & 7;
+    bool rvalid = true;  // QTAIL: the row-major chunks of a row at or past T are zeros
+    if constexpr (QTAIL) rvalid = q0 + row < a.T;
+    constexpr int ALL = 0x7fffffff;  // QTAIL: the transposing stagers clamp to row T - 1
 #pragma unroll
     for (int blk = 0; blk < NB; ++blk) {
       const int col = 64 * blk + 8 * ch;
-      qreg[blk] = load16_or_zero(qb + (int64_t)(q0 + row) * a.ldq + col, col < DH);
+      qreg[blk] = load16_or_zero(qb + (int64_t)(q0 + row) * a.ldq + col, QTAIL ? col < DH && rvalid : col < DH);
       if constexpr (ROPE) qreg[blk] = rope8(qreg[blk], a.rope + (int64_t)(q0 + row) * a.ldt + hd * DH + col);
-      greg[blk] = load16_or_zero(gb + (int64_t)(q0 + row) * a.ldo + col, col < DH);
-      if constexpr (!LEAN) oreg[blk] = load16_or_zero(ob + (int64_t)(q0 + row) * a.ldo + col, col < DH);
-      if (tid < 256) treg[blk].load(qb + 64 * blk, a.ldq, q0, tid, 0x7fffffff, DH - 64 * blk,
+      greg[blk] = load16_or_zero(gb + (int64_t)(q0 + row) * a.ldo + col, QTAIL ? col < DH && rvalid : col < DH);
+      if constexpr (!LEAN) oreg[blk] = load16_or_zero(ob + (int64_t)(q0 + row) * a.ldo + col, QTAIL ? col < DH && rvalid : col < DH);
+      if (tid < 256) treg[blk].load(qb + 64 * blk, a.ldq, q0, tid, QTAIL ? a.T : ALL, DH - 64 * blk,
                                     ROPE ? a.rope + hd * DH + 64 * blk : nullptr, a.ldt);
-      else treg[blk].load(gb + 64 * blk, a.ldo, q0, tid - 256, 0x7fffffff, DH - 64 * blk);
+      else treg[blk].load(gb + 64 * blk, a.ldo, q0, tid - 256, QTAIL ? a.T : ALL, DH - 64 * blk);
+    }
+    if constexpr (QTAIL) {  // S of a row at or past T starts at -inf: P = 0 exactly; its delta is 0
+      if (tid < 64) {
+        const bool lvalid = q0 + tid < a.T;
+        const int lrow = min(q0 + tid, a.T - 1);
+        lreg = lvalid ? -lseb[lrow] * inv_scale : -INFINITY;
+        if constexpr (LEAN) dreg = lvalid ? -a.delta[((int64_t)b * a.H + hd) * a.T + lrow] : 0.f;
+      }
+      return;
     }
     if (tid < 64) lreg = -lseb[q0 + tid] * inv_scale;  // row constant of S, in units of the raw dot product
     if constexpr (LEAN)
@@ -454,7 +480,7 @@ __global__ void __launch_bounds__(512, 2) attn_bwd_mfma(const MArgs a) {
     if (ch == 0) dl[row] = -ds;
   };
 
-  const int nt = a.T / 64;
+  const int nt = QTAIL ? (a.T + 63) / 64 : a.T / 64;
   const int nk32 = a.T / 32;
   const int fr = lane & 15, fq = lane >> 4;
   load_tile(0);
@@ -617,7 +643,9 @@ __global__ void __launch_bounds__(512, 2) attn_bwd_mfma(const MArgs a) {
 //   dQ^T[d][q] += K^T[d][key] . dS^T[key][q]              (dS^T accumulator reused as the B operand, as P^T in forward)
 // so dQ accumulates over all key tiles in the wave's own registers: no atomics, no cross-workgroup reduction.
 // delta[q] = sum_d dO O is formed from the wave's own dO fragments and the matching O chunks.
-template <bool BIAS, int DH>
+// QTAIL (T no multiple of 64): as in the forward kernel, the lanes of the last query tile at or past T read row T - 1 of Q, dO, O
+// and lse, and store neither dq nor delta.
+template <bool BIAS, int DH, bool QTAIL = false>
 __global__ void __launch_bounds__(256, 2) attn_bwd_dq_mfma(const MArgs a) {
   using G = HeadGeom<DH>;
   constexpr int NB = G::NB, NKS = G::NKS, NDT = G::NDT;
@@ -650,17 +678,26 @@ __global__ void __launch_bounds__(256, 2) attn_bwd_dq_mfma(const MArgs a) {
 #pragma unroll
     for (int s = 0; s < NKS; ++s) {
       const bool ok = 16 * s + 8 * h < DH;
-      qf[s] = load16_or_zero(qb + (int64_t)(q0 + r) * a.ldq + 16 * s + 8 * h, ok);
-      gf[s] = load16_or_zero(gb + (int64_t)(q0 + r) * a.ldo + 16 * s + 8 * h, ok);
-      const uint4 of = load16_or_zero(ob + (int64_t)(q0 + r) * a.ldo + 16 * s + 8 * h, ok);
+      uint4 of;
+      if constexpr (QTAIL) {
+        const int qrow = min(q0 + r, a.T - 1);
+        qf[s] = load16_or_zero(qb + (int64_t)qrow * a.ldq + 16 * s + 8 * h, ok);
+        gf[s] = load16_or_zero(gb + (int64_t)qrow * a.ldo + 16 * s + 8 * h, ok);
+        of = load16_or_zero(ob + (int64_t)qrow * a.ldo + 16 * s + 8 * h, ok);
+      } else {
+        qf[s] = load16_or_zero(qb + (int64_t)(q0 + r) * a.ldq + 16 * s + 8 * h, ok);
+        gf[s] = load16_or_zero(gb + (int64_t)(q0 + r) * a.ldo + 16 * s + 8 * h, ok);
+        of = load16_or_zero(ob + (int64_t)(q0 + r) * a.ldo + 16 * s + 8 * h, ok);
+      }
       const bf16x8 gv = *reinterpret_cast<const bf16x8*>(&gf[s]), ov = *reinterpret_cast<const bf16x8*>(&of);
 #pragma unroll
       for (int j = 0; j < 8; ++j) dl += (float)gv[j] * (float)ov[j];
     }
     dl += __shfl_xor(dl, 32, 64);  // the two lane halves hold the two halves of the row
     if constexpr (G::LEAN)  // the dK / dV kernel of this head dim reads delta instead of forming it (launched after this one)
-      if (h == 0) a.delta[((int64_t)b * a.H + hd) * a.T + q0 + r] = dl;
-    lq = a.lse[((int64_t)b * a.H + hd) * a.T + q0 + r] * 1.4426950408889634f;
+      if (QTAIL ? h == 0 && q0 + r < a.T : h == 0) a.delta[((int64_t)b * a.H + hd) * a.T + q0 + r] = dl;
+    if constexpr (QTAIL) lq = a.lse[((int64_t)b * a.H + hd) * a.T + min(q0 + r, a.T - 1)] * 1.4426950408889634f;
+    else lq = a.lse[((int64_t)b * a.H + hd) * a.T + q0 + r] * 1.4426950408889634f;
   }
   f32x16 dq[NDT];
 #pragma unroll
@@ -763,7 +800,7 @@ __global__ void __launch_bounds__(256, 2) attn_bwd_dq_mfma(const MArgs a) {
     if (t + 1 < nt) store_tile((t + 1) & 1);
     __syncthreads();
   }
-  if (active) {
+  if (QTAIL ? active && q0 + r < a.T : active) {
     bf16_t* dqb = a.dq + (int64_t)b * a.T * a.ldq + hd * DH + (int64_t)(q0 + r) * a.ldq;
 #pragma unroll
     for (int dt = 0; dt < NDT; ++dt)
@@ -780,11 +817,17 @@ __global__ void __launch_bounds__(256, 2) attn_bwd_dq_mfma(const MArgs a) {
 }  // namespace
 
 // ------------------------------------------------------------------------------------------- host side
-// head dim 40 / 64 / 72 / 80 / 128, whole 64-row query tiles; any number of keys (ragged key tiles are masked: cross-attention,
-// Tk = 77)
+// head dim 40 / 64 / 72 / 80 / 128; any number of keys (ragged key tiles are masked: cross-attention, Tk = 77); whole 64-row
+// query tiles, or any query count above UWU_ATTN_QTAIL_MIN (the QTAIL kernels: the last tile's rows past Tq are guarded).  Ragged
+// query counts up to 256 stay on the generic kernels: whether they would gain here has not been measured.
+// The QTAIL kernels exist at head dim 40, 64 and 80.  At 72 and 128 the dK / dV kernel (and at 128 the dQ kernel) with the guard
+// needs scratch memory, as the whole-tile ones of those widths already do; a spilling instantiation is not shipped, so ragged query
+// counts of these two widths stay where they were (72: the generic kernels; 128: refused).
+constexpr int UWU_ATTN_QTAIL_MIN = 256;
+constexpr bool qtail_head_dim(int d) { return d == 40 || d == 64 || d == 80; }
 bool uwu_attn_mfma_fwd_ok(int Tq, int Tk, int d, int ldq, int ldk, int ldv, int ldo) {
-  return (d == 40 || d == 64 || d == 72 || d == 80 || d == 128) && Tk >= 1 && Tq % 64 == 0 && ldq % 8 == 0 && ldk % 8 == 0 && ldv % 8 == 0 &&
-         ldo % 8 == 0;
+  return (d == 40 || d == 64 || d == 72 || d == 80 || d == 128) && Tk >= 1 &&
+         (Tq % 64 == 0 || (Tq > UWU_ATTN_QTAIL_MIN && qtail_head_dim(d))) && ldq % 8 == 0 && ldk % 8 == 0 && ldv % 8 == 0 && ldo % 8 == 0;
 }
 bool uwu_attn_mfma_bwd_ok(int Tq, int Tk, int d, int ldq, int ldk, int ldv, int ldo) {
   return uwu_attn_mfma_fwd_ok(Tq, Tk, d, ldq, ldk, ldv, ldo);
@@ -801,53 +844,58 @@ bool allow_lds(K kernel, int bytes, unsigned char* done, const char* what) {
   return false;
 }
 
-template <int DH>
+template <int DH, bool QTAIL>
 int launch_fwd(const MArgs& a, hipStream_t st) {
   constexpr int NB = HeadGeom<DH>::NB;
   constexpr int lds = NB == 1 ? 0 : 2 * 2 * NB * 8192;  // wider heads: the two stages live in dynamic LDS
   static unsigned char done[2][UWU_MAX_DEV];
-  if (lds && !(allow_lds(attn_fwd_mfma<true, DH>, lds, done[0], "attention_fwd(mfma)") &&
-               allow_lds(attn_fwd_mfma<false, DH>, lds, done[1], "attention_fwd(mfma)")))
+  if (lds && !(allow_lds(attn_fwd_mfma<true, DH, false, QTAIL>, lds, done[0], "attention_fwd(mfma)") &&
+               allow_lds(attn_fwd_mfma<false, DH, false, QTAIL>, lds, done[1], "attention_fwd(mfma)")))
     return UWU_ELAUNCH;
   const dim3 grid(((a.T + 127) / 128) * a.B * a.H);
-  if (a.kbias) hipLaunchKernelGGL((attn_fwd_mfma<true, DH>), grid, dim3(256), lds, st, a);
-  else hipLaunchKernelGGL((attn_fwd_mfma<false, DH>), grid, dim3(256), lds, st, a);
+  if (a.kbias) hipLaunchKernelGGL((attn_fwd_mfma<true, DH, false, QTAIL>), grid, dim3(256), lds, st, a);
+  else hipLaunchKernelGGL((attn_fwd_mfma<false, DH, false, QTAIL>), grid, dim3(256), lds, st, a);
+  return UWU_OK;
+}
+
+// the two-kernel backward: dK / dV per block of 256 keys, dQ per tile of 128 queries
+template <int DH, bool BIAS, bool QTAIL>
+int launch_bwd_two(const MArgs& a, hipStream_t st) {
+  constexpr int NB = HeadGeom<DH>::NB;
+  constexpr int lds_kv = bwd_lds_kv(NB);                  // key-block variant: the two staging stages + lse / delta
+  constexpr int lds_dq = NB == 1 ? 0 : 2 * 3 * NB * 8192;
+  static unsigned char done[2][UWU_MAX_DEV];
+  constexpr const char* what = "attention_bwd(mfma)";
+  if (!allow_lds(attn_bwd_mfma<false, BIAS, DH, false, QTAIL>, lds_kv, done[0], what)) return UWU_ELAUNCH;
+  if (lds_dq && !allow_lds(attn_bwd_dq_mfma<BIAS, DH, QTAIL>, lds_dq, done[1], what)) return UWU_ELAUNCH;
+  const dim3 gkv(a.B * a.H * ((a.Tk + 255) / 256)), gq(a.B * a.H * ((a.T + 127) / 128));
+  constexpr bool dq_first = HeadGeom<DH>::LEAN;  // the lean dK / dV kernel reads the delta the dQ pass writes
+  if (dq_first) hipLaunchKernelGGL((attn_bwd_dq_mfma<BIAS, DH, QTAIL>), gq, dim3(256), lds_dq, st, a);
+  hipLaunchKernelGGL((attn_bwd_mfma<false, BIAS, DH, false, QTAIL>), gkv, dim3(512), lds_kv, st, a);
+  if (!dq_first) hipLaunchKernelGGL((attn_bwd_dq_mfma<BIAS, DH, QTAIL>), gq, dim3(256), lds_dq, st, a);
   return UWU_OK;
 }
 
 template <int DH>
 int launch_bwd(const MArgs& a, hipStream_t st) {
-  constexpr int NB = HeadGeom<DH>::NB;
-  constexpr int lds_kv = bwd_lds_kv(NB);                  // key-block variant: the two staging stages + lse / delta
-  constexpr int lds_dq = NB == 1 ? 0 : 2 * 3 * NB * 8192;
-  static unsigned char done[5][UWU_MAX_DEV];
-  constexpr const char* what = "attention_bwd(mfma)";
-  if (DH == 64 && !allow_lds(attn_bwd_mfma<true, false, 64>, BWD_LDS, done[0], what)) return UWU_ELAUNCH;
-  if (!allow_lds(attn_bwd_mfma<false, false, DH>, lds_kv, done[1], what) ||
-      !allow_lds(attn_bwd_mfma<false, true, DH>, lds_kv, done[2], what))
-    return UWU_ELAUNCH;
-  if (lds_dq && !(allow_lds(attn_bwd_dq_mfma<true, DH>, lds_dq, done[3], what) &&
-                  allow_lds(attn_bwd_dq_mfma<false, DH>, lds_dq, done[4], what)))
-    return UWU_ELAUNCH;
-  const dim3 gkv(a.B * a.H * ((a.Tk + 255) / 256)), gq(a.B * a.H * ((a.T + 127) / 128));
-  constexpr bool dq_first = HeadGeom<DH>::LEAN;  // the lean dK / dV kernel reads the delta the dQ pass writes
-  if (a.kbias) {  // biased scores: always the two-kernel form
-    if (dq_first) hipLaunchKernelGGL((attn_bwd_dq_mfma<true, DH>), gq, dim3(256), lds_dq, st, a);
-    hipLaunchKernelGGL((attn_bwd_mfma<false, true, DH>), gkv, dim3(512), lds_kv, st, a);
-    if (!dq_first) hipLaunchKernelGGL((attn_bwd_dq_mfma<true, DH>), gq, dim3(256), lds_dq, st, a);
-    return UWU_OK;
+  if (a.T % 64 != 0) {  // a ragged last query tile (T > 256): always the two-kernel form
+    if constexpr (qtail_head_dim(DH)) {
+      return a.kbias ? launch_bwd_two<DH, true, true>(a, st) : launch_bwd_two<DH, false, true>(a, st);
+    } else {
+      uwu_set_error("attention_bwd(mfma): head dim %d has no kernel for a query count (%d) that is no multiple of 64", DH, a.T);
+      return UWU_EINVAL;
+    }
   }
+  if (a.kbias) return launch_bwd_two<DH, true, false>(a, st);  // biased scores: always the two-kernel form
   if constexpr (DH == 64) {
     if (a.T == a.Tk && a.T <= 256) {
+      static unsigned char done[UWU_MAX_DEV];
+      if (!allow_lds(attn_bwd_mfma<true, false, 64>, BWD_LDS, done, "attention_bwd(mfma)")) return UWU_ELAUNCH;
       hipLaunchKernelGGL((attn_bwd_mfma<true, false, 64>), dim3(a.B * a.H), dim3(512), BWD_LDS, st, a);
       return UWU_OK;
     }
   }
-  // dK / dV per block of 256 keys, dQ per tile of 128 queries
-  if (dq_first) hipLaunchKernelGGL((attn_bwd_dq_mfma<false, DH>), gq, dim3(256), lds_dq, st, a);
-  hipLaunchKernelGGL((attn_bwd_mfma<false, false, DH>), gkv, dim3(512), lds_kv, st, a);
-  if (!dq_first) hipLaunchKernelGGL((attn_bwd_dq_mfma<false, DH>), gq, dim3(256), lds_dq, st, a);
-  return UWU_OK;
+  return launch_bwd_two<DH, false, false>(a, st);
 }
 
 // the instantiated head dims (uwu_attn_mfma_fwd_ok admits exactly these)
@@ -929,7 +977,16 @@ int uwu_attn_mfma_fwd(const void* q, const void* k, const void* v, void* o, floa
   a.q = (const bf16_t*)q; a.k = (const bf16_t*)k; a.v = (const bf16_t*)v; a.out = (bf16_t*)o; a.lse = lse;
   a.kbias = kbias;
   a.B = B; a.T = T; a.Tk = Tk; a.H = H; a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo; a.scale = scale;
-  const int rc = by_head_dim(d, [&](auto dh) { return launch_fwd<decltype(dh)::value>(a, st); });
+  const int rc = by_head_dim(d, [&](auto dh) {
+    constexpr int DH = decltype(dh)::value;
+    if (T % 64 == 0) return launch_fwd<DH, false>(a, st);
+    if constexpr (qtail_head_dim(DH)) {
+      return launch_fwd<DH, true>(a, st);
+    } else {
+      uwu_set_error("attention_fwd(mfma): head dim %d has no kernel for a query count (%d) that is no multiple of 64", DH, T);
+      return UWU_EINVAL;
+    }
+  });
   if (rc != UWU_OK) return rc;
   UWU_LAUNCH_CHECK("attention_fwd(mfma)");
   return UWU_OK;

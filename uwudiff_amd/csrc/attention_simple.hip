@@ -316,6 +316,16 @@ int uwu_attn_mfma_fwd(const void* q, const void* k, const void* v, void* o, floa
 int uwu_attn_mfma_bwd(const void* q, const void* k, const void* v, const void* o, const void* dO, const float* lse,
                       float* delta, const float* kbias, void* dq, void* dk, void* dv, int B, int T, int Tk, int H,
                       int d, int ldq, int ldk, int ldv, int ldo, float scale, hipStream_t st);
+// The one rule that picks the kernels: bf16 on a shape the MFMA kernels admit.  The dispatch adds the 16-byte alignment of the
+// pointers; uwu_attention_route answers for aligned tensors.
+static bool mfma_route(bool bwd, int Tq, int Tk, int d, int ldq, int ldk, int ldv, int ldo, int dtype) {
+  if (dtype != UWU_BF16 || Tq < 1) return false;
+  return bwd ? uwu_attn_mfma_bwd_ok(Tq, Tk, d, ldq, ldk, ldv, ldo) : uwu_attn_mfma_fwd_ok(Tq, Tk, d, ldq, ldk, ldv, ldo);
+}
+extern "C" int uwu_attention_route(int pass, int Tq, int Tk, int d, int ldq, int ldk, int ldv, int ldo, int dtype) {
+  return mfma_route(pass != 0, Tq, Tk, d, ldq, ldk, ldv, ldo, dtype) ? 1 : 0;
+}
+
 static int check_common(const void* q, const void* k, const void* v, int B, int Tq, int Tk, int H, int d, int ldq,
                         int ldk, int ldv, int ldo, int dtype) {
   UWU_CHECK_ARG(q && k && v, "attention: null pointer");
@@ -336,7 +346,7 @@ static int attention_fwd_impl(const void* q, const void* k, const void* v, void*
   if (rc) return rc;
   UWU_CHECK_ARG(o && lse, "attention_fwd: null output");
   UWU_CHECK_ARG(scale > 0.f, "attention: scale must be positive");
-  if (dtype == UWU_BF16 && uwu_attn_mfma_fwd_ok(Tq, Tk, d, ldq, ldk, ldv, ldo) &&
+  if (mfma_route(false, Tq, Tk, d, ldq, ldk, ldv, ldo, dtype) &&
       (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)o) & 15) == 0) {
     UwuProfScope prof(stream);
     rc = uwu_attn_mfma_fwd(q, k, v, o, lse, kbias, B, Tq, Tk, H, d, ldq, ldk, ldv, ldo, scale, (hipStream_t)stream);
@@ -359,7 +369,7 @@ static int attention_bwd_impl(const void* q, const void* k, const void* v, const
   if (rc) return rc;
   UWU_CHECK_ARG(o && dO && lse && delta && dq && dk && dv, "attention_bwd: null pointer");
   UWU_CHECK_ARG(scale > 0.f, "attention: scale must be positive");
-  if (dtype == UWU_BF16 && uwu_attn_mfma_bwd_ok(Tq, Tk, d, ldq, ldk, ldv, ldo) &&
+  if (mfma_route(true, Tq, Tk, d, ldq, ldk, ldv, ldo, dtype) &&
       (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)o | (uintptr_t)dO | (uintptr_t)dq | (uintptr_t)dk |
         (uintptr_t)dv) & 15) == 0) {
     UwuProfScope prof(stream);

@@ -139,6 +139,7 @@ _SIGS = {
     "uwu_attention_bwd": (c_int, [P] * 10 + [c_int] * 9 + [c_float, c_int, P]),
     "uwu_attention_bias_fwd": (c_int, [P] * 6 + [c_int] * 9 + [c_float, c_int, P]),
     "uwu_attention_bias_bwd": (c_int, [P] * 11 + [c_int] * 9 + [c_float, c_int, P]),
+    "uwu_attention_route": (c_int, [c_int] * 9),
     "uwu_axial_rope_fwd": (c_int, [P, P, P, P, P, c_int64, c_int, c_int, c_int, c_int, P]),
     "uwu_axial_rope_bwd": (c_int, [P, P, P, P, P, P, P, P, c_int64, c_int, c_int, c_int, c_int, P]),
     "uwu_axial_rope_bwd_shared": (c_int, [P, P, P, c_int, P, P, P, P, P, c_int64, c_int, c_int, c_int, c_int, P]),

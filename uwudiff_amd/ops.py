@@ -106,6 +106,15 @@ def attention_bwd(q, k, v, o, do, lse, dq, dk, dv, B, Tq, Tk, H, d, scale=None, 
     return dq, dk, dv
 
 
+def attention_route(Tq, Tk, d, ldq=None, ldk=None, ldv=None, ldo=None, dtype=torch.bfloat16, backward=False):
+    """True where ``attention_fwd`` / ``attention_bwd`` run the MFMA kernels on this shape, False where the generic ones: the
+    predicate of the dispatch itself (``uwu_attention_route``), asked on the host -- no GPU needed.  Strides default to one head's
+    width; 16-byte-aligned tensors are assumed."""
+    ld = [int(d if x is None else x) for x in (ldq, ldk, ldv, ldo)]
+    dt = {torch.float32: L.F32, torch.bfloat16: L.BF16}[dtype]
+    return bool(L.load().uwu_attention_route(int(bool(backward)), int(Tq), int(Tk), int(d), *ld, dt))
+
+
 def colsum(x, out=None, accumulate=False):
     M, N = x.shape
     if out is None:
