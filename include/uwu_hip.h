@@ -262,6 +262,66 @@ int uwu_adamw_fp16_step(float* p, float* g, void* m16, void* v16, void* p_bf16, 
  * element alignment. */
 int uwu_param_decay(float* p, void* p_bf16, int64_t n, double factor, void* stream);
 
+/* prodigyopt.Prodigy (Mishchenko & Defazio, "Prodigy: An Expeditiously Adaptive Parameter-Free Learner") on flat buffers: a
+ * step is uwu_prodigy_stats per chunk, then uwu_prodigy_finalize, then uwu_prodigy_apply, all on one stream, nothing read back.
+ * With g = g * pre_scale * clip[1] (clip may be NULL; the fp32 factor of uwu_adamw_step), the package's step is
+ *   beta3 = beta3 or sqrt(beta2) ; bc = sqrt(1 - beta2^(k+1)) / (1 - beta1^(k+1)) if use_bias_correction else 1
+ *   dlr   = d * lr * bc                                                        (the OLD d)
+ *   if weight_decay != 0 and not decouple:  g += weight_decay * p
+ *   d_numerator = beta3 * d_numerator + (d/d0) * dlr * sum_i g_i (p0_i - p_i)
+ *   exp_avg     = beta1 * exp_avg    + d * (1-beta1) * g
+ *   exp_avg_sq  = beta2 * exp_avg_sq + d*d * (1-beta2) * g*g
+ *   s           = beta3 * s + (d/d0) * (d if safeguard_warmup else dlr) * g
+ *   d_denom     = sum_i |s_i|
+ *   if d_denom == 0:  return              (p, the shadow and k keep their values)
+ *   d_hat = d_coef * d_numerator / d_denom ; if d == d0: d = max(d, d_hat)
+ *   d_max = max(d_max, d_hat) ; d = min(d_max, d * growth_rate)
+ *   if weight_decay != 0 and decouple:  p *= 1 - weight_decay * dlr
+ *   p -= dlr * exp_avg / (sqrt(exp_avg_sq) + d * eps)                          (the OLD dlr, the NEW d)
+ *   k += 1
+ * lr == 0 skips the moments, s and both sums as the package does (d_numerator still decays; d_denom is 0: the early return).
+ *
+ * scalars: UWU_PRODIGY_SCALARS doubles on the device, 8-byte aligned, in the order of the UWU_PRODIGY_* indices; a fresh block
+ * is {d0, d0, 0, 0, 0, 0, 0, 0}.  beta3 is passed resolved (never 0 for "None").  The hyper-parameters are doubles: 1 - beta is
+ * formed in double on the host (see uwu_lion_step), and everything derived from d on the device in double. */
+#define UWU_PRODIGY_SCALARS 8
+#define UWU_PRODIGY_D 0           /* the step size estimate */
+#define UWU_PRODIGY_D_MAX 1
+#define UWU_PRODIGY_D_NUMERATOR 2
+#define UWU_PRODIGY_D_DENOM 3     /* of the last step */
+#define UWU_PRODIGY_D_HAT 4       /* of the last step that did not return early */
+#define UWU_PRODIGY_K 5           /* steps taken (early returns not counted) */
+#define UWU_PRODIGY_SKIPPED 6     /* 1 when the last step returned early (d_denom == 0), else 0 */
+#define UWU_PRODIGY_DLR 7         /* the last step's dlr (its OLD d): what uwu_prodigy_apply moves p by */
+
+/* Workgroups (= workspace slots) uwu_prodigy_stats uses for n elements: a function of n alone.  0 for n <= 0. */
+int uwu_prodigy_stats_blocks(int64_t n);
+
+/* The statistics pass over one chunk of n elements: updates exp_avg, exp_avg_sq and s in place from the block's d and k, leaves
+ * g zeroed when zero_grad, and writes one partial of sum g (p0 - p) and one of sum |s| per workgroup to
+ * ws[2 * (slot0 + b)], ws[2 * (slot0 + b) + 1], b < uwu_prodigy_stats_blocks(n): slots of their own, no atomics.  Products,
+ * p0 - p and the sums are formed in double; each stored moment is rounded to fp32 once.  p and p0 are only read.  ws holds
+ * 2 * ws_slots doubles; slot0 + blocks > ws_slots is refused.  The six buffers 16-byte aligned, scalars and ws 8-byte aligned,
+ * n > 0.  24 B read + 12 B written per parameter (+ 4 B for the zeroed gradient). */
+int uwu_prodigy_stats(const float* p, float* g, const float* p0, float* exp_avg, float* exp_avg_sq, float* s, int64_t n,
+                      const double* scalars, double* ws, int64_t ws_slots, int64_t slot0, double lr, double beta1, double beta2,
+                      double beta3, double weight_decay, int decouple, double d0, int use_bias_correction, int safeguard_warmup,
+                      float pre_scale, const float* clip, int zero_grad, void* stream);
+
+/* One workgroup: adds the partials of slots [0, nslots) in slot order in double (bit-identical run to run at a fixed chunking)
+ * and applies the scalar recurrence above to the block: d_numerator, d_denom, dlr always; d, d_max, d_hat, k and skipped = 0
+ * unless d_denom == 0 (then skipped = 1 and nothing else).  One thread writes.  lr, betas and use_bias_correction as given to
+ * uwu_prodigy_stats in this step. */
+int uwu_prodigy_finalize(double* scalars, const double* ws, int64_t nslots, double lr, double beta1, double beta2, double beta3,
+                         double d0, double d_coef, double growth_rate, int use_bias_correction, void* stream);
+
+/* The update over the whole buffer, from the block uwu_prodigy_finalize left: the decoupled decay and
+ * p -= dlr * exp_avg / (sqrt(exp_avg_sq) + d * eps) in fp32 (dlr, d * eps and 1 - weight_decay * dlr rounded once from double),
+ * p_bf16 (may be NULL) refreshed as uwu_cast_f32_to_bf16 rounds.  Does nothing at all when skipped is set.  p, exp_avg,
+ * exp_avg_sq 16-byte aligned, p_bf16 8-byte aligned, n > 0.  12 B read + 4 B written per parameter (+ 2 B for the shadow). */
+int uwu_prodigy_apply(float* p, const float* exp_avg, const float* exp_avg_sq, void* p_bf16, int64_t n, const double* scalars,
+                      double eps, double weight_decay, int decouple, void* stream);
+
 /* Weight averaging on flat buffers (torch.optim.swa_utils.AveragedModel as lightning.pytorch.callbacks.WeightAveraging /
  * EMAWeightAveraging drive it; uwudiff_amd/averaging.py):
  *   avg[i] = fma(keep, avg[i], take * p[i])      fp32: two roundings per element, 8 B read and 4 B written per parameter

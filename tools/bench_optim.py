@@ -1,11 +1,13 @@
-"""The three flat-buffer update kernels (AdamW, Lion, AdamWFP16: uwudiff_amd/csrc/optimizer.hip) alone, with the bf16 shadow and
-``zero_grad`` on, at DiT-S/2's parameter count and at the SDXL-shape UNet's 2.57 G: ms per launch, bytes moved per parameter
-and GB/s, and the optimizer-state bytes of the SDXL-shape UNet under each optimizer.  One JSON line.  DESIGN.md section 4.28.
+"""The flat-buffer update kernels (AdamW, Lion, AdamWFP16 and Prodigy's three: uwudiff_amd/csrc/optimizer.hip) alone, with the bf16
+shadow and ``zero_grad`` on, at DiT-S/2's parameter count and at the SDXL-shape UNet's 2.57 G: ms per launch, bytes moved per
+parameter and GB/s, and the optimizer-state bytes of the SDXL-shape UNet under each optimizer.  Prodigy is shown as its statistics
+pass, its one-workgroup finalize and its apply pass separately, and as the whole step (the three on one stream), next to the AdamW
+kernel of the same run.  One JSON line.  DESIGN.md sections 4.28 and 4.36.
 
     python tools/bench_optim.py [--sizes 32966464,2570000000] [--reps 5] [--warmup 3]
 
 Bytes per parameter are derived from the update rule (reads + writes of p, g and the state, + 2 for the shadow, + 4 for the zeroed
-gradient); the times are device events around a window of launches, the three kernels alternating inside every repetition."""
+gradient); the times are device events around a window of launches, the kernels alternating inside every repetition."""
 import argparse
 import json
 import os
@@ -18,9 +20,16 @@ DIT_S2, SDXL_UNET = 32_966_464, 2_570_000_000
 # bytes per parameter: (read + written by the update rule, optimizer state held)
 KERNELS = {"adamw": (16 + 12, 8), "lion": (12 + 8, 4), "adamw_fp16": (12 + 8, 4)}
 EXTRA = 2 + 4  # bf16 shadow written, consumed gradient zeroed
+# Prodigy's passes: bytes per parameter with the extras (statistics: p, g, p0, exp_avg, exp_avg_sq, s read, the three moments
+# written, + 4 for the zeroed gradient; apply: p, exp_avg, exp_avg_sq read, p written, + 2 for the shadow); 16 B of state
+PRODIGY = {"prodigy_stats": 24 + 12 + 4, "prodigy_finalize": 0, "prodigy_apply": 12 + 4 + 2}
+PRODIGY["prodigy_step"] = sum(PRODIGY.values())
+PRODIGY_STATE = 16  # exp_avg, exp_avg_sq, s, p0
 
 
 def bench_size(n, reps, warmup):
+    import math
+
     import torch
 
     from uwudiff_amd import lib as L
@@ -40,6 +49,23 @@ def bench_size(n, reps, warmup):
         "adamw_fp16": lambda k: L.call("uwu_adamw_fp16_step", L.ptr(p), L.ptr(g), L.ptr(st["adamw_fp16"][0]),
                                        L.ptr(st["adamw_fp16"][1]), L.ptr(shadow), n, 1e-6, 0.9, 0.999, 1e-8, k, 1.0, None, 1, s),
     }
+    # Prodigy on moments of its own, with the demo config's options (bias correction, safeguard, decoupled decay)
+    pm, pv, ps, p0 = f32().zero_(), f32().zero_(), f32().zero_(), p.clone()
+    scal = torch.tensor([1e-6, 1e-6, 0, 0, 0, 0, 0, 0], dtype=torch.float64, device=dev)
+    blocks = L.load().uwu_prodigy_stats_blocks(n)
+    ws = torch.zeros(2 * blocks, dtype=torch.float64, device=dev)
+    b3 = math.sqrt(0.999)
+    launch["prodigy_stats"] = lambda k: L.call(
+        "uwu_prodigy_stats", L.ptr(p), L.ptr(g), L.ptr(p0), L.ptr(pm), L.ptr(pv), L.ptr(ps), n, L.ptr(scal), L.ptr(ws), blocks, 0,
+        1.0, 0.9, 0.999, b3, 0.01, 1, 1e-6, 1, 1, 1.0, None, 1, s)
+    launch["prodigy_finalize"] = lambda k: L.call("uwu_prodigy_finalize", L.ptr(scal), L.ptr(ws), blocks, 1.0, 0.9, 0.999, b3,
+                                                  1e-6, 1.0, float("inf"), 1, s)
+    launch["prodigy_apply"] = lambda k: L.call("uwu_prodigy_apply", L.ptr(p), L.ptr(pm), L.ptr(pv), L.ptr(shadow), n, L.ptr(scal),
+                                               1e-8, 0.01, 1, s)
+    launch["prodigy_step"] = lambda k: (launch["prodigy_stats"](k), launch["prodigy_finalize"](k), launch["prodigy_apply"](k))
+    # one whole Prodigy step while g is still nonzero (every kernel leaves it zeroed): s is nonzero from here on, so no later step
+    # returns early and the apply pass does its full work in every window (checked below)
+    launch["prodigy_step"](0)
     iters = max(4, min(200, int(2e11 / (34 * n))))  # a window of roughly 0.2 GB/param-byte: tens of ms at either size
     for k in range(1, warmup + 1):
         for fn in launch.values():
@@ -59,10 +85,14 @@ def bench_size(n, reps, warmup):
     for name, times in ms.items():
         times = sorted(times)
         med = times[len(times) // 2]
-        bpp = KERNELS[name][0] + EXTRA
+        bpp = KERNELS[name][0] + EXTRA if name in KERNELS else PRODIGY[name]
         out[name] = {"ms": round(med, 4), "ms_min": round(times[0], 4), "ms_max": round(times[-1], 4),
                      "bytes_per_param": bpp, "GBps": round(bpp * n / med / 1e6, 1),
                      "GBps_min": round(bpp * n / times[-1] / 1e6, 1), "GBps_max": round(bpp * n / times[0] / 1e6, 1)}
+    if scal.tolist()[6] != 0.0:
+        raise SystemExit("bench_optim.py: Prodigy's last step returned early (d_denom == 0): its apply pass did no work")
+    for name in ("prodigy_stats", "prodigy_apply"):  # plain streams: to be judged against the AdamW kernel of this run
+        out[name]["GBps_vs_adamw"] = round(out[name]["GBps"] / out["adamw"]["GBps"], 3)
     return {"n": n, "launches_per_window": iters, "reps": reps, "kernels": out}
 
 
@@ -77,11 +107,12 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("bench_optim.py measures on the GPU; there is no CPU path")
     res = {"sizes": [bench_size(int(n), a.reps, a.warmup) for n in a.sizes.split(",")],
-           "state_bytes_sdxl_unet": {name: state * SDXL_UNET for name, (_, state) in KERNELS.items()},
+           "state_bytes_sdxl_unet": {**{name: state * SDXL_UNET for name, (_, state) in KERNELS.items()},
+                                     "prodigy": PRODIGY_STATE * SDXL_UNET},
            "weights_bytes_sdxl_unet": 4 * SDXL_UNET}
     for r in res["sizes"]:
         for name, k in r["kernels"].items():
-            print(f"n = {r['n']:>13,}  {name:<11} {k['ms']:9.4f} ms ({k['ms_min']:.4f} .. {k['ms_max']:.4f})  "
+            print(f"n = {r['n']:>13,}  {name:<16} {k['ms']:9.4f} ms ({k['ms_min']:.4f} .. {k['ms_max']:.4f})  "
                   f"{k['bytes_per_param']} B/param  {k['GBps']:8.1f} GB/s ({k['GBps_min']:.1f} .. {k['GBps_max']:.1f})")
     for name, b in res["state_bytes_sdxl_unet"].items():
         print(f"SDXL-shape UNet optimizer state under {name:<11}: {b / 1e9:6.2f} GB (weights {4 * SDXL_UNET / 1e9:.2f} GB)")

@@ -26,6 +26,7 @@ ALIASES = {
     "torchvision.transforms.Resize": "uwudiff_amd.transforms.Resize",
     "torchvision.transforms.ToTensor": "uwudiff_amd.transforms.ToTensor",
     "lion_pytorch.Lion": "uwudiff_amd.optim.FusedLion",  # the commented alternative of the reference's training YAMLs
+    "prodigyopt.Prodigy": "uwudiff_amd.optim.FusedProdigy",  # parameter-free step size
     "lightning.pytorch.callbacks.ModelCheckpoint": "uwudiff_amd.engine.ModelCheckpoint",
     "lightning.pytorch.callbacks.LearningRateMonitor": "uwudiff_amd.engine.LearningRateMonitor",
     "lightning.pytorch.callbacks.WeightAveraging": "uwudiff_amd.averaging.WeightAveraging",  # on the flat buffer

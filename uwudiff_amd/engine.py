@@ -115,8 +115,15 @@ class ModelCheckpoint:
 
 
 class LearningRateMonitor:
+    """Lightning's callback of that name: `lr` is in every logged record already; with this callback present, an optimizer that
+    estimates its own step size (``FusedProdigy.d``: a device scalar, a host synchronisation to read) has it logged next to `lr`,
+    at the logging interval only."""
+
     def __init__(self, **kw):
         self.kw = kw
+
+    def extra(self, opt):
+        return {"d": float(opt.d)} if hasattr(opt, "d") else {}
 
 
 class GradualWarmupScheduler:
@@ -564,6 +571,9 @@ class Fitter:
                 if self.global_step % self.log_every_n_steps == 0 or self.fast_dev_run or done:
                     rec = {"step": self.global_step, "loss": float(loss.detach()), "ema_loss": float(module.ema_loss),
                            "lr": opt.param_groups[0]["lr"], "elapsed_s": round(time.time() - t0, 3)}
+                    for cb in self.callbacks:
+                        if isinstance(cb, LearningRateMonitor):
+                            rec.update(cb.extra(opt))
                     if n_acc > 1:
                         rec["accum"] = window  # micro-batches in this window (`loss` is the last one's, as Lightning's on_step log)
                     self.history.append(rec)

@@ -84,6 +84,11 @@ _SIGS = {
     "uwu_adamw_fp16_step": (c_int, [P, P, P, P, P, c_int64, c_double, c_double, c_double, c_double, c_int, c_float, P,
                                     c_int, P]),
     "uwu_param_decay": (c_int, [P, P, c_int64, c_double, P]),
+    "uwu_prodigy_stats_blocks": (c_int, [c_int64]),
+    "uwu_prodigy_stats": (c_int, [P] * 6 + [c_int64, P, P, c_int64, c_int64] + [c_double] * 5 + [c_int, c_double, c_int, c_int,
+                                  c_float, P, c_int, P]),
+    "uwu_prodigy_finalize": (c_int, [P, P, c_int64] + [c_double] * 7 + [c_int, P]),
+    "uwu_prodigy_apply": (c_int, [P, P, P, P, c_int64, P, c_double, c_double, c_int, P]),
     "uwu_ema_update": (c_int, [P, P, c_int64, c_float, c_float, P]),
     "uwu_ema_swap": (c_int, [P, P, P, c_int64, c_int, P]),
     "uwu_cast_f32_to_bf16": (c_int, [P, P, c_int64, P]),

@@ -3,7 +3,8 @@
 ``FusedAdamW`` mirrors ``torch.optim.AdamW`` single-tensor semantics (the reference instantiates ``torch.optim.AdamW`` from
 YAML, reference src/duwu/trainer/trainer.py:52-74, configs/demo_training_latent.yaml:30-39), ``FusedLion`` is
 ``lion_pytorch.Lion`` (the commented alternative of the reference's training YAMLs) and ``FusedAdamWFP16`` the reference's own
-``duwu.trainer.optimizers.AdamWFP16`` (src/duwu/trainer/optimizers.py).  ``FlatFusedOptimizer`` is what they share and what
+``duwu.trainer.optimizers.AdamWFP16`` (src/duwu/trainer/optimizers.py); ``FusedProdigy`` is ``prodigyopt.Prodigy``, whose step
+size comes from two sums over all parameters kept on the device.  ``FlatFusedOptimizer`` is what they share and what
 the trainer's fused path asks for: Lightning's ``gradient_clip_val`` (global L2 norm, demo_training.yaml:12) as a device
 coefficient, one launch per flat parameter buffer (or per reduced chunk of it), the consumed gradient zeroed and the bf16
 shadow of the parameters (MFMA operands) refreshed by the same kernel.
@@ -220,6 +221,117 @@ class FusedAdamWFP16(FlatFusedOptimizer):
                 sp = shadow.data_ptr() + 2 * off if shadow is not None else None
                 L.call("uwu_param_decay", p.data_ptr() + 4 * off, sp, ln, 1.0 - acc[i], L.stream())
                 acc[i] -= acc[i]
+
+
+class FusedProdigy(FlatFusedOptimizer):
+    """``prodigyopt.Prodigy`` (Mishchenko & Defazio, "Prodigy: An Expeditiously Adaptive Parameter-Free Learner") on a flat
+    buffer: Adam whose step size ``d`` is estimated from two sums over all parameters, ``sum g.(p0 - p)`` and ``sum |s|``.  The rule
+    is written out at ``uwu_prodigy_stats`` (include/uwu_hip.h).  The package reads both sums back with an ``.item()`` per parameter
+    tensor; here a step is ``uwu_prodigy_stats`` per chunk (``_launch``: the moments and one partial of each sum per workgroup, still
+    behind ``before_chunk`` and so overlapped with the gradient exchange), then ``uwu_prodigy_finalize`` (one workgroup: the sums in
+    slot order and the scalar recurrence) and ``uwu_prodigy_apply`` over the whole buffer (``_finish``).  Nothing is read back.
+
+    State per parameter: ``exp_avg``, ``exp_avg_sq``, ``s``, ``p0`` (the parameters at the first step) and ``scalars``, the device
+    block ``SCALARS`` names.  The block holds doubles and is kept as their fp32 words: ``load_state_dict`` casts every state tensor
+    to the parameter's dtype, which leaves fp32 words bit for bit and would round a float64 tensor.  ``state_dict()`` and the
+    checkpoint path carry it like any moment: 16 B of state per parameter.
+
+    One flat parameter buffer (``d`` is one number for all parameters; several buffers would need their sums added: not built), one
+    ``lr``.  ``fsdp_in_use`` is accepted for the package's signature and ignored; ``slice_p`` is not implemented.
+
+    World > 1: every rank holds the same reduced gradient and the same parameters, so with the same chunking every rank adds the
+    same partials in the same order and ``d`` is bit-identical on all of them: no extra collective."""
+
+    SCALARS = ("d", "d_max", "d_numerator", "d_denom", "d_hat", "k", "skipped", "dlr")  # the UWU_PRODIGY_* indices
+
+    def __init__(self, params, lr=1.0, betas=(0.9, 0.999), beta3=None, eps=1e-8, weight_decay=0, decouple=True,
+                 use_bias_correction=False, safeguard_warmup=False, d0=1e-6, d_coef=1.0, growth_rate=float("inf"),
+                 fsdp_in_use=False):
+        if not 0.0 < d0:
+            raise ValueError(f"Invalid d0 value: {d0}")
+        if not 0.0 < lr:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if not 0.0 < eps:
+            raise ValueError(f"Invalid epsilon value: {eps}")
+        if not 0.0 <= betas[0] < 1.0:
+            raise ValueError(f"Invalid beta parameter at index 0: {betas[0]}")
+        if not 0.0 <= betas[1] < 1.0:
+            raise ValueError(f"Invalid beta parameter at index 1: {betas[1]}")
+        super().__init__(params, dict(lr=lr, betas=tuple(betas), beta3=beta3, eps=eps, weight_decay=weight_decay,
+                                      decouple=bool(decouple), use_bias_correction=bool(use_bias_correction),
+                                      safeguard_warmup=bool(safeguard_warmup), d0=d0, d_coef=d_coef, growth_rate=growth_rate,
+                                      fsdp_in_use=fsdp_in_use))
+        if sum(len(g["params"]) for g in self.param_groups) != 1:
+            raise NotImplementedError("FusedProdigy expects one flat parameter buffer (d is estimated over all parameters)")
+        self._partials = {}  # device -> float64 workspace: a pair of partial sums per workgroup of the step's launches
+        self._slots = 0  # slots the launches of the current step have written
+
+    def _init_state(self, p, st):
+        d0 = float(self.param_groups[0]["d0"])
+        st["exp_avg"] = _zeros_like(p.data)
+        st["exp_avg_sq"] = _zeros_like(p.data)
+        st["s"] = _zeros_like(p.data)
+        st["p0"] = p.data.clone()
+        block = torch.tensor([d0, d0] + [0.0] * (len(self.SCALARS) - 2), dtype=torch.float64)
+        st["scalars"] = block.view(torch.float32).to(p.device)
+
+    def _workspace(self, device, slots):
+        """the partials' workspace with room for ``slots`` slots; grown on the stream (what this step has written moves along)"""
+        ws = self._partials.get(device)
+        if ws is None or ws.numel() < 2 * slots:
+            grown = torch.empty(2 * max(slots, 0 if ws is None else ws.numel()), device=device, dtype=torch.float64)
+            if ws is not None and self._slots:
+                grown[:2 * self._slots].copy_(ws[:2 * self._slots])
+            self._partials[device] = ws = grown
+        return ws
+
+    @staticmethod
+    def _beta3(group):
+        return float(group["beta3"]) if group["beta3"] is not None else math.sqrt(group["betas"][1])
+
+    def _launch(self, group, st, p_ptr, g_ptr, shadow_ptr, off, ln, pre_scale, clip_ptr, zero_grad):
+        b1, b2 = group["betas"]
+        blocks = L.load().uwu_prodigy_stats_blocks(ln)
+        ws = self._workspace(st["s"].device, self._slots + blocks)
+        L.call("uwu_prodigy_stats", p_ptr, g_ptr, L.ptr(st["p0"]) + 4 * off, L.ptr(st["exp_avg"]) + 4 * off,
+               L.ptr(st["exp_avg_sq"]) + 4 * off, L.ptr(st["s"]) + 4 * off, ln, L.ptr(st["scalars"]), L.ptr(ws), ws.numel() // 2,
+               self._slots, float(group["lr"]), b1, b2, self._beta3(group), float(group["weight_decay"]), int(group["decouple"]),
+               float(group["d0"]), int(group["use_bias_correction"]), int(group["safeguard_warmup"]), pre_scale, clip_ptr,
+               zero_grad, L.stream())
+        self._slots += blocks
+
+    def _finish(self, group, p, st, shadow):
+        b1, b2 = group["betas"]
+        slots, self._slots = self._slots, 0
+        L.call("uwu_prodigy_finalize", L.ptr(st["scalars"]), L.ptr(self._partials[p.device]), slots, float(group["lr"]), b1, b2,
+               self._beta3(group), float(group["d0"]), float(group["d_coef"]), float(group["growth_rate"]),
+               int(group["use_bias_correction"]), L.stream())
+        L.call("uwu_prodigy_apply", L.ptr(p.data), L.ptr(st["exp_avg"]), L.ptr(st["exp_avg_sq"]), L.ptr(shadow), p.numel(),
+               L.ptr(st["scalars"]), float(group["eps"]), float(group["weight_decay"]), int(group["decouple"]), L.stream())
+
+    @torch.no_grad()
+    def step(self, *args, **kwargs):
+        self._slots = 0  # (a step that raised between its launches leaves no slots behind)
+        for group in self.param_groups:  # the entry points take raw pointers: the shadow's dtype is checked here, before any launch
+            for p in group["params"]:
+                shadow = getattr(p, "_uwu_bf16_shadow", None)
+                if shadow is not None and shadow.numel() == p.numel() and shadow.dtype != torch.bfloat16:
+                    raise L.UwuError(f"uwu_prodigy_apply: the shadow must be bfloat16, got {shadow.dtype}")
+        return super().step(*args, **kwargs)
+
+    def scalars(self):
+        """The scalar block as a dict of python floats, keyed by ``SCALARS``.  A host synchronisation: for logging and tests,
+        never inside the step.  Before the first step: the fresh block."""
+        for st in self.state.values():
+            if "scalars" in st:
+                return dict(zip(self.SCALARS, st["scalars"].view(torch.float64).tolist()))
+        d0 = float(self.param_groups[0]["d0"])
+        return dict(zip(self.SCALARS, [d0, d0] + [0.0] * (len(self.SCALARS) - 2)))
+
+    @property
+    def d(self):
+        """The current step size estimate.  Reads the device scalar: a host synchronisation, meant for logging only."""
+        return self.scalars()["d"]
 
 
 def cosine_lr(base_lr, step, T_max, eta_min):
