@@ -657,6 +657,50 @@ int uwu_clip_score_accum(const void* image_embeds, const void* text_embeds, floa
  * the concatenation gives.  B > 0, 1 <= n_steps <= 65536.  No host synchronisation. */
 int uwu_timestep_stats_accum(const float* losses, const void* timesteps, int t_dtype, const float* loss_mean, int B, int n_steps,
                              double* stats, double* totals, void* stream);
+
+/* ------------------------------------------------------------------ InceptionV3 feature extractor and FID statistics (4.37) */
+/* Forward convolution on channels-last activations, y = [relu](conv(x, w) + bias), as an implicit GEMM on the MFMA units (no column
+ * matrix in memory) in both dtypes (bf16: v_mfma_f32_16x16x32_bf16; fp32: v_mfma_f32_16x16x4_f32, the parity mode).  Kernel (KH, KW)
+ * one of 1x1, 3x3, 5x5, 1x7, 7x1, 1x3, 3x1; stride 1 or 2; zero padding (ph, pw) below the kernel size.  x: rows of ldx elements, one
+ * per input pixel (b, iy, ix), the convolution reading channels xoff .. xoff + C - 1 of each; y: rows of ldy elements, one per output
+ * pixel, channels yoff .. yoff + Cout - 1 written and every other element of the row left alone (a branch writes its slice of a
+ * concatenation); Ho = (H + 2 ph - KH) / stride + 1, Wo likewise.  w [Cout][KH][KW][C] in `dtype`, bias fp32 [Cout] or NULL.  C,
+ * Cout, ldx, ldy, xoff, yoff multiples of 8 (48 and 80 channels need no padding), B Ho Wo arbitrary (a true M tail), 16-byte aligned
+ * pointers.  uwu_conv2d_ok: 1 where the shape is built, 0 where uwu_conv2d_fwd refuses it (before any launch, y untouched);
+ * uwu_conv2d_ws_bytes: the workspace the shape needs -- 0 for every shape today, the argument is there for an explicit route.
+ * Reference: the BasicConv2d of torch-fidelity's FeatureExtractorInceptionV3, which torchmetrics' FrechetInceptionDistance wraps
+ * (reference src/duwu/metrics/fid.py:5). */
+int uwu_conv2d_ok(int B, int H, int W, int C, int Cout, int KH, int KW, int stride, int ph, int pw, int ldx, int xoff, int ldy, int yoff,
+                  int dtype);
+size_t uwu_conv2d_ws_bytes(int B, int H, int W, int C, int Cout, int KH, int KW, int stride, int ph, int pw, int ldx, int xoff, int ldy,
+                           int yoff, int dtype);
+int uwu_conv2d_fwd(const void* x, const void* w, const float* bias, void* y, int B, int H, int W, int C, int Cout, int KH, int KW,
+                   int stride, int ph, int pw, int ldx, int xoff, int ldy, int yoff, int relu, int dtype, void* ws, size_t ws_bytes,
+                   void* stream);
+/* The A operand of Conv2d_1a_3x3 (3 -> 32, 3x3, stride 2, no padding).  images [B, 3, H, W] contiguous: uint8 (in_u8 != 0) taken as
+ * they are, or fp32 in [0, 1] turned into  v = trunc(clamp(x, 0, 1) * 255)  (the product rounded to fp32, then truncated; NaN -> 0);
+ * then  (v - 128) / 128,  exact in bf16.  out [B Ho Wo, 32] in `dtype`, Ho = (H - 3) / 2 + 1: column 9 c + 3 ky + kx of row
+ * (b, oy, ox) is pixel (c, 2 oy + ky, 2 ox + kx), the order of conv.weight.view(32, 27); columns 27 .. 31 are zeros. */
+int uwu_inception_stem(const void* images, int in_u8, void* out, int B, int H, int W, int dtype, void* stream);
+/* 3x3 pooling, channels-last, strided in and out like uwu_conv2d_fwd.  MAX_S2: stride 2, no padding, Ho = (H - 3) / 2 + 1 (H, W >= 3);
+ * MAX_S1P1: stride 1, padding 1 that never wins (the maximum over the pixels inside the image); AVG_S1P1: stride 1, padding 1, the
+ * sum over the pixels inside the image divided by their number, 4 / 6 / 9 (count_include_pad = False), in fp32.  C a multiple of 8. */
+#define UWU_POOL_MAX_S2 0
+#define UWU_POOL_MAX_S1P1 1
+#define UWU_POOL_AVG_S1P1 2
+int uwu_pool2d_fwd(const void* x, void* y, int B, int H, int W, int C, int mode, int ldx, int xoff, int ldy, int yoff, int dtype,
+                   void* stream);
+/* y[m, yoff .. yoff + N) = max(., 0) in place on M rows of ldy elements: the ReLU behind a uwu_gemm with UWU_EPI_BIAS, which is how the
+ * extractor runs the 1x1 convolutions that uwu_gemm was measured faster on.  N, ldy, yoff multiples of 8. */
+int uwu_relu_rows(void* y, int64_t M, int N, int ldy, int yoff, int dtype, void* stream);
+/* out[b, c] = mean over the HW pixels of x[b, :, c], added in ascending order in fp32; x rows of ldx elements in `dtype`, out fp32 [B, C] */
+int uwu_global_avgpool(const void* x, float* out, int B, int HW, int C, int ldx, int dtype, void* stream);
+/* FID statistics of a batch of features, accumulated on the device.  features fp32 [B, D] contiguous; acc: 1 + D + D D doubles,
+ * zeroed by the caller before the first batch:  acc[0] += B,  acc[1 + d] += sum_b f[b, d],  acc[1 + D + i D + j] += sum_b f[b, i]
+ * f[b, j].  Products and sums in double, b ascending; every element is owned by one thread: no floating-point atomics, the same
+ * batches in the same order give the same bits.  D a multiple of 64, at most 8192.  No host synchronisation. */
+int uwu_fid_stats_accum(const float* features, double* acc, int B, int D, void* stream);
+
 /* T5LayerNorm with the previous sublayer's residual add fused in:  x_out = x_in + y (y may be NULL: x_out is then not written and
  * may be NULL),  n_out = x_out * rsqrt(mean(x_out^2) + eps) * weight -- no mean subtraction, no bias.  x_in, y, x_out, n_out [M, D]
  * contiguous in `dtype`, weight fp32 [D]; D a multiple of 8, 16-byte aligned; statistics in fp32, taken of x_out as stored.

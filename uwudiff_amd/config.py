@@ -25,6 +25,8 @@ ALIASES = {
     "torchvision.transforms.Compose": "uwudiff_amd.transforms.Compose",  # PIL-based stand-ins: torchvision is not installable offline
     "torchvision.transforms.Resize": "uwudiff_amd.transforms.Resize",
     "torchvision.transforms.ToTensor": "uwudiff_amd.transforms.ToTensor",
+    "torchvision.transforms.CenterCrop": "uwudiff_amd.transforms.CenterCrop",
+    "torchmetrics.image.fid.FrechetInceptionDistance": "uwudiff_amd.metrics.FrechetInceptionDistance",  # native
     "lion_pytorch.Lion": "uwudiff_amd.optim.FusedLion",  # the commented alternative of the reference's training YAMLs
     "prodigyopt.Prodigy": "uwudiff_amd.optim.FusedProdigy",  # parameter-free step size
     "lightning.pytorch.callbacks.ModelCheckpoint": "uwudiff_amd.engine.ModelCheckpoint",

@@ -137,6 +137,14 @@ _SIGS = {
     "uwu_vit_embed": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, P]),
     "uwu_clip_score_accum": (c_int, [P, P, P, P, c_int, c_int, c_int, P]),
     "uwu_timestep_stats_accum": (c_int, [P, P, c_int, P, c_int, c_int, P, P, P]),
+    "uwu_conv2d_ok": (c_int, [c_int] * 15),
+    "uwu_conv2d_ws_bytes": (ctypes.c_size_t, [c_int] * 15),
+    "uwu_conv2d_fwd": (c_int, [P, P, P, P] + [c_int] * 16 + [P, ctypes.c_size_t, P]),
+    "uwu_inception_stem": (c_int, [P, c_int, P, c_int, c_int, c_int, c_int, P]),
+    "uwu_pool2d_fwd": (c_int, [P, P] + [c_int] * 10 + [P]),
+    "uwu_relu_rows": (c_int, [P, c_int64, c_int, c_int, c_int, c_int, P]),
+    "uwu_global_avgpool": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, P]),
+    "uwu_fid_stats_accum": (c_int, [P, P, c_int, c_int, P]),
     "uwu_add_rmsnorm_fwd": (c_int, [P] * 5 + [c_int, c_int, c_float, c_int, P]),
     "uwu_gated_act_fwd": (c_int, [P, P] + [c_int] * 6 + [P]),
     "uwu_t5_rel_bias": (c_int, [P, P, P, c_int, c_int, c_int, P]),

@@ -293,6 +293,105 @@ def clip_score_accum(image_embeds, text_embeds, acc):
     return scores
 
 
+def _pair(v):
+    return (int(v), int(v)) if isinstance(v, int) else (int(v[0]), int(v[1]))
+
+
+def conv2d_out_hw(H, W, kernel, stride=1, padding=0):
+    (KH, KW), (ph, pw) = _pair(kernel), _pair(padding)
+    return (H + 2 * ph - KH) // stride + 1, (W + 2 * pw - KW) // stride + 1
+
+
+def conv2d_ok(B, H, W, C, Cout, kernel, stride=1, padding=0, ldx=None, xoff=0, ldy=None, yoff=0, dtype=torch.bfloat16):
+    """True where ``conv2d_fwd`` runs the shape, False where it refuses it: the entry point's own predicate, asked on the host"""
+    (KH, KW), (ph, pw) = _pair(kernel), _pair(padding)
+    dt = {torch.float32: L.F32, torch.bfloat16: L.BF16}.get(dtype, -1)
+    return bool(L.load().uwu_conv2d_ok(B, H, W, C, Cout, KH, KW, stride, ph, pw, C if ldx is None else ldx, xoff,
+                                       Cout if ldy is None else ldy, yoff, dt))
+
+
+def conv2d_fwd(x, w, bias, B, H, W, C, Cout, kernel, stride=1, padding=0, relu=False, xoff=0, out=None, yoff=0):
+    """y = [relu](conv(x, w) + bias) on channels-last activations: x [B*H*W, ldx] of which channels xoff .. xoff + C are read, w
+    [Cout, KH*KW*C] (tap-major), bias fp32 [Cout] or None -> out [B*Ho*Wo, ldy] of which channels yoff .. yoff + Cout are written (a
+    new [B*Ho*Wo, Cout] without `out`)."""
+    (KH, KW), (ph, pw) = _pair(kernel), _pair(padding)
+    Ho, Wo = conv2d_out_hw(H, W, (KH, KW), stride, (ph, pw))
+    if out is None:
+        out = torch.empty(max(B * Ho * Wo, 0), Cout, device=x.device, dtype=x.dtype)
+    if (x.dim() != 2 or out.dim() != 2 or x.shape[0] != B * H * W or out.shape[0] != B * Ho * Wo or out.dtype != x.dtype or w.dtype != x.dtype
+            or w.numel() != Cout * KH * KW * C or (bias is not None and (bias.dtype != torch.float32 or bias.numel() != Cout))):
+        raise L.UwuError(f"conv2d_fwd: x {tuple(x.shape)} {x.dtype}, w {tuple(w.shape)} {w.dtype}, out {tuple(out.shape)} {out.dtype} do not "
+                         f"fit B = {B}, H = {H}, W = {W}, C = {C}, Cout = {Cout}, kernel {KH} x {KW}, stride {stride}, padding ({ph}, {pw})")
+    L.call("uwu_conv2d_fwd", L.ptr(x), L.ptr(w), L.ptr(bias), L.ptr(out), B, H, W, C, Cout, KH, KW, stride, ph, pw, x.shape[1], xoff,
+           out.shape[1], yoff, int(relu), L.dt(x), None, 0, L.stream())
+    return out
+
+
+def conv1x1_gemm_fwd(x, w, bias, C, Cout, relu=False, xoff=0, out=None, yoff=0):
+    """The same result as a 1x1 / stride 1 ``conv2d_fwd`` by the explicit route, whose column matrix is the activation itself:
+    ``uwu_gemm`` with the bias epilogue on channels xoff.. of x [M, ldx] into channels yoff.. of out [M, ldy], then ``uwu_relu_rows``
+    in place (uwu_gemm has no ReLU epilogue)."""
+    M = x.shape[0]
+    if out is None:
+        out = torch.empty(M, Cout, device=x.device, dtype=x.dtype)
+    if (x.dim() != 2 or out.dim() != 2 or out.shape[0] != M or out.dtype != x.dtype or w.dtype != x.dtype or tuple(w.shape) != (Cout, C)
+            or bias.dtype != torch.float32 or bias.numel() != Cout or xoff % 8 or yoff % 8 or xoff < 0 or yoff < 0
+            or xoff + C > x.shape[1] or yoff + Cout > out.shape[1]):
+        raise L.UwuError(f"conv1x1_gemm_fwd: x {tuple(x.shape)} (offset {xoff}), w {tuple(w.shape)}, out {tuple(out.shape)} (offset {yoff}) "
+                         f"do not fit C = {C}, Cout = {Cout} (offsets multiples of 8, slices inside their rows)")
+    es = x.element_size()
+    L.call("uwu_gemm", L.ptr(x) + xoff * es, L.ptr(w), L.ptr(out) + yoff * es, None, L.ptr(bias), None, M, Cout, C, x.shape[1], C,
+           out.shape[1], 0, 0, 0, L.dt(x), L.dt(out), L.EPI_BIAS, 1, L.stream())
+    if relu:
+        L.call("uwu_relu_rows", L.ptr(out), M, Cout, out.shape[1], yoff, L.dt(out), L.stream())
+    return out
+
+
+def inception_stem(images, dtype):
+    """pictures [B, 3, H, W], uint8 or fp32 in [0, 1] -> the operand [B*Ho*Wo, 32] of the first convolution (3x3, stride 2) in `dtype`,
+    ``(v - 128) / 128`` of the integer pixel value v fused in (a float is first turned into ``trunc(clamp(x, 0, 1) * 255)``)"""
+    if images.dim() != 4 or images.shape[1] != 3 or images.dtype not in (torch.uint8, torch.float32):
+        raise L.UwuError(f"inception_stem: images must be uint8 or fp32 [B, 3, H, W], got {images.dtype} {tuple(images.shape)}")
+    B, _, H, W = images.shape
+    out = torch.empty(B * ((H - 3) // 2 + 1) * ((W - 3) // 2 + 1), 32, device=images.device, dtype=dtype)
+    L.call("uwu_inception_stem", L.ptr(images), int(images.dtype == torch.uint8), L.ptr(out), B, H, W, L.dt(out), L.stream())
+    return out
+
+
+POOL = {"max_s2": 0, "max_s1p1": 1, "avg_s1p1": 2}  # UWU_POOL_*
+
+
+def pool2d_fwd(x, B, H, W, C, mode, xoff=0, out=None, yoff=0):
+    """3x3 pooling on channels-last rows: "max_s2" (stride 2, no padding), "max_s1p1", "avg_s1p1" (count_include_pad=False);
+    channels xoff .. xoff + C of x [B*H*W, ldx] -> channels yoff .. yoff + C of out [B*Ho*Wo, ldy]"""
+    Ho, Wo = ((H - 3) // 2 + 1, (W - 3) // 2 + 1) if mode == "max_s2" else (H, W)
+    if out is None:
+        out = torch.empty(max(B * Ho * Wo, 0), C, device=x.device, dtype=x.dtype)
+    if x.dim() != 2 or out.dim() != 2 or x.shape[0] != B * H * W or out.shape[0] != B * Ho * Wo or out.dtype != x.dtype:
+        raise L.UwuError(f"pool2d_fwd: x {tuple(x.shape)} and out {tuple(out.shape)} do not fit B = {B}, H = {H}, W = {W} ({mode})")
+    L.call("uwu_pool2d_fwd", L.ptr(x), L.ptr(out), B, H, W, C, POOL[mode], x.shape[1], xoff, out.shape[1], yoff, L.dt(x), L.stream())
+    return out
+
+
+def global_avgpool(x, B, HW, C):
+    """x [B*HW, C] -> fp32 [B, C], the mean over each picture's pixels"""
+    if x.dim() != 2 or tuple(x.shape) != (B * HW, C):
+        raise L.UwuError(f"global_avgpool: x {tuple(x.shape)} is not [{B} * {HW}, {C}]")
+    out = torch.empty(B, C, device=x.device, dtype=torch.float32)
+    L.call("uwu_global_avgpool", L.ptr(x), L.ptr(out), B, HW, C, x.shape[1], L.dt(x), L.stream())
+    return out
+
+
+def fid_stats_accum(features, acc):
+    """acc (float64 [1 + D + D*D] on the device: n, sum, outer) += the statistics of features fp32 [B, D], in a fixed order"""
+    if features.dim() != 2 or features.dtype != torch.float32:
+        raise L.UwuError(f"fid_stats_accum: features must be fp32 [B, D], got {features.dtype} {tuple(features.shape)}")
+    B, D = features.shape
+    if acc.dtype != torch.float64 or acc.numel() != 1 + D + D * D:
+        raise L.UwuError(f"fid_stats_accum: acc must be float64 [{1 + D + D * D}]")
+    L.call("uwu_fid_stats_accum", L.ptr(features), L.ptr(acc), B, D, L.stream())
+
+
 def add_rmsnorm_fwd(x_in, weight, eps, y=None):
     """(x_in + y, RMSNorm(x_in + y) * weight) on [M, D]; without y the first is x_in itself.  weight fp32 [D]."""
     M, D = x_in.shape

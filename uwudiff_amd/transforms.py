@@ -1,5 +1,5 @@
-"""PIL-based stand-ins for the three ``torchvision.transforms`` the reference's metric configs name (``configs/demo_metrics.yaml``:
-``Compose([Resize(size), ToTensor()])``); torchvision is not installable offline, ``uwudiff_amd.config.ALIASES`` points the targets
+"""PIL-based stand-ins for the four ``torchvision.transforms`` the reference's metric configs name (``configs/demo_metrics.yaml``:
+``Compose([Resize(size), ToTensor()])``, and ``CenterCrop`` in the FID block's reference dataset); torchvision is not installable offline, ``uwudiff_amd.config.ALIASES`` points the targets
 here.  They work on PIL images only, which is what ``duwu.data.text_image_local`` hands them."""
 import numpy as np
 import torch
@@ -54,3 +54,28 @@ class ToTensor:
         if a.ndim == 2:
             a = a[:, :, None]
         return torch.from_numpy(np.ascontiguousarray(a.transpose(2, 0, 1))).float().div(255)
+
+
+class CenterCrop:
+    """The centre ``size`` = (height, width) (an int: a square) of a PIL image, with torchvision's rounding of the corner
+    (``int(round((h - th) / 2))``); a side shorter than the crop is first padded with zeros on both ends, as torchvision does."""
+
+    def __init__(self, size):
+        self.size = (int(size), int(size)) if isinstance(size, int) else tuple(int(s) for s in size)
+        if len(self.size) == 1:
+            self.size = (self.size[0], self.size[0])
+        if len(self.size) != 2 or min(self.size) < 1:
+            raise ValueError(f"CenterCrop: size must be a positive int or (height, width), got {size!r}")
+
+    def __call__(self, img):
+        if not isinstance(img, Image.Image):
+            raise TypeError(f"CenterCrop works on PIL images, got {type(img).__name__}")
+        th, tw = self.size
+        w, h = img.size
+        if tw > w or th > h:
+            pl, pt = (tw - w) // 2 if tw > w else 0, (th - h) // 2 if th > h else 0
+            padded = Image.new(img.mode, (max(w, tw), max(h, th)))
+            padded.paste(img, (pl, pt))
+            img, (w, h) = padded, padded.size
+        top, left = int(round((h - th) / 2.0)), int(round((w - tw) / 2.0))
+        return img.crop((left, top, left + tw, top + th))
