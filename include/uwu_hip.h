@@ -365,6 +365,32 @@ int uwu_adapter_merge(const float* base, const float* p, const int64_t* table, c
  *   LOKR*: out_l ceil(out_k in_n / 2048) in_m + out_l out_k in_n + 2 out_k in_n   (out_l = N/out_k, in_m = K/in_n) */
 int uwu_adapter_grad(const float* dw, int64_t N, int64_t K, int kind, const float* p, float* g, int64_t pa, int64_t pb,
                      int64_t pc, int r, int out_k, int in_n, float scale, float* ws, int64_t ws_elems, void* stream);
+/* Weight decomposition (DoRA): W' = m V / n with V = base + delta (delta as above), one magnitude m
+ * and one norm n = ||V||_2 + 2^-23 per row (orient 1, wd_on_out) or per column (orient 0) of an adapted [rows, cols] Linear.
+ * Segment table: one row of 16 int64 per decomposed tensor -- the 13 fields of uwu_adapter_merge, then
+ *   dora_off (m in p: rows or cols floats), norm_off (n in norms: as many floats), orient
+ * `table` is the device copy the kernels read, `table_host` the same rows in host memory: every row is checked (kind LORA /
+ * LOKR / LOKR_LOWRANK, r in [1, 128], base / eff / shadow offsets multiples of 64, nblocks) before anything is launched.
+ * uwu_adapter_dora_norms writes n of every segment in one launch; the sum of squares is added in double in an order fixed
+ * by the shape (no float atomics).  blk_start [nseg + 1] = exclusive prefix sum of ceil(rows / 4) (orient 1) or
+ * ceil(cols / 64) (orient 0) per row.
+ * uwu_adapter_dora_merge writes W' to eff and / or shadow with the conventions of uwu_adapter_merge (blk_start as there:
+ * ceil(rows * cols / 4096)); it reads the norms the previous launch wrote.  eff may alias base. */
+int uwu_adapter_dora_norms(const float* base, const float* p, const int64_t* table, const int64_t* table_host,
+                           const int64_t* blk_start, int nseg, int64_t nblocks, float* norms, void* stream);
+int uwu_adapter_dora_merge(const float* base, const float* p, const int64_t* table, const int64_t* table_host,
+                           const int64_t* blk_start, int nseg, int64_t nblocks, const float* norms, float* eff, void* shadow,
+                           void* stream);
+/* The stage in front of uwu_adapter_grad for a decomposed [N, K] weight.  dw holds dL/dW' on entry and dL/dV on return (in
+ * place); dL/dm is ACCUMULATED into g at dora_off.  With t = <dw, V> over a row (wd_on_out != 0) or a column, u = ||V||:
+ *   dm = t / n,  dV = m / n (dw - V t / (n u))   (the second term 0 where u = 0)
+ * base: this weight's frozen fp32 values, norms: its n (both already offset); V is recomputed from base and p, and u^2 is
+ * summed next to t (the bracket is evaluated in double as (dw - V t / u^2) + V t / u^2 eps / n: it cancels where one element
+ * carries the row or column).  dw and base are 16-byte aligned where K is a multiple of 4.  Deterministic: fixed-order sums;
+ * per column they go through ws (8-byte aligned).  ws_elems: floats of ws -- 0 (wd_on_out) or 4 ceil(N / 256) K. */
+int uwu_adapter_dora_grad(float* dw, const float* base, int64_t N, int64_t K, int kind, const float* p, float* g, int64_t pa,
+                          int64_t pb, int64_t pc, int r, int out_k, int in_n, float scale, int64_t dora_off,
+                          const float* norms, int wd_on_out, float* ws, int64_t ws_elems, void* stream);
 
 /* ------------------------------------------------------------------ gradient exchange (section 8e)
  * One RCCL communicator per rank (librccl resolved at run time), created once; uwu_allreduce_flat sums a slice of the

@@ -1,8 +1,10 @@
 """LyCORIS adapter training vs full fine-tuning of the SDXL UNet at BASELINE config 4's shape (4x128x128 latents, batch 12,
 bf16, fused AdamW): ms/step and peak memory of each mode, and the two adapter kernels alone (merge of every adapted
 tensor, adapter gradient of every adapted Linear) with the bytes they move.  One JSON line.  DESIGN.md section 4.21.
+With a weight-decomposed config (--lycoris configs/lycoris/sdxl-diffusers-dora.toml, section 4.39) the merge figure covers
+its three launches and the summed time of uwu_adapter_dora_grad is reported on its own.
 
-    python tools/bench_lycoris.py [--batch 12] [--steps 5] [--warmup 2] [--mode both|full|lycoris]
+    python tools/bench_lycoris.py [--batch 12] [--steps 5] [--warmup 2] [--mode both|full|lycoris] [--lycoris PATH]
 
 Each mode runs in a child process of its own (peak memory of one mode is not polluted by the other)."""
 import argparse
@@ -17,7 +19,7 @@ sys.path.insert(0, ROOT)
 TOML = os.path.join(ROOT, "configs", "lycoris", "sdxl-diffusers.toml")
 
 
-def run_mode(mode, B, steps, warmup):
+def run_mode(mode, B, steps, warmup, toml=TOML):
     import torch
 
     from duwu.loss import DiffusionLoss
@@ -33,9 +35,12 @@ def run_mode(mode, B, steps, warmup):
         from uwudiff_amd.adapters import LycorisNetwork
 
         model.requires_grad_(False)
-        net = LycorisNetwork(model, TOML).to(dev)
+        net = LycorisNetwork(model, toml).to(dev)
         with torch.no_grad():  # non-zero adapters (a zero LoKr w2 computes the same, but the timing should not rely on it)
+            keep = {s.name: net.view(s.name, "dora_scale").clone() for s in net.specs if s.dora}
             net.flat.data.normal_(0, 1e-3)
+            for name, m in keep.items():  # (the magnitudes keep their start: the norms of the base weights)
+                net.view(name, "dora_scale").copy_(m)
         net.apply_to(model)
         params = list(net.parameters())
     else:
@@ -88,6 +93,8 @@ def run_mode(mode, B, steps, warmup):
     t_merge = ev[0].elapsed_time(ev[1]) / reps
     n_eff = sum(int(torch.tensor(model.P.registry[n][1]).prod()) for n in ad.eff_off)
     merge_bytes = n_el * (4 + 2) + n_eff * 4 + net.n * 4
+    n_dora = sum(int(torch.tensor(model.P.registry[n][1]).prod()) for n in ad.dora)
+    merge_bytes += n_dora * 4  # the norm pass reads the decomposed base elements once more
     # adapter gradients of every adapted Linear from an fp32 dW of its shape (reads dW once + the factors + small partials)
     grads_names = [n for n in ad.names if ad.seg[n][1] != 0]
     dws = {}
@@ -105,6 +112,15 @@ def run_mode(mode, B, steps, warmup):
     torch.cuda.synchronize()
     t_grad = ev[0].elapsed_time(ev[1])
     grad_bytes = sum(int(torch.tensor(model.P.registry[n][1]).prod()) * 4 for n in grads_names)
+    if ad.dora:  # the stage in front of uwu_adapter_grad alone: G read twice, base read once, G written once
+        ev[0].record()
+        for n in ad.dora:
+            ad.dora_grad(model.P, n, dws[tuple(model.P.registry[n][1])])
+        ev[1].record()
+        torch.cuda.synchronize()
+        t_dora = ev[0].elapsed_time(ev[1])
+        out.update({"decomposed_elements": n_dora, "dora_grad_ms_per_step": round(t_dora, 3),
+                    "dora_grad_bytes": n_dora * 16, "dora_grad_GBps": round(n_dora * 16 / t_dora / 1e6, 1)})
     out.update({"adapted_elements": n_el, "merge_ms": round(t_merge, 3), "merge_bytes": merge_bytes,
                 "merge_GBps": round(merge_bytes / t_merge / 1e6, 1), "adapter_grad_ms_per_step": round(t_grad, 3),
                 "adapted_linears": len(grads_names), "adapter_grad_dW_bytes": grad_bytes,
@@ -118,21 +134,24 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--mode", default="both", choices=["both", "full", "lycoris"])
+    ap.add_argument("--lycoris", default=TOML, help="LyCORIS TOML of the adapter mode (default: the shipped preset)")
     ap.add_argument("--child", action="store_true")
     a = ap.parse_args()
     if a.child:
-        print("RESULT " + json.dumps(run_mode(a.mode, a.batch, a.steps, a.warmup)), flush=True)
+        print("RESULT " + json.dumps(run_mode(a.mode, a.batch, a.steps, a.warmup, a.lycoris)), flush=True)
         return
     res = {}
     for mode in (["full", "lycoris"] if a.mode == "both" else [a.mode]):
         r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", "--mode", mode, "--batch", str(a.batch),
-                            "--steps", str(a.steps), "--warmup", str(a.warmup)], capture_output=True, text=True)
+                            "--steps", str(a.steps), "--warmup", str(a.warmup), "--lycoris", os.path.abspath(a.lycoris)],
+                           capture_output=True, text=True)
         line = [l for l in r.stdout.splitlines() if l.startswith("RESULT ")]
         if r.returncode != 0 or not line:
             res[mode] = {"error": f"exit {r.returncode}", "tail": (r.stdout + r.stderr)[-1500:]}
             break  # (nothing more on the device after a failed run)
         res[mode] = json.loads(line[0][len("RESULT "):])
-    print(json.dumps({"tool": "bench_lycoris", "shape": f"SDXL UNet bf16, 4x128x128, batch {a.batch}", **res}))
+    print(json.dumps({"tool": "bench_lycoris", "shape": f"SDXL UNet bf16, 4x128x128, batch {a.batch}",
+                      "lycoris": os.path.relpath(os.path.abspath(a.lycoris), ROOT), **res}))
 
 
 if __name__ == "__main__":

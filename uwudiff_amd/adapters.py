@@ -9,8 +9,11 @@ is not a dependency of this build; the subset below is this project's contract (
            (out_l, out_k) = factorization(out, factor), (in_m, in_n) = factorization(in, factor); w2 = w2_a @ w2_b
            (w2_b the zero factor, scale alpha / dim) when not full_matrix and dim < max(out_k, in_n) / 2, else scale 1
   * norm   gamma + w_norm, beta + b_norm                     both zeros
+  * dora_wd (on LoRA / LoKr): W' = m (W + dW) / (||W + dW|| + eps), one magnitude m (``dora_scale``) and one norm per
+           output row (wd_on_out) or per input column, eps = 2^-23 added to the norm; m starts at the base weight's norm
+           
 
-so a freshly attached network leaves the model's output unchanged.  Every adapter tensor is a named view of ONE flat
+so a freshly attached network leaves the model's output unchanged (with dora_wd: to rounding).  Every adapter tensor is a named view of ONE flat
 fp32 parameter (the fused AdamW and the gradient exchange work on it as on the UNet's flat buffer); the UNet merges them
 into its effective weights with one kernel launch (csrc/adapter.hip) and computes their gradients from the weight
 gradients of the adapted layers.  Matching runs on the UNet's name / shape registry only: a UNet built on the ``meta``
@@ -26,7 +29,8 @@ import torch.nn as nn
 from .flat import pad64
 
 CONFIG_DEFAULTS = dict(algo="lora", linear_dim=4, linear_alpha=1.0, factor=-1, full_matrix=False, train_norm=False,
-                       conv_dim=None, conv_alpha=None, use_tucker=False)
+                       conv_dim=None, conv_alpha=None, use_tucker=False, dora_wd=False, wd_on_out=True)
+BOOL_KEYS = ("dora_wd", "wd_on_out")
 PRESET_KEYS = ("target_module", "target_name", "enable_conv", "module_algo_map")
 ALGOS = ("lora", "lokr")
 KIND_NORM, KIND_LORA, KIND_LOKR, KIND_LOKR_LOWRANK = 0, 1, 2, 3  # UWU_ADAPTER_* of include/uwu_hip.h
@@ -97,6 +101,9 @@ def _check_algo_table(t, where):
     if "algo" in t and t["algo"] not in ALGOS:
         raise NotImplementedError(f"lycoris_config.{where}: algo {t['algo']!r} is not implemented (supported: "
                                   f"{', '.join(ALGOS)})")
+    for k in BOOL_KEYS:
+        if k in t and not isinstance(t[k], bool):
+            raise ValueError(f"lycoris_config.{where}: {k} must be true or false, got {t[k]!r}")
     return t
 
 
@@ -145,9 +152,16 @@ class Spec:
     """One adapted layer: ``name`` (module), ``algo`` ('lora' / 'lokr' / 'norm'), ``shape`` ([out, in] or [C]), the
     adapter tensors [(tensor name, shape)], and the factors the kernels need."""
 
-    def __init__(self, name, algo, shape, dim=0, alpha=1.0, factor=-1, full_matrix=False):
+    def __init__(self, name, algo, shape, dim=0, alpha=1.0, factor=-1, full_matrix=False, dora_wd=False, wd_on_out=True):
         self.name, self.algo, self.shape = name, algo, tuple(shape)
         self.dim, self.alpha, self.r, self.out_k, self.in_n, self.lowrank = 0, None, 0, 0, 0, False
+        self.dora, self.wd_on_out = bool(dora_wd) and algo != "norm", bool(wd_on_out)
+        self._factors(dim, alpha, factor, full_matrix)
+        if self.dora:  # one magnitude per output row or per input column, always the last tensor
+            self.tensors.append(("dora_scale", (self.shape[0], 1) if self.wd_on_out else (1, self.shape[1])))
+
+    def _factors(self, dim, alpha, factor, full_matrix):
+        name, algo = self.name, self.algo
         if algo == "norm":
             self.tensors = [("w_norm", self.shape), ("b_norm", self.shape)]
             self.scale = 1.0
@@ -215,7 +229,8 @@ def match_layers(unet, lycoris_config):
         cfg = {**config, **(over or {})}
         if kind == "Linear":
             specs.append(Spec(leaf, cfg["algo"], registry[leaf + ".weight"][1], dim=cfg["linear_dim"],
-                              alpha=cfg["linear_alpha"], factor=cfg["factor"], full_matrix=cfg["full_matrix"]))
+                              alpha=cfg["linear_alpha"], factor=cfg["factor"], full_matrix=cfg["full_matrix"],
+                              dora_wd=cfg["dora_wd"], wd_on_out=cfg["wd_on_out"]))
         elif kind in ("LayerNorm", "GroupNorm"):
             if cfg["train_norm"]:
                 specs.append(Spec(leaf, "norm", registry[leaf + ".weight"][1]))
@@ -238,6 +253,11 @@ def grad_ws_elems(spec, N, K):
     return out_l * -(-W2 // 2048) * in_m + out_l * W2 + 2 * W2
 
 
+def dora_grad_ws_elems(spec, N, K):
+    """floats of uwu_adapter_dora_grad's workspace (include/uwu_hip.h): the column sums go through row-tile partials"""
+    return 0 if spec.wd_on_out else 4 * -(-N // 256) * K
+
+
 class LycorisNetwork(nn.Module):
     """The adapters of one UNet: ``flat`` (one fp32 parameter) with every adapter tensor as a named view.
 
@@ -258,7 +278,9 @@ class LycorisNetwork(nn.Module):
             device = unet.flat.device if unet.flat.device.type != "meta" else "cpu"
         self.flat = nn.Parameter(torch.zeros(n, dtype=torch.float32, device=device))
         self._dirty = True
-        self.reset_parameters()
+        # dora_scale starts at the norm of the BASE weight; a UNet without storage (meta) cannot supply it
+        self.dora_uninitialised = False
+        self.reset_parameters(unet)
 
     # ------------------------------------------------------------------ views / init
     def view(self, spec_name, tensor, buf=None):
@@ -266,9 +288,10 @@ class LycorisNetwork(nn.Module):
         return (self.flat.data if buf is None else buf)[off:off + math.prod(shape)].view(shape)
 
     @torch.no_grad()
-    def reset_parameters(self):
+    def reset_parameters(self, unet=None):
         """kaiming_uniform(a=sqrt 5) on lora_down / lokr_w1 / lokr_w2_a (torch's default generator), zeros elsewhere:
-        dW = 0 and the adapted model computes what the bare one does."""
+        dW = 0 and the adapted model computes what the bare one does.  dora_scale: the norms of the base weights of
+        ``unet`` (default: the UNet the network is attached to)."""
         self.flat.data.zero_()
         for s in self.specs:
             for t, shape in s.tensors:
@@ -276,7 +299,21 @@ class LycorisNetwork(nn.Module):
                     w = torch.empty(shape, dtype=torch.float32)
                     nn.init.kaiming_uniform_(w, a=math.sqrt(5))
                     self.view(s.name, t).copy_(w)
+        self._init_dora(unet if unet is not None else self.__dict__.get("_unet"))
         self.mark_dirty()
+
+    def _init_dora(self, unet):
+        dora = [s for s in self.specs if s.dora]
+        if not dora:
+            return
+        if unet is None or unet.flat.device.type == "meta":
+            self.dora_uninitialised = True  # zeros: apply_to refuses until a state dict supplies every dora_scale
+            return
+        for s in dora:
+            w = unet.P.base32(s.name + ".weight").detach().double()  # (summed in fp64, rounded once)
+            m = torch.linalg.vector_norm(w, dim=1 if s.wd_on_out else 0, keepdim=True).float()
+            self.view(s.name, "dora_scale").copy_(m)
+        self.dora_uninitialised = False
 
     def mark_dirty(self):
         """the adapter weights changed (optimizer step, load): the UNet merges again before its next forward"""
@@ -297,7 +334,7 @@ class LycorisNetwork(nn.Module):
 
     def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys,
                               error_msgs):
-        mine = set()
+        mine, dora_loaded = set(), True
         with torch.no_grad():
             for s in self.specs:
                 for t, shape in s.tensors:
@@ -305,10 +342,12 @@ class LycorisNetwork(nn.Module):
                     mine.add(k)
                     if k not in state_dict:
                         missing_keys.append(k)
+                        dora_loaded &= t != "dora_scale"
                         continue
                     v = state_dict[k]
                     if tuple(v.shape) != tuple(shape):
                         error_msgs.append(f"size mismatch for {k}: checkpoint {tuple(v.shape)}, adapter {tuple(shape)}")
+                        dora_loaded &= t != "dora_scale"
                         continue
                     self.view(s.name, t).copy_(v.float())
                 if s.alpha is not None:
@@ -319,11 +358,17 @@ class LycorisNetwork(nn.Module):
         for k in state_dict:
             if k.startswith(prefix) and k not in mine:
                 unexpected_keys.append(k)
+        if dora_loaded:
+            self.dora_uninitialised = False
         self.mark_dirty()
 
     # ------------------------------------------------------------------ attach / detach / fold
     def apply_to(self, unet=None):
         unet = unet if unet is not None else self._unet
+        if self.dora_uninitialised:
+            raise RuntimeError("LycorisNetwork.apply_to: dora_scale is uninitialised (the network was built on a UNet "
+                               "without storage); build it on a UNet with weights or load a state dict with every "
+                               "dora_scale first")
         object.__setattr__(self, "_unet", unet)  # (not a sub-module: the UNet's state dict stays the base weights)
         unet.attach_adapters(self)
         return self

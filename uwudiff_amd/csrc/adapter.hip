@@ -7,6 +7,9 @@
 //          dw2 += s sum_ij w1[i,j] dW block (i,j) (through w2 = w2_a w2_b for the low-rank form).  dW is read once; the
 //          partial sums of the workgroups go to a workspace and a second launch adds them in a fixed order: no float
 //          atomics, the result is bit-identical run to run.
+//   dora:  weight decomposition on top of LoRA / LoKr (section 4.39): W' = m (W + dW) / (||W + dW|| + eps) per row or column --
+//          the norms of every decomposed tensor (one launch), the merge with the factor m / n (one launch), and per layer the
+//          stage in front of `grad` that turns dL/dW' into dL/d(W + dW) in place and adds dL/dm.  Fixed-order fp64 sums.
 #include "common.h"
 
 namespace {
@@ -240,6 +243,280 @@ int64_t ad_grad_ws_elems(int kind, int64_t N, int64_t K, int r, int out_k, int i
   return out_l * G * in_m + out_l * W2 + 2 * W2;
 }
 
+// ---------------------------------------------------------------------------------------------------------------- DoRA
+// Weight decomposition: W' = m V / n, V = base + delta, n = ||V row or column||_2 + eps.
+// A decomposed segment row has 16 fields: the 13 of the merge, then dora_off (m in p), norm_off (n in norms), orient
+// (1: one magnitude per row, wd_on_out; 0: one per column).
+constexpr int AD_DNF = 16;
+constexpr int AD_ROWS_WG = 4;    // row orientation: one wave per row, four rows per workgroup
+constexpr int AD_COLS_WG = 64;   // column orientation: one lane per column, the four waves stride the rows
+constexpr int AD_COL_RT = 256;   // rows per workgroup of the column-orientation gradient stage
+constexpr double AD_EPS = 1.1920928955078125e-07;  // 2^-23 = torch.finfo(torch.float32).eps
+
+// V = base + delta with the sum rounded on its own (never contracted into delta's last multiplication): the norm pass, the
+// merge and both passes of the gradient stage must see the same V bit for bit -- the gradient's bracket cancels on it
+__device__ __forceinline__ float ad_v(float b, const int64_t* __restrict__ row, const float* __restrict__ p, int e) {
+  return __fadd_rn(b, ad_delta(row, p, e));
+}
+
+struct AdSeg {
+  int64_t f[AD_DNF];
+};
+
+__device__ __forceinline__ double wave_sum_f64(double v) {  // xor butterfly: a fixed order, the sum in every lane
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+struct AdSums {
+  double ss, t;  // <V, V> and <G, V> (t: only with G)
+};
+
+// the sums over the row `i`; one wave, the result in every lane
+__device__ __forceinline__ AdSums ad_row_sums(const int64_t* __restrict__ row, const float* __restrict__ base,
+                                              const float* __restrict__ p, const float* __restrict__ G, int i, int cols,
+                                              int lane) {
+  const int e0 = i * cols;
+  AdSums a = {0.0, 0.0};
+  if ((cols & 3) == 0) {
+    for (int j = 4 * lane; j < cols; j += 4 * UWU_WAVE) {
+      f32x4 v = load4(base + e0 + j);
+      f32x4 w = {0.f, 0.f, 0.f, 0.f};
+      if (G) w = load4(G + e0 + j);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const double x = (double)ad_v(v[q], row, p, e0 + j + q);
+        a.ss += x * x;
+        a.t += x * (double)w[q];
+      }
+    }
+  } else {
+    for (int j = lane; j < cols; j += UWU_WAVE) {
+      const double x = (double)ad_v(base[e0 + j], row, p, e0 + j);
+      a.ss += x * x;
+      if (G) a.t += x * (double)G[e0 + j];
+    }
+  }
+  a.ss = wave_sum_f64(a.ss);
+  if (G) a.t = wave_sum_f64(a.t);
+  return a;
+}
+
+// the sums over the rows [i0, i1) of column j: the four waves take every fourth row, their sums are added in wave order
+// through `red` [2][4][64].  Valid where j < cols; every thread of the workgroup must call it.
+__device__ __forceinline__ AdSums ad_col_sums(const int64_t* __restrict__ row, const float* __restrict__ base,
+                                              const float* __restrict__ p, const float* __restrict__ G, int i0, int i1,
+                                              int cols, int j, double (*red)[4][AD_COLS_WG]) {
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  AdSums a = {0.0, 0.0};
+  if (j < cols) {
+    for (int i = i0 + w; i < i1; i += 4) {
+      const int e = i * cols + j;
+      const double x = (double)ad_v(base[e], row, p, e);
+      a.ss += x * x;
+      if (G) a.t += x * (double)G[e];
+    }
+  }
+  red[0][w][lane] = a.ss;
+  red[1][w][lane] = a.t;
+  __syncthreads();
+  a.ss = ((red[0][0][lane] + red[0][1][lane]) + red[0][2][lane]) + red[0][3][lane];
+  a.t = ((red[1][0][lane] + red[1][1][lane]) + red[1][2][lane]) + red[1][3][lane];
+  return a;
+}
+
+__device__ __forceinline__ int ad_find_segment(const int64_t* __restrict__ blk_start, int nseg, int64_t bid) {
+  int lo = 0, hi = nseg;  // blk_start[lo] <= bid < blk_start[hi]
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (blk_start[mid] <= bid) lo = mid;
+    else hi = mid;
+  }
+  return lo;
+}
+
+// norms[norm_off + a] = ||V[a, :]|| + eps (orient 1) or ||V[:, a]|| + eps (orient 0) of every decomposed segment.  The sum of
+// squares is added in double in an order the shape alone fixes: lane partials, then the butterfly (rows); wave partials,
+// then wave order (columns).
+__global__ void __launch_bounds__(256) adapter_dora_norms_kernel(const float* __restrict__ base, const float* __restrict__ p,
+                                                                 const int64_t* __restrict__ table,
+                                                                 const int64_t* __restrict__ blk_start, int nseg,
+                                                                 float* __restrict__ norms) {
+  __shared__ double red[2][4][AD_COLS_WG];
+  const int64_t bid = blockIdx.x;
+  const int lo = ad_find_segment(blk_start, nseg, bid);
+  const int64_t* row = table + (int64_t)lo * AD_DNF;
+  const int rows = (int)row[1], cols = (int)row[2];
+  const int b = (int)(bid - blk_start[lo]);
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const float* bs = base + row[3];
+  float* out = norms + row[14];
+  if (row[15]) {
+    const int i = b * AD_ROWS_WG + w;
+    if (i >= rows) return;
+    const AdSums a = ad_row_sums(row, bs, p, nullptr, i, cols, lane);
+    if (lane == 0) out[i] = (float)(sqrt(a.ss) + AD_EPS);
+  } else {
+    const int j = b * AD_COLS_WG + lane;
+    const AdSums a = ad_col_sums(row, bs, p, nullptr, 0, rows, cols, j, red);
+    if (w == 0 && j < cols) out[j] = (float)(sqrt(a.ss) + AD_EPS);
+  }
+}
+
+// W' = (base + delta) m / n: the merge kernel with one more factor per row or column
+__global__ void __launch_bounds__(256) adapter_dora_merge_kernel(const float* __restrict__ base, const float* __restrict__ p,
+                                                                 const int64_t* __restrict__ table,
+                                                                 const int64_t* __restrict__ blk_start, int nseg,
+                                                                 const float* __restrict__ norms, float* __restrict__ eff,
+                                                                 bf16_t* __restrict__ shadow) {
+  const int64_t bid = blockIdx.x;
+  const int lo = ad_find_segment(blk_start, nseg, bid);
+  const int64_t* row = table + (int64_t)lo * AD_DNF;
+  const int cols = (int)row[2];
+  const int n = (int)(row[1] * row[2]);
+  const int64_t boff = row[3], eoff = row[4], soff = row[5];
+  const float* m = p + row[13];
+  const float* nr = norms + row[14];
+  const bool by_row = row[15] != 0;
+  const int e0 = (int)(bid - blk_start[lo]) * AD_MERGE_ELEMS;
+#pragma unroll
+  for (int it = 0; it < AD_MERGE_ELEMS / 1024; ++it) {
+    const int e = e0 + it * 1024 + 4 * threadIdx.x;
+    if (e >= n) break;
+    if (e + 4 <= n) {
+      f32x4 v = load4(base + boff + e);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int i = (e + q) / cols;
+        const int a = by_row ? i : e + q - i * cols;
+        v[q] = ad_v(v[q], row, p, e + q) * (m[a] / nr[a]);
+      }
+      if (eoff >= 0) store4(eff + eoff + e, v);
+      if (shadow && soff >= 0) store4(shadow + soff + e, v);
+    } else {
+      for (int q = e; q < n; ++q) {
+        const int i = q / cols;
+        const int a = by_row ? i : q - i * cols;
+        const float v = ad_v(base[boff + q], row, p, q) * (m[a] / nr[a]);
+        if (eoff >= 0) eff[eoff + q] = v;
+        if (shadow && soff >= 0) shadow[soff + q] = (bf16_t)v;
+      }
+    }
+  }
+}
+
+// dV = s (G - V t / (n u)), s = m / n, dm = t / n with the n of the merge.  Where one element carries its row or column,
+// G - V t / (n u) is the difference of two nearly equal numbers (for a single element: G eps / n), and the fp32 n no longer
+// tells u = n - eps apart from n.  So u^2 = <V, V> is summed again next to t, and the term is evaluated in double as
+//   (G - V a) + V a eps / n,  a = t / u^2   (a = 0 where u = 0)
+// whose first part cancels exactly where it must.
+struct AdCoef {
+  double a, b;  // a = t / u^2, b = a eps / n
+  float s, dm;
+};
+__device__ __forceinline__ AdCoef ad_dora_coeffs(float n, float m, AdSums sums) {
+  AdCoef c;
+  c.a = sums.ss > 0.0 ? sums.t / sums.ss : 0.0;
+  c.b = c.a * (AD_EPS / (double)n);
+  c.s = m / n;
+  c.dm = (float)(sums.t / (double)n);
+  return c;
+}
+__device__ __forceinline__ float ad_dora_dv(AdCoef c, float g, float v) {
+  const double va = (double)v * c.a;
+  return c.s * (float)(((double)g - va) + (double)v * c.b);
+}
+
+// row orientation: one wave per row.  t = <G row, V row>, then the row of G is rewritten; V is recomputed both times (the
+// second read of base and G is served by the cache this wave has just filled).
+__global__ void __launch_bounds__(256) adapter_dora_grad_row_kernel(float* __restrict__ G, const float* __restrict__ base,
+                                                                    const float* __restrict__ p, float* __restrict__ g,
+                                                                    const float* __restrict__ norms, AdSeg seg) {
+  const int64_t* row = seg.f;
+  const int rows = (int)row[1], cols = (int)row[2];
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int i = blockIdx.x * AD_ROWS_WG + w;
+  if (i >= rows) return;
+  const AdCoef c = ad_dora_coeffs(norms[row[14] + i], p[row[13] + i], ad_row_sums(row, base, p, G, i, cols, lane));
+  const int e0 = i * cols;
+  if ((cols & 3) == 0) {
+    for (int j = 4 * lane; j < cols; j += 4 * UWU_WAVE) {
+      const f32x4 v = load4(base + e0 + j);
+      f32x4 gv = load4(G + e0 + j);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) gv[q] = ad_dora_dv(c, gv[q], ad_v(v[q], row, p, e0 + j + q));
+      store4(G + e0 + j, gv);
+    }
+  } else {
+    for (int j = lane; j < cols; j += UWU_WAVE)
+      G[e0 + j] = ad_dora_dv(c, G[e0 + j], ad_v(base[e0 + j], row, p, e0 + j));
+  }
+  if (lane == 0) g[row[13] + i] += c.dm;
+}
+
+// column orientation, stage 1: part[rt][j] = the two sums over the 256 rows of tile rt
+__global__ void __launch_bounds__(256) adapter_dora_grad_col_partial_kernel(const float* __restrict__ G,
+                                                                            const float* __restrict__ base,
+                                                                            const float* __restrict__ p,
+                                                                            AdSums* __restrict__ part, AdSeg seg) {
+  __shared__ double red[2][4][AD_COLS_WG];
+  const int64_t* row = seg.f;
+  const int rows = (int)row[1], cols = (int)row[2];
+  const int j = blockIdx.x * AD_COLS_WG + (threadIdx.x & 63);
+  const int i0 = blockIdx.y * AD_COL_RT, i1 = min(rows, i0 + AD_COL_RT);
+  const AdSums a = ad_col_sums(row, base, p, G, i0, i1, cols, j, red);
+  if (threadIdx.x < 64 && j < cols) part[(int64_t)blockIdx.y * cols + j] = a;
+}
+
+// stage 2: the sums of column j = the tile partials added in tile order (every workgroup of a column group computes the same sum), then the
+// workgroup's 256 x 64 tile of G is rewritten; the first row tile adds dm
+__global__ void __launch_bounds__(256) adapter_dora_grad_col_apply_kernel(float* __restrict__ G,
+                                                                          const float* __restrict__ base,
+                                                                          const float* __restrict__ p, float* __restrict__ g,
+                                                                          const float* __restrict__ norms,
+                                                                          const AdSums* __restrict__ part, int nrt,
+                                                                          AdSeg seg) {
+  const int64_t* row = seg.f;
+  const int rows = (int)row[1], cols = (int)row[2];
+  const int w = threadIdx.x >> 6;
+  const int j = blockIdx.x * AD_COLS_WG + (threadIdx.x & 63);
+  if (j >= cols) return;
+  AdSums sums = {0.0, 0.0};
+  for (int q = 0; q < nrt; ++q) {
+    const AdSums a = part[(int64_t)q * cols + j];
+    sums.ss += a.ss;
+    sums.t += a.t;
+  }
+  const AdCoef c = ad_dora_coeffs(norms[row[14] + j], p[row[13] + j], sums);
+  const int i0 = blockIdx.y * AD_COL_RT, i1 = min(rows, i0 + AD_COL_RT);
+  for (int i = i0 + w; i < i1; i += 4) {
+    const int e = i * cols + j;
+    G[e] = ad_dora_dv(c, G[e], ad_v(base[e], row, p, e));
+  }
+  if (blockIdx.y == 0 && w == 0) g[row[13] + j] += c.dm;
+}
+
+// workspace of uwu_adapter_dora_grad in floats (mirrored by uwudiff_amd/adapters.py: dora_grad_ws_elems)
+int64_t ad_dora_grad_ws_elems(int64_t N, int64_t K, int wd_on_out) {
+  return wd_on_out ? 0 : 4 * ((N + AD_COL_RT - 1) / AD_COL_RT) * K;
+}
+
+// the host copy of a decomposed segment table: every row is checked before anything is launched
+const char* ad_dora_check_rows(const int64_t* t, int nseg) {
+  for (int s = 0; s < nseg; ++s) {
+    const int64_t* r = t + (int64_t)s * AD_DNF;
+    if (r[0] != UWU_ADAPTER_LORA && r[0] != UWU_ADAPTER_LOKR && r[0] != UWU_ADAPTER_LOKR_LOWRANK) return "kind";
+    if (r[1] < 1 || r[2] < 1 || r[1] * r[2] >= (1ll << 31)) return "shape";
+    if (r[0] != UWU_ADAPTER_LOKR && (r[9] < 1 || r[9] > AD_MAX_RANK)) return "rank outside [1, 128]";
+    if (r[0] != UWU_ADAPTER_LORA && (r[10] < 1 || r[11] < 1 || r[1] % r[10] || r[2] % r[11])) return "LoKr factors";
+    if (r[3] < 0 || r[3] % 64 || (r[4] >= 0 && r[4] % 64) || (r[5] >= 0 && r[5] % 64)) return "misaligned base / eff / shadow offset";
+    if (r[6] < 0 || r[7] < 0 || r[8] < 0 || r[13] < 0 || r[14] < 0) return "negative offset";
+    if (r[15] != 0 && r[15] != 1) return "orientation";
+  }
+  return nullptr;
+}
+
 }  // namespace
 
 extern "C" int uwu_adapter_merge(const float* base, const float* p, const int64_t* table, const int64_t* blk_start,
@@ -304,5 +581,73 @@ extern "C" int uwu_adapter_grad(const float* dw, int64_t N, int64_t K, int kind,
                        out_k, in_n, r, g + pb, g + pc);
   }
   UWU_LAUNCH_CHECK("adapter_grad");
+  return UWU_OK;
+}
+
+extern "C" int uwu_adapter_dora_norms(const float* base, const float* p, const int64_t* table, const int64_t* table_host,
+                                      const int64_t* blk_start, int nseg, int64_t nblocks, float* norms, void* stream) {
+  UWU_CHECK_ARG(base && p && table && table_host && blk_start && norms && nseg > 0 && nblocks > 0 && nblocks < (1ll << 31),
+                "adapter_dora_norms: bad args (nseg=%d nblocks=%lld)", nseg, (long long)nblocks);
+  const char* why = ad_dora_check_rows(table_host, nseg);
+  UWU_CHECK_ARG(!why, "adapter_dora_norms: bad segment table: %s", why);
+  int64_t want = 0;
+  for (int s = 0; s < nseg; ++s) {
+    const int64_t* r = table_host + (int64_t)s * AD_DNF;
+    want += r[15] ? (r[1] + AD_ROWS_WG - 1) / AD_ROWS_WG : (r[2] + AD_COLS_WG - 1) / AD_COLS_WG;
+  }
+  UWU_CHECK_ARG(want == nblocks, "adapter_dora_norms: nblocks %lld, the table needs %lld", (long long)nblocks, (long long)want);
+  hipLaunchKernelGGL(adapter_dora_norms_kernel, dim3((unsigned)nblocks), dim3(256), 0, (hipStream_t)stream, base, p, table,
+                     blk_start, nseg, norms);
+  UWU_LAUNCH_CHECK("adapter_dora_norms");
+  return UWU_OK;
+}
+
+extern "C" int uwu_adapter_dora_merge(const float* base, const float* p, const int64_t* table, const int64_t* table_host,
+                                      const int64_t* blk_start, int nseg, int64_t nblocks, const float* norms, float* eff,
+                                      void* shadow, void* stream) {
+  UWU_CHECK_ARG(base && p && table && table_host && blk_start && norms && nseg > 0 && nblocks > 0 && nblocks < (1ll << 31),
+                "adapter_dora_merge: bad args (nseg=%d nblocks=%lld)", nseg, (long long)nblocks);
+  UWU_CHECK_ARG(eff || shadow, "adapter_dora_merge: no output");
+  const char* why = ad_dora_check_rows(table_host, nseg);
+  UWU_CHECK_ARG(!why, "adapter_dora_merge: bad segment table: %s", why);
+  int64_t want = 0;
+  for (int s = 0; s < nseg; ++s) {
+    const int64_t* r = table_host + (int64_t)s * AD_DNF;
+    want += (r[1] * r[2] + AD_MERGE_ELEMS - 1) / AD_MERGE_ELEMS;
+  }
+  UWU_CHECK_ARG(want == nblocks, "adapter_dora_merge: nblocks %lld, the table needs %lld", (long long)nblocks, (long long)want);
+  hipLaunchKernelGGL(adapter_dora_merge_kernel, dim3((unsigned)nblocks), dim3(256), 0, (hipStream_t)stream, base, p, table,
+                     blk_start, nseg, norms, eff, (bf16_t*)shadow);
+  UWU_LAUNCH_CHECK("adapter_dora_merge");
+  return UWU_OK;
+}
+
+extern "C" int uwu_adapter_dora_grad(float* dw, const float* base, int64_t N, int64_t K, int kind, const float* p, float* g,
+                                     int64_t pa, int64_t pb, int64_t pc, int r, int out_k, int in_n, float scale,
+                                     int64_t dora_off, const float* norms, int wd_on_out, float* ws, int64_t ws_elems,
+                                     void* stream) {
+  UWU_CHECK_ARG(dw && base && p && g && norms && N > 0 && K > 0 && N * K < (1ll << 31), "adapter_dora_grad: bad args");
+  const AdSeg seg = {{kind, N, K, 0, -1, -1, pa, pb, pc, r, out_k, in_n, (int64_t)__builtin_bit_cast(uint32_t, scale),
+                      dora_off, 0, wd_on_out}};
+  const char* why = ad_dora_check_rows(seg.f, 1);
+  UWU_CHECK_ARG(!why, "adapter_dora_grad: bad segment: %s", why);
+  UWU_CHECK_ARG(K % 4 != 0 || (((uintptr_t)dw | (uintptr_t)base) & 15) == 0,
+                "adapter_dora_grad: misaligned dw / base (16 bytes where K is a multiple of 4)");
+  const int64_t need = ad_dora_grad_ws_elems(N, K, wd_on_out);
+  UWU_CHECK_ARG(ws_elems >= need && (need == 0 || (ws && ((uintptr_t)ws & 7) == 0)),
+                "adapter_dora_grad: workspace %lld < %lld floats, null or not 8-byte aligned", (long long)ws_elems,
+                (long long)need);
+  hipStream_t st = (hipStream_t)stream;
+  if (wd_on_out) {
+    hipLaunchKernelGGL(adapter_dora_grad_row_kernel, dim3((unsigned)((N + AD_ROWS_WG - 1) / AD_ROWS_WG)), dim3(256), 0, st, dw,
+                       base, p, g, norms, seg);
+  } else {
+    const int nrt = (int)((N + AD_COL_RT - 1) / AD_COL_RT);
+    const dim3 grid((unsigned)((K + AD_COLS_WG - 1) / AD_COLS_WG), (unsigned)nrt);
+    hipLaunchKernelGGL(adapter_dora_grad_col_partial_kernel, grid, dim3(256), 0, st, dw, base, p, (AdSums*)ws, seg);
+    hipLaunchKernelGGL(adapter_dora_grad_col_apply_kernel, grid, dim3(256), 0, st, dw, base, p, g, norms, (const AdSums*)ws,
+                       nrt, seg);
+  }
+  UWU_LAUNCH_CHECK("adapter_dora_grad");
   return UWU_OK;
 }

@@ -151,7 +151,12 @@ class _Adapters:
     ``seg``: registry name of every adapted tensor -> (spec, kind, pa, pb, pc) (offsets into the adapter buffer).  The
     effective weights W + dW live in the bf16 shadow (GEMM operands in bf16 mode) and in ``eff``, an fp32 buffer covering
     only the adapted tensors that are read in fp32: all of them in fp32 mode; norm vectors and the conditioning Linears
-    (fp32 matrix-vector kernels) in bf16 mode.  ``merge`` rewrites both in one uwu_adapter_merge launch."""
+    (fp32 matrix-vector kernels) in bf16 mode.  ``merge`` rewrites both in one uwu_adapter_merge launch.
+
+    Weight decomposition (``dora_wd``): ``dora``: name of every decomposed weight -> (offset of its
+    dora_scale in the adapter buffer, offset of its norms in ``norms``).  Those segments leave the plain table for a second
+    one; ``merge`` then is three launches (plain merge, norms, decomposed merge), and ``norms`` -- refreshed by every merge,
+    not state -- is what the backward of that forward divides by."""
 
     def __init__(self, net, P, fp32_names):
         from .adapters import KIND_LOKR, KIND_LOKR_LOWRANK, KIND_LORA, KIND_NORM
@@ -172,23 +177,68 @@ class _Adapters:
                 self.seg[s.name + ".weight"] = (s, KIND_LOKR, off(s, "lokr_w1"), off(s, "lokr_w2"), 0)
         order = {n: i for i, n in enumerate(P.registry)}
         self.names = sorted(self.seg, key=order.__getitem__)
+        self.dora, n = {}, 0
+        for nm in self.names:
+            s = self.seg[nm][0]
+            if s.dora:
+                self.dora[nm] = (off(s, "dora_scale"), n)
+                n += pad64(s.shape[0] if s.wd_on_out else s.shape[1])
+        self.plain = [nm for nm in self.names if nm not in self.dora]
+        self.norms_n, self.norms = n, None
         self.key = None
         self.eff, self.eff_off = None, {}
         self.version = None
 
     def _table(self, P, eff_off, shadow):
+        """the 13-field rows of the segments without decomposition (None: there is none)"""
         rows, blk = [], [0]
-        for nm in self.names:
-            spec, kind, pa, pb, pc = self.seg[nm]
-            base, shape = P.registry[nm]
-            r_, c_ = (shape[0], shape[1]) if len(shape) == 2 else (1, shape[0])
-            sbits = int.from_bytes(torch.tensor([spec.scale], dtype=torch.float32).numpy().tobytes(), "little")
-            rows.append([kind, r_, c_, base, eff_off.get(nm, -1), base if shadow else -1, pa, pb, pc, spec.r, spec.out_k,
-                         spec.in_n, sbits])
-            blk.append(blk[-1] + -(-(r_ * c_) // 4096))
+        for nm in self.plain:
+            rows.append(self._row(P, nm, eff_off, shadow))
+            blk.append(blk[-1] + -(-(rows[-1][1] * rows[-1][2]) // 4096))
+        if not rows:
+            return None
         dev = P.flat.device
         return (torch.tensor(rows, dtype=torch.int64).to(dev), torch.tensor(blk, dtype=torch.int64).to(dev),
                 len(rows), blk[-1])
+
+    def _row(self, P, nm, eff_off, shadow):
+        spec, kind, pa, pb, pc = self.seg[nm]
+        base, shape = P.registry[nm]
+        r_, c_ = (shape[0], shape[1]) if len(shape) == 2 else (1, shape[0])
+        sbits = int.from_bytes(torch.tensor([spec.scale], dtype=torch.float32).numpy().tobytes(), "little")
+        return [kind, r_, c_, base, eff_off.get(nm, -1), base if shadow else -1, pa, pb, pc, spec.r, spec.out_k, spec.in_n,
+                sbits]
+
+    def _dora_table(self, P, eff_off, shadow):
+        """the 16-field rows of the decomposed segments: (device table, host copy, norms blk_start, norms workgroups,
+        merge blk_start, merge workgroups, segments); None: there is none"""
+        if not self.dora:
+            return None
+        rows, nblk, mblk = [], [0], [0]
+        for nm, (doff, noff) in self.dora.items():
+            by_row = self.seg[nm][0].wd_on_out
+            row = self._row(P, nm, eff_off, shadow) + [doff, noff, int(by_row)]
+            rows.append(row)
+            nblk.append(nblk[-1] + (-(-row[1] // 4) if by_row else -(-row[2] // 64)))
+            mblk.append(mblk[-1] + -(-(row[1] * row[2]) // 4096))
+        dev = P.flat.device
+        host = torch.tensor(rows, dtype=torch.int64)
+        if self.norms is None or self.norms.device != dev:
+            self.norms = torch.empty(max(self.norms_n, 64), device=dev, dtype=torch.float32)
+        return (host.to(dev), host, torch.tensor(nblk, dtype=torch.int64).to(dev), nblk[-1],
+                torch.tensor(mblk, dtype=torch.int64).to(dev), mblk[-1], len(rows))
+
+    def _launch_merge(self, P, tab, dtab, eff, shadow):
+        base, p = L.ptr(P.flat.data), L.ptr(self.net.flat.data)
+        if tab is not None:
+            t, blk, nseg, nblocks = tab
+            L.call("uwu_adapter_merge", base, p, L.ptr(t), L.ptr(blk), nseg, nblocks, L.ptr(eff), L.ptr(shadow), L.stream())
+        if dtab is not None:
+            t, host, nblk, nnb, mblk, nmb, nseg = dtab
+            L.call("uwu_adapter_dora_norms", base, p, L.ptr(t), host.data_ptr(), L.ptr(nblk), nseg, nnb, L.ptr(self.norms),
+                   L.stream())
+            L.call("uwu_adapter_dora_merge", base, p, L.ptr(t), host.data_ptr(), L.ptr(mblk), nseg, nmb, L.ptr(self.norms),
+                   L.ptr(eff), L.ptr(shadow), L.stream())
 
     def prepare(self, P):
         key = (P.flat.device, P.bf16)
@@ -201,26 +251,23 @@ class _Adapters:
                 n += pad64(math.prod(P.registry[nm][1]))
         self.eff = torch.empty(max(n, 64), device=P.flat.device, dtype=torch.float32)
         self.tab = self._table(P, self.eff_off, P.bf16)
+        self.dtab = self._dora_table(P, self.eff_off, P.bf16)
         self.key, self.version = key, None
 
     def needs_merge(self, P):
         return self.key != (P.flat.device, P.bf16) or self.net._dirty or self.version != self.net.flat._version
 
     def merge(self, P):
-        """W_eff = W + dW of every adapted tensor: one launch"""
+        """W_eff = W + dW of every adapted tensor: one launch (with decomposed weights: three)"""
         self.prepare(P)
-        tab, blk, nseg, nblocks = self.tab
-        shadow = P.shadow if P.bf16 else None
-        L.call("uwu_adapter_merge", L.ptr(P.flat.data), L.ptr(self.net.flat.data), L.ptr(tab), L.ptr(blk), nseg, nblocks,
-               L.ptr(self.eff), L.ptr(shadow), L.stream())
+        self._launch_merge(P, self.tab, self.dtab, self.eff, P.shadow if P.bf16 else None)
         self.net._dirty = False
         self.version = self.net.flat._version
 
     def fold(self, P):
         """W += dW in the base fp32 weights themselves (in place: every element is read and written by one thread)"""
-        tab, blk, nseg, nblocks = self._table(P, {nm: P.registry[nm][0] for nm in self.names}, False)
-        L.call("uwu_adapter_merge", L.ptr(P.flat.data), L.ptr(self.net.flat.data), L.ptr(tab), L.ptr(blk), nseg, nblocks,
-               L.ptr(P.flat.data), None, L.stream())
+        eff_off = {nm: P.registry[nm][0] for nm in self.names}
+        self._launch_merge(P, self._table(P, eff_off, False), self._dora_table(P, eff_off, False), P.flat.data, None)
 
     def eff_view(self, P, name):
         first, n = name if isinstance(name, tuple) else (name, 1)
@@ -260,6 +307,20 @@ class _Adapters:
             ops.gemm_wgrad_shared(dy, x, dW, blocks=_wgrad_blocks(x.shape[0], N, K))
         self.grad_rows(P, names, dW)
 
+    def dora_grad(self, P, nm, dW):
+        """decomposed weight `nm`: dW (dL/dW', its rows of the layer's fp32 weight gradient) becomes dL/d(W + dW) in place
+        and dL/d dora_scale is added to the adapter gradient, with the norms of the last merge"""
+        from .adapters import dora_grad_ws_elems
+
+        spec, kind, pa, pb, pc = self.seg[nm]
+        doff, noff = self.dora[nm]
+        rows, K = P.registry[nm][1]
+        n_ws = dora_grad_ws_elems(spec, rows, K)  # (0 with one magnitude per row: a wave sums its own row)
+        ws = torch.empty(n_ws, device=dW.device, dtype=torch.float32) if n_ws else None
+        L.call("uwu_adapter_dora_grad", L.ptr(dW), L.ptr(P.flat.data[P.registry[nm][0]:]), rows, K, kind,
+               L.ptr(self.net.flat.data), L.ptr(self.net.flat.grad), pa, pb, pc, spec.r, spec.out_k, spec.in_n,
+               float(spec.scale), doff, L.ptr(self.norms[noff:]), int(spec.wd_on_out), L.ptr(ws), n_ws, L.stream())
+
     def grad_rows(self, P, names, dW):
         from .adapters import grad_ws_elems
 
@@ -270,6 +331,8 @@ class _Adapters:
             ent = self.seg.get(nm)
             if ent is not None:
                 spec, kind, pa, pb, pc = ent
+                if nm in self.dora:
+                    self.dora_grad(P, nm, dW[row:row + rows])
                 ws = torch.empty(max(grad_ws_elems(spec, rows, K), 1), device=dW.device, dtype=torch.float32)
                 L.call("uwu_adapter_grad", L.ptr(dW[row:row + rows]), rows, K, kind, L.ptr(p), L.ptr(g), pa, pb, pc, spec.r,
                        spec.out_k, spec.in_n, float(spec.scale), L.ptr(ws), ws.numel(), L.stream())
