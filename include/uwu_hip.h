@@ -416,6 +416,11 @@ int uwu_comm_destroy(void* comm);
 int uwu_gemm(const void* A, const void* B, void* C, void* C2, const float* bias, const void* aux,
              int M, int N, int K, int lda, int ldb, int ldc, int ldaux, int transA, int transB, int dtype,
              int c_dtype, int epilogue, int split_k, void* stream);
+/* Name of the kernel family that the most recent GEMM launch of this process went to ("" before the first): "gemm" (128x128),
+ * "gemm_r3_256" / "gemm_r3_128" (ring, 256x128 / 128x128 tiles), "gemm_big" (256x256), "gemm_wide" (192x384), "gemm_m64"
+ * (64x128), "gemm_as" (A-stationary), "gemm_p8" / "gemm_p8n" (8-phase 256x256 / 128x384), and the fp8 / weight-gradient
+ * families' own names.  A static string; for tests that must know which kernel a dispatch rule chose. */
+const char* uwu_gemm_last_kernel(void);
 
 /* fp8 operands (OCP e4m3 / e5m2, BASELINE.json config 5 "fp8 MFMA GEMMs"; the reference has no fp8 path -- its
  * Linear is nn.Linear under bf16 autocast, rope_unet.py:122-166, demo_training_latent.yaml:6):

@@ -10,6 +10,15 @@ import torch
 pytestmark = pytest.mark.gpu
 
 
+def _kernel():
+    """The kernel family the last uwu_gemm launch went to ("gemm" = the 128x128 kernel).  The family tests below assert it on the
+    forced side of every comparison; where a shape does not meet its family's rule the assertion names the kernel that runs on
+    both sides instead (such a case covers that fallback against itself, and is marked "fallback")."""
+    from uwudiff_amd import lib as L
+
+    return L.load().uwu_gemm_last_kernel().decode()
+
+
 def _ref(a, b, ta, tb):
     A = a.float().cpu().double()
     B = b.float().cpu().double()
@@ -72,6 +81,17 @@ def test_gemm_epilogues(dtype):
     from uwudiff_amd import lib as L
     from uwudiff_amd import ops
 
+    from tests import gemm_oracle as O
+
+    def within_bar(got, epi, key, aux=None):
+        """the oracle's bar (tests/test_gemm_epilogue_gpu.py): fp64 on the device's operands, 4 x the fp32 yardstick"""
+        args = (a.cpu(), b.cpu(), bias.cpu(), aux.cpu() if aux is not None else None, False, False, epi)
+        r64, r32 = O.reference(*args), O.reference(*args, dtype=torch.float32)
+        A = r64["A_c"] if key == "c" else None
+        e32, r = O.ratio(got.cpu(), r64[key], r32[key], A=A, bf16_out=dtype == torch.bfloat16)
+        print(f"[gemm-acc] test_gemm_epilogues {dtype} epi {epi} {key}: {r:.2f} (E32 {e32:.1e})")
+        assert r <= 4.0, (epi, key, r)
+
     M, N, K = 260, 384, 128
     a, b = _operands(M, N, K, False, False, dtype, ints=False, seed=2)
     bias = torch.randn(N).cuda()
@@ -82,14 +102,19 @@ def test_gemm_epilogues(dtype):
     u, f = ops.gemm(a, b, bias=bias, epilogue=L.EPI_BIAS_GELU)
     torch.testing.assert_close(u.float().cpu(), ref, **tol)
     torch.testing.assert_close(f.float().cpu(), F.gelu(u.float().cpu(), approximate="tanh"), **tol)
+    within_bar(u, L.EPI_BIAS_GELU, "c")
+    within_bar(f, L.EPI_BIAS_GELU, "c2")
     u, s = ops.gemm(a, b, bias=bias, epilogue=L.EPI_BIAS_SILU)
     torch.testing.assert_close(s.float().cpu(), F.silu(u.float().cpu()), **tol)
+    within_bar(u, L.EPI_BIAS_SILU, "c")
+    within_bar(s, L.EPI_BIAS_SILU, "c2")
     # dgelu: C = (A.B) * gelu'(aux)
     aux = torch.randn(M, N).to(dtype).cuda()
     x = aux.float().cpu().requires_grad_(True)
     F.gelu(x, approximate="tanh").sum().backward()
     d = ops.gemm(a, b, aux=aux, epilogue=L.EPI_DGELU)
     torch.testing.assert_close(d.float().cpu(), _ref(a, b, False, False) * x.grad, **tol)
+    within_bar(d, L.EPI_DGELU, "c", aux=aux)
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
@@ -141,12 +166,20 @@ def test_gemm_r3_matches_128_kernel(M, N, K, c_dtype, monkeypatch):
 
     a, b = _operands(M, N, K, False, False, torch.bfloat16, ints=False, seed=7)
     bias = torch.randn(N, generator=torch.Generator().manual_seed(8)).cuda()
+    # bf16 output: K = 1536 meets the 8-phase kernel's default rule, which comes first on both sides (fallback: gemm_p8 against
+    # itself); at K = 384, N = 1152 the A-stationary kernel takes the two bias epilogues ahead of the ring
+    hot = c_dtype == torch.bfloat16
+    ring = "gemm_p8" if hot and K == 1536 else "gemm_r3_256"
+    with_bias = "gemm_as" if hot and (M, N, K) == (65536, 1152, 384) else ring
     ref, got = _both(monkeypatch, lambda: ops.gemm(a, b, c_dtype=c_dtype))
+    assert _kernel() == ring
     assert torch.equal(ref, got)
     ref, got = _both(monkeypatch, lambda: ops.gemm(a, b, bias=bias, epilogue=L.EPI_BIAS, c_dtype=c_dtype))
+    assert _kernel() == with_bias
     assert torch.equal(ref, got)
     if M * N <= 65536 * 1152:
         (u0, f0), (u1, f1) = _both(monkeypatch, lambda: ops.gemm(a, b, bias=bias, epilogue=L.EPI_BIAS_GELU, c_dtype=c_dtype))
+        assert _kernel() == with_bias
         assert torch.equal(u0, u1) and torch.equal(f0, f1)
 
 
@@ -158,6 +191,7 @@ def test_gemm_r3_exact_integers_and_dgelu(monkeypatch):
     a, b = _operands(M, N, K, False, False, torch.bfloat16, ints=True, seed=9)
     monkeypatch.setenv("UWU_GEMM_R3", "1")
     c = ops.gemm(a, b, c_dtype=torch.float32)
+    assert _kernel() == "gemm_r3_256"
     # exact on integers: compare with a torch fp32 matmul of the same (exactly representable) operands
     want = a.float() @ b.float().t()
     assert torch.equal(c, want)
@@ -169,6 +203,7 @@ def test_gemm_r3_exact_integers_and_dgelu(monkeypatch):
         return (out[0] if isinstance(out, tuple) else out), cs
 
     (d0, s0), (d1, s1) = _both(monkeypatch, run)
+    assert _kernel() == "gemm_r3_256"  # (column sums asked for: not the A-stationary kernel)
     assert torch.equal(d0, d1)
     torch.testing.assert_close(s0, s1, rtol=1e-4, atol=1.0)  # fp32 atomics: order differs
 
@@ -189,10 +224,14 @@ def test_gemm_big_tile_matches_128_kernel(monkeypatch):
     for M, N, K in [(65536, 1536, 384), (33000, 768, 192)]:
         a, b = _operands(M, N, K, False, False, torch.bfloat16, ints=False, seed=31)
         bias = torch.randn(N, generator=torch.Generator().manual_seed(32)).cuda()
+        # (K = 384, M = 65536: the A-stationary kernel takes the two bias epilogues ahead of the 256x256 kernel)
+        biased = "gemm_as" if K == 384 else "gemm_big"
         (u0, f0), (u1, f1) = both(lambda: ops.gemm(a, b, bias=bias, epilogue=L.EPI_BIAS_GELU))
+        assert _kernel() == biased
         assert torch.equal(u0, u1) and torch.equal(f0, f1)
         for kw in ({}, dict(bias=bias, epilogue=L.EPI_BIAS)):
             ref, got = both(lambda: ops.gemm(a, b, **kw))
+            assert _kernel() == (biased if kw else "gemm_big")
             assert torch.equal(ref, got)
         # input gradient with the GELU derivative and the bias-gradient column sums: dy [M, K'] x W [K', N]
         Kc = K
@@ -205,9 +244,11 @@ def test_gemm_big_tile_matches_128_kernel(monkeypatch):
             return (out[0] if isinstance(out, tuple) else out), cs
 
         (d0, s0), (d1, s1) = both(run)
+        assert _kernel() == "gemm_big"
         assert torch.equal(d0, d1)
         torch.testing.assert_close(s0, s1, rtol=1e-3, atol=0.5)  # fp32 atomics: order differs
         ref, got = both(lambda: ops.gemm(dy, w, trans_b=True))
+        assert _kernel() == "gemm_big"
         assert torch.equal(ref, got)
 
 
@@ -229,10 +270,16 @@ def test_gemm_wide_tile_matches_128_kernel(monkeypatch):
         bias = torch.randn(N, generator=torch.Generator().manual_seed(42)).cuda()
         for kw in ({}, dict(bias=bias, epilogue=L.EPI_BIAS)):
             ref, got = both(lambda: ops.gemm(a, b, **kw))
+            # (bias at K = 384, N = 1152, M = 65536: the A-stationary kernel comes first)
+            assert _kernel() == ("gemm_as" if kw and (M, N, K) == (65536, 1152, 384) else "gemm_wide")
             assert torch.equal(ref, got)
+    # fallback: all three meet the 128x384 8-phase kernel's default rule for input gradients (N % 384 == 0, K % 128 == 0, >= 256
+    # tiles), which comes ahead of the ring on both sides: gemm_p8n against itself.  The 192x384 kernel's K-major form is pinned
+    # by tests/test_gemm_epilogue_gpu.py.
     for M, N, K in [(65536, 384, 1152), (50000, 384, 1536), (65536, 1152, 384)]:  # input gradients: dy [M,K] x W [K,N]
         dy, w = _operands(M, N, K, False, True, torch.bfloat16, ints=False, seed=43)
         ref, got = both(lambda: ops.gemm(dy, w, trans_b=True))
+        assert _kernel() == "gemm_p8n"
         assert torch.equal(ref, got)
 
 
@@ -250,13 +297,20 @@ def test_gemm_m64_tile_matches_128_kernel(monkeypatch):
     for M, N, K in [(4096, 384, 384), (4096, 1152, 384), (4000, 1536, 384), (1000, 200, 128)]:
         a, b = _operands(M, N, K, False, False, torch.bfloat16, ints=False, seed=51)
         bias = torch.randn(N, generator=torch.Generator().manual_seed(52)).cuda()
+        # fallback: N = 1152 and 1536 give 288 and 384 tiles of 128x128, not fewer than 256: the 128x128 kernel (forward) and the
+        # 128x128 ring (input gradients) run on both sides
+        m64 = (M + 127) // 128 * ((N + 127) // 128) < 256
+        fwd, dgrad = ("gemm_m64", "gemm_m64") if m64 else ("gemm", "gemm_r3_128")
         for kw in ({}, dict(bias=bias, epilogue=L.EPI_BIAS)):
             ref, got = both(lambda: ops.gemm(a, b, **kw))
+            assert _kernel() == fwd
             assert torch.equal(ref, got)
         (u0, f0), (u1, f1) = both(lambda: ops.gemm(a, b, bias=bias, epilogue=L.EPI_BIAS_GELU))
+        assert _kernel() == fwd
         assert torch.equal(u0, u1) and torch.equal(f0, f1)
         dy, w = _operands(M, N, K, False, True, torch.bfloat16, ints=False, seed=53)  # input gradient: dy [M,K] x W [K,N]
         ref, got = both(lambda: ops.gemm(dy, w, trans_b=True))
+        assert _kernel() == dgrad
         assert torch.equal(ref, got)
         u = (torch.randn(M, N, generator=torch.Generator().manual_seed(54)) * 1.5).bfloat16().cuda()
 
@@ -266,6 +320,7 @@ def test_gemm_m64_tile_matches_128_kernel(monkeypatch):
             return (out[0] if isinstance(out, tuple) else out), cs
 
         (d0, s0), (d1, s1) = both(run)
+        assert _kernel() == dgrad
         assert torch.equal(d0, d1)
         torch.testing.assert_close(s0, s1, rtol=1e-3, atol=0.2)  # fp32 atomics: order differs
 
@@ -347,6 +402,10 @@ def test_gemm_r3_input_gradient_matches_128_kernel(M, N, K, monkeypatch):
 
     a, b = _operands(M, N, K, False, True, torch.bfloat16, ints=False, seed=21)
     ref, got = _both(monkeypatch, lambda: ops.gemm(a, b, trans_b=True))
+    # N = 1536: the 256x256 kernel comes ahead of the ring (against the 128x128 kernel all the same); N = 384, K = 1152 without
+    # an epilogue: fallback, the 128x384 8-phase kernel's default rule takes it on both sides
+    ring = "gemm_big" if N == 1536 else "gemm_r3_256"
+    assert _kernel() == ("gemm_p8n" if (N, K) == (384, 1152) else ring)
     assert torch.equal(ref, got)
     u = (torch.randn(M, N, generator=torch.Generator().manual_seed(22)) * 1.5).bfloat16().cuda()
 
@@ -356,6 +415,7 @@ def test_gemm_r3_input_gradient_matches_128_kernel(M, N, K, monkeypatch):
         return (out[0] if isinstance(out, tuple) else out), cs
 
     (d0, s0), (d1, s1) = _both(monkeypatch, run)
+    assert _kernel() == ring
     assert torch.equal(d0, d1)
     torch.testing.assert_close(s0, s1, rtol=1e-3, atol=0.5)  # fp32 atomics: order differs
 
@@ -397,6 +457,8 @@ def test_gemm_wgrad_many_tiles_xcd_partition(M, N, K, slices, monkeypatch):
 
 # ---- A-stationary kernel (gemm_as_kernel: K = 384, whole 256-row panels, N in 1024..2048): same MFMA sequence per output as
 # the 256x256 kernel it replaces for fc1 + bias + GELU, so both outputs must agree bit for bit (UWU_GEMM_AS=0 = the old path).
+# (fallback: the last case of each of the three lists below has M < 65536 = 256 * 256 and does not meet uwu_gemm_use_as; it runs the
+# 64x128 / 128x128 kernel on both sides)
 @pytest.mark.parametrize("M,N", [(65536, 1536), (65536, 1024), (196608, 1536), (65536, 2048), (1024, 2048)])
 def test_gemm_as_bias_gelu_matches_big_kernel(M, N, monkeypatch):
     from uwudiff_amd import lib as L
@@ -412,6 +474,8 @@ def test_gemm_as_bias_gelu_matches_big_kernel(M, N, monkeypatch):
         h = torch.empty_like(u)
         for _ in range(3):  # the chunk pipeline must not depend on timing
             ops.gemm(a, b, bias=bias, epilogue=L.EPI_BIAS_GELU, out=u, out2=h)
+        if flag == "1":
+            assert _kernel() == ("gemm_as" if M >= 65536 else "gemm_m64")
         outs[flag] = (u.clone(), h.clone())
     assert torch.equal(outs["1"][0], outs["0"][0])
     assert torch.equal(outs["1"][1], outs["0"][1])
@@ -435,6 +499,8 @@ def test_gemm_as_bias_matches_other_kernels(M, N, monkeypatch):
         y = torch.empty(M, N, device="cuda", dtype=torch.bfloat16)
         for _ in range(3):
             ops.gemm(a, b, bias=bias, epilogue=L.EPI_BIAS, out=y)
+        if flag == "1":
+            assert _kernel() == ("gemm_as" if M >= 65536 else "gemm_m64")
         outs[flag] = y.clone()
     assert torch.equal(outs["1"], outs["0"])
 
@@ -459,6 +525,7 @@ def test_gemm_as_dgelu_matches_k_major_kernel(M, N):
     got = torch.empty_like(ref)
     for _ in range(3):
         ops.gemm(dy, w2t, aux=u, epilogue=L.EPI_DGELU, out=got)
+    assert _kernel() == ("gemm_as" if M >= 65536 else "gemm")
     assert torch.equal(got, ref)
 
 
@@ -485,10 +552,12 @@ def test_gemm_as_exact_integers_all_epilogues(N):
     # bias
     y = torch.empty(M, N, device="cuda", dtype=torch.bfloat16)
     ops.gemm(a16, b16, bias=bias, epilogue=L.EPI_BIAS, out=y)
+    assert _kernel() == "gemm_as"
     assert torch.equal(y.float(), ref + bias)
     # bias + GELU: two outputs
     u, h = torch.empty_like(y), torch.empty_like(y)
     ops.gemm(a16, b16, bias=bias, epilogue=L.EPI_BIAS_GELU, out=u, out2=h)
+    assert _kernel() == "gemm_as"
     assert torch.equal(u.float(), ref + bias)
     want = F.gelu(ref + bias, approximate="tanh")
     assert float((h.float() - want).abs().max()) <= 2.0 ** -7 * float(want.abs().max())
@@ -499,6 +568,7 @@ def test_gemm_as_exact_integers_all_epilogues(N):
     aux = (torch.randint(-1, 2, (M, N), generator=g).float() * 10).bfloat16().cuda()
     d = torch.empty_like(y)
     ops.gemm(a16, b16, aux=aux, epilogue=L.EPI_DGELU, out=d)
+    assert _kernel() == "gemm_as"
     fac = torch.where(aux == 0, 0.5, torch.where(aux > 0, 1.0, 0.0)).float()
     torch.testing.assert_close(d.float(), ref * fac, rtol=0, atol=1e-20)
 
@@ -525,10 +595,12 @@ def test_gemm_p8_exact_integers(M, N, K, monkeypatch):
     a, b = _operands(M, N, K, False, False, torch.bfloat16, ints=True, seed=51)
     for _ in range(3):  # repeated launches: the ring's ordering must hold under different timings
         c = ops.gemm(a, b)
+        assert _kernel() == "gemm_p8"
         assert torch.equal(c.float(), (a.float() @ b.float().t()).bfloat16().float())
     dy, w = _operands(M, N, K, False, True, torch.bfloat16, ints=True, seed=52)
     for _ in range(3):
         c = ops.gemm(dy, w, trans_b=True)
+        assert _kernel() == "gemm_p8"
         assert torch.equal(c.float(), (dy.float() @ w.float()).bfloat16().float())
 
 
@@ -541,11 +613,14 @@ def test_gemm_p8_matches_older_kernels(M, N, K, monkeypatch):
     bias = torch.randn(N, generator=torch.Generator().manual_seed(54)).cuda()
     for kw in ({}, dict(bias=bias, epilogue=L.EPI_BIAS)):
         ref, got = _p8_both(monkeypatch, lambda: ops.gemm(a, b, **kw))
+        assert _kernel() == "gemm_p8"
         assert torch.equal(ref, got)
     (u0, f0), (u1, f1) = _p8_both(monkeypatch, lambda: ops.gemm(a, b, bias=bias, epilogue=L.EPI_BIAS_GELU))
+    assert _kernel() == "gemm_p8"
     assert torch.equal(u0, u1) and torch.equal(f0, f1)
     dy, w = _operands(M, N, K, False, True, torch.bfloat16, ints=False, seed=55)
     ref, got = _p8_both(monkeypatch, lambda: ops.gemm(dy, w, trans_b=True))
+    assert _kernel() == "gemm_p8"
     assert torch.equal(ref, got)
     u = (torch.randn(M, N, generator=torch.Generator().manual_seed(56)) * 1.5).bfloat16().cuda()
 
@@ -555,9 +630,11 @@ def test_gemm_p8_matches_older_kernels(M, N, K, monkeypatch):
         return (out[0] if isinstance(out, tuple) else out), cs
 
     (d0, s0), (d1, s1) = _p8_both(monkeypatch, run)
+    assert _kernel() == "gemm_p8"
     assert torch.equal(d0, d1)
     torch.testing.assert_close(s0, s1, rtol=1e-3, atol=0.5)  # fp32 atomics: order differs
     ref, got = _p8_both(monkeypatch, lambda: ops.gemm(dy, w, trans_b=True, aux=u, epilogue=L.EPI_DGELU))
+    assert _kernel() == "gemm_p8"
     assert torch.equal(ref, got)
 
 
@@ -570,12 +647,19 @@ def test_gemm_p8_bench_shape_exact(monkeypatch):
     want = (a.float() @ b.float().t()).bfloat16()
     for _ in range(2):
         assert torch.equal(ops.gemm(a, b), want)
+        assert _kernel() == "gemm_p8"
 
 
 # ---- 128 x 384 sibling (gemm_p8n.hip): N a multiple of 384 -- the N = 384 / 1152 Linears of DiT-S/2 and DiT-XL/2 -------------
 # UWU_GEMM_P8N=1 forces it on any shape it can run, =0 keeps the older kernels (UWU_GEMM_P8=0 as well: N = 768 / 1536 would go
 # to the 256 x 256 kernel first).  Same MFMA sequence per output element as every other bf16 kernel: bit-identical results.
+# (fallback: N = 768 and 1536 are multiples of 256, which dispatch keeps off this kernel: with UWU_GEMM_P8=0 those two shapes run the
+# 64x128 kernel on both sides)
 P8N_SHAPES = [(4096, 384, 384), (2048, 1152, 1536), (1000, 768, 256), (777, 384, 1152), (300, 1536, 640), (66000, 384, 384)]
+
+
+def _p8n_kernel(N):
+    return "gemm_p8n" if N % 256 else "gemm_m64"
 
 
 def _p8n_both(monkeypatch, fn):
@@ -595,10 +679,12 @@ def test_gemm_p8n_exact_integers(M, N, K, monkeypatch):
     a, b = _operands(M, N, K, False, False, torch.bfloat16, ints=True, seed=71)
     for _ in range(3):  # repeated launches: the ring's ordering must hold under different timings
         c = ops.gemm(a, b)
+        assert _kernel() == _p8n_kernel(N)
         assert torch.equal(c.float(), (a.float() @ b.float().t()).bfloat16().float())
     dy, w = _operands(M, N, K, False, True, torch.bfloat16, ints=True, seed=72)
     for _ in range(3):
         c = ops.gemm(dy, w, trans_b=True)
+        assert _kernel() == _p8n_kernel(N)
         assert torch.equal(c.float(), (dy.float() @ w.float()).bfloat16().float())
 
 
@@ -611,11 +697,14 @@ def test_gemm_p8n_matches_older_kernels(M, N, K, monkeypatch):
     bias = torch.randn(N, generator=torch.Generator().manual_seed(74)).cuda()
     for kw in ({}, dict(bias=bias, epilogue=L.EPI_BIAS)):
         ref, got = _p8n_both(monkeypatch, lambda: ops.gemm(a, b, **kw))
+        assert _kernel() == _p8n_kernel(N)
         assert torch.equal(ref, got)
     (u0, f0), (u1, f1) = _p8n_both(monkeypatch, lambda: ops.gemm(a, b, bias=bias, epilogue=L.EPI_BIAS_GELU))
+    assert _kernel() == _p8n_kernel(N)
     assert torch.equal(u0, u1) and torch.equal(f0, f1)
     dy, w = _operands(M, N, K, False, True, torch.bfloat16, ints=False, seed=75)
     ref, got = _p8n_both(monkeypatch, lambda: ops.gemm(dy, w, trans_b=True))
+    assert _kernel() == _p8n_kernel(N)
     assert torch.equal(ref, got)
 
 

@@ -2,6 +2,8 @@
 
 fp32 compute mode: <= 1e-3 relative (north-star bar).  bf16 mode: own tolerance.  The oracle itself is structurally
 pinned by the public SDXL parameter count (tests/test_unet_cpu.py)."""
+import gc
+
 import pytest
 import torch
 
@@ -135,6 +137,9 @@ def test_unet_gradient_checkpointing_same_gradients_less_memory():
     def run(ckpt):
         model.enable_gradient_checkpointing(ckpt)
         model.flat.grad = torch.zeros_like(model.flat.data)
+        # (garbage of earlier tests -- device tensors held only by reference cycles -- is freed whenever Python's collector happens to
+        # run; inside the forward that would be subtracted from `held`, so it goes now, as in test_lycoris_gpu / test_conv_gpu)
+        gc.collect()
         torch.cuda.synchronize()
         torch.cuda.reset_peak_memory_stats()
         base = torch.cuda.memory_allocated()

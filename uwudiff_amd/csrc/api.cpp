@@ -3,6 +3,8 @@
 #include <stdarg.h>
 #include <stdio.h>
 
+#include <atomic>
+
 #include "../../include/uwu_hip.h"
 
 static thread_local char g_err[512] = "";
@@ -21,6 +23,10 @@ extern "C" int uwu_version(void) { return 1; }
 static int g_env_gen = 0;
 int uwu_env_generation() { return g_env_gen; }
 extern "C" int uwu_env_refresh(void) { return ++g_env_gen; }
+
+// kernel family of the most recent gemm_launch() (gemm_shared.h): one host store per launch, read by the tests
+std::atomic<const char*> g_uwu_gemm_last_kernel{""};
+extern "C" const char* uwu_gemm_last_kernel(void) { return g_uwu_gemm_last_kernel.load(std::memory_order_relaxed); }
 
 extern "C" int uwu_memset_zero(void* p, uint64_t bytes, void* stream) {
   if (!p || !bytes) {

@@ -777,7 +777,8 @@ int launch_r3(GemmArgs g, hipStream_t st) {
   g.tiles_n = (g.N + 127) / 128;
   GemmProf prof = gemm_prof(g, TB, sizeof(TC));
   if (CONV) prof = {UWU_PROF_CONV, 0, 2.0 * g.M * g.N * g.K, ((double)g.M * g.K / 9 + (double)g.N * g.K + (double)g.M * g.N) * 2};
-  return gemm_launch<gemm_r3_kernel<TC, EPI, TB, FI, CONV>>("gemm_r3", LDS, dim3(g.tiles_m * g.tiles_n), 256, st, prof, g);
+  return gemm_launch<gemm_r3_kernel<TC, EPI, TB, FI, CONV>>(FI == 8 ? "gemm_r3_256" : "gemm_r3_128", LDS,  // 256x128 / 128x128 tiles
+                                                           dim3(g.tiles_m * g.tiles_n), 256, st, prof, g);
 }
 template <typename TC, int EPI, bool TB>
 int launch_big(GemmArgs g, hipStream_t st) {

@@ -5,6 +5,7 @@
 #pragma once
 #include <stdlib.h>
 
+#include <atomic>
 #include <type_traits>
 
 #include "common.h"
@@ -14,6 +15,10 @@
     const int rc_ = (__VA_ARGS__); \
     if (rc_ != UWU_OK) return rc_; \
   } while (0)
+
+// Name of the kernel family of the most recent gemm_launch() of any translation unit (api.cpp; uwu_gemm_last_kernel()).
+// Atomic only so that launches from two host threads do not race on it; relaxed: it orders nothing.
+extern std::atomic<const char*> g_uwu_gemm_last_kernel;
 
 struct GemmArgs {
   const void* A;
@@ -496,6 +501,7 @@ static GemmProf gemm_prof(const GemmArgs& g, bool tb, int esc) {
 template <auto KERN, typename... Args>
 int gemm_launch(const char* name, int lds, dim3 grid, int block, hipStream_t st, const GemmProf& p, const Args&... args) {
   RETURN_IF(gemm_lds_optin<KERN>(name, lds));
+  g_uwu_gemm_last_kernel.store(name, std::memory_order_relaxed);
   UwuProfScope prof(st);
   hipLaunchKernelGGL(KERN, grid, dim3(block), lds, st, args...);
   prof.done(p.tag, p.kind, p.flops, p.bytes);

@@ -105,6 +105,7 @@ _SIGS = {
     "uwu_allreduce_flat": (c_int, [P, P, c_int64, P]),
     "uwu_comm_destroy": (c_int, [P]),
     "uwu_gemm": (c_int, [P, P, P, P, P, P] + [c_int] * 13 + [P]),
+    "uwu_gemm_last_kernel": (c_char_p, []),
     "uwu_gemm_fp8_scratch_bytes": (ctypes.c_size_t, [c_int, c_int, c_int]),
     "uwu_gemm_fp8": (c_int, [P, P, P, P, P, P] + [c_int] * 9 + [P, P, P, ctypes.c_size_t, P]),
     "uwu_fp8_amax": (c_int, [P, c_int, c_int64, P, P]),
