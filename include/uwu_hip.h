@@ -262,6 +262,39 @@ int uwu_adamw_fp16_step(float* p, float* g, void* m16, void* v16, void* p_bf16, 
  * element alignment. */
 int uwu_param_decay(float* p, void* p_bf16, int64_t n, double factor, void* stream);
 
+/* AdamW with 8-bit block-wise moments: the state layout of bitsandbytes.optim.AdamW8bit (Dettmers et al. 2022, "8-bit Optimizers
+ * via Block-wise Quantization") on flat buffers.  The package is not a dependency: the rule is restated here.
+ *
+ * State: state1 / state2 hold one uint8 code per element, absmax1 / absmax2 one fp32 scale per block, qmap1 / qmap2 the code
+ * tables: 256 fp32 values each, strictly increasing, within [-1, 1] (the package's signed / unsigned dynamic maps; the kernel
+ * assumes nothing else about them).  Block b covers elements [256 b, 256 b + 256) counted from the buffer's start; the last
+ * block may be partial.  All pointers are the buffers' BASE pointers; the launch updates the element range [e0, e1) of the n
+ * elements, e0 a multiple of 256, e1 a multiple of 256 or equal to n.  Per block, in one pass:
+ *   m = qmap1[state1] * absmax1[b] ; v = qmap2[state2] * absmax2[b]
+ *   g = g * pre_scale * clip[1]                            (clip may be NULL; the fp32 factor of uwu_adamw_step)
+ *   p *= 1 - lr*wd ; m = m + (g - m) * (1-beta1) ; v = beta2*v + (1-beta2)*g*g
+ *   p -= lr/(1-beta1^step) * m / (sqrt(v)/sqrt(1-beta2^step) + eps)        (the unrounded fp32 m and v)
+ *   absmax1[b] = max |m| ; absmax2[b] = max v               over the block's elements inside the buffer
+ *   state1 = the index of the entry of qmap1 nearest to m / absmax1[b], a tie to the lower index; state2 likewise
+ *   a block whose new absmax is 0 gets the code of the entry nearest to 0 (127 / 0 in the package's maps) and absmax 0
+ * p_bf16 (may be NULL) is refreshed, zero_grad leaves g zeroed, step is the 1-based step count.  The hyper-parameters are
+ * doubles: 1 - beta, 1 - lr*wd and the bias corrections are formed in double on the host (see uwu_lion_step).
+ * Not reproduced from the package: it applies the weight decay after the update (O(lr^2 wd) per step apart) and moves a first-
+ * moment code whose sign differs from the value's to its neighbour after quantising.
+ * No atomics, and a block's result does not depend on the grid or on the range it was launched in: the same inputs give the
+ * same bits.  p, g 16-byte aligned; codes, absmax and tables 4-byte aligned; p_bf16 8-byte aligned.
+ * 10 B read + 6 B written per parameter (+ 2 B for the shadow, + 4 B for the zeroed gradient). */
+int uwu_adamw8_step(float* p, float* g, void* state1, void* state2, float* absmax1, float* absmax2, const float* qmap1,
+                    const float* qmap2, void* p_bf16, int64_t n, int64_t e0, int64_t e1, double lr, double beta1, double beta2,
+                    double eps, double weight_decay, int step, float pre_scale, const float* clip, int zero_grad, void* stream);
+
+/* Lion with an 8-bit block-wise moment (bitsandbytes.optim.Lion8bit's state layout): the step of uwu_lion_step with
+ * m = qmap1[state1] * absmax1[b] before it and absmax1[b] = max |m|, state1 = nearest entry of m / absmax1[b] after it.  Blocks,
+ * base pointers, the range [e0, e1), alignment and determinism as in uwu_adamw8_step. */
+int uwu_lion8_step(float* p, float* g, void* state1, float* absmax1, const float* qmap1, void* p_bf16, int64_t n, int64_t e0,
+                   int64_t e1, double lr, double beta1, double beta2, double weight_decay, float pre_scale, const float* clip,
+                   int zero_grad, void* stream);
+
 /* prodigyopt.Prodigy (Mishchenko & Defazio, "Prodigy: An Expeditiously Adaptive Parameter-Free Learner") on flat buffers: a
  * step is uwu_prodigy_stats per chunk, then uwu_prodigy_finalize, then uwu_prodigy_apply, all on one stream, nothing read back.
  * With g = g * pre_scale * clip[1] (clip may be NULL; the fp32 factor of uwu_adamw_step), the package's step is

@@ -1,8 +1,9 @@
-"""The flat-buffer update kernels (AdamW, Lion, AdamWFP16 and Prodigy's three: uwudiff_amd/csrc/optimizer.hip) alone, with the bf16
+"""The flat-buffer update kernels (AdamW, Lion, AdamWFP16, the 8-bit block-wise AdamW and Lion, and Prodigy's three:
+uwudiff_amd/csrc/optimizer.hip) alone, with the bf16
 shadow and ``zero_grad`` on, at DiT-S/2's parameter count and at the SDXL-shape UNet's 2.57 G: ms per launch, bytes moved per
 parameter and GB/s, and the optimizer-state bytes of the SDXL-shape UNet under each optimizer.  Prodigy is shown as its statistics
 pass, its one-workgroup finalize and its apply pass separately, and as the whole step (the three on one stream), next to the AdamW
-kernel of the same run.  One JSON line.  DESIGN.md sections 4.28 and 4.36.
+kernel of the same run.  One JSON line.  DESIGN.md sections 4.28, 4.36 and 4.40.
 
     python tools/bench_optim.py [--sizes 32966464,2570000000] [--reps 5] [--warmup 3]
 
@@ -18,7 +19,9 @@ sys.path.insert(0, ROOT)
 
 DIT_S2, SDXL_UNET = 32_966_464, 2_570_000_000
 # bytes per parameter: (read + written by the update rule, optimizer state held)
-KERNELS = {"adamw": (16 + 12, 8), "lion": (12 + 8, 4), "adamw_fp16": (12 + 8, 4)}
+KERNELS = {"adamw": (16 + 12, 8), "lion": (12 + 8, 4), "adamw_fp16": (12 + 8, 4),
+           # 8-bit codes + one fp32 scale per 256 elements and moment (the scales' traffic, 1/32 B per parameter, is left out)
+           "adamw8": (10 + 6, 2 + 8 / 256), "lion8": (9 + 5, 1 + 4 / 256)}
 EXTRA = 2 + 4  # bf16 shadow written, consumed gradient zeroed
 # Prodigy's passes: bytes per parameter with the extras (statistics: p, g, p0, exp_avg, exp_avg_sq, s read, the three moments
 # written, + 4 for the zeroed gradient; apply: p, exp_avg, exp_avg_sq read, p written, + 2 for the shadow); 16 B of state
@@ -41,6 +44,24 @@ def bench_size(n, reps, warmup):
     st = {"adamw": (f32().zero_(), f32().zero_()), "lion": (f32().zero_(),),
           "adamw_fp16": (torch.zeros(n, device=dev, dtype=torch.float16), torch.zeros(n, device=dev, dtype=torch.float16))}
     s = L.stream()
+    from uwudiff_amd.optim import dynamic_map
+
+    nb = (n + 255) // 256
+    q1, q2 = dynamic_map(True).to(dev), dynamic_map(False).to(dev)
+    c8 = lambda: torch.zeros(n, device=dev, dtype=torch.uint8)  # noqa: E731
+    am = lambda: torch.zeros(nb, device=dev, dtype=torch.float32)  # noqa: E731
+    st["adamw8"] = (c8(), c8(), am(), am())
+    st["lion8"] = (c8(), am())
+
+    def spread(name):
+        """codes drawn uniformly over the table and unit scales, put there before every timed window: every kernel leaves g zeroed,
+        and the zero state would send all 64 lanes of a wave down the same path of the table search (no LDS bank conflicts).  With
+        g = 0 a block's moments shrink by one factor, so the ratios and the codes stay as spread as they were drawn."""
+        for t in st[name]:
+            if t.dtype == torch.uint8:
+                t.random_(0, 256)
+            else:
+                t.fill_(1.0)
     launch = {
         "adamw": lambda k: L.call("uwu_adamw_step", L.ptr(p), L.ptr(g), L.ptr(st["adamw"][0]), L.ptr(st["adamw"][1]),
                                   L.ptr(shadow), n, 1e-6, 0.9, 0.999, 1e-8, 0.01, k, 1.0, None, 1, s),
@@ -48,6 +69,10 @@ def bench_size(n, reps, warmup):
                                  0.01, 1.0, None, 1, s),
         "adamw_fp16": lambda k: L.call("uwu_adamw_fp16_step", L.ptr(p), L.ptr(g), L.ptr(st["adamw_fp16"][0]),
                                        L.ptr(st["adamw_fp16"][1]), L.ptr(shadow), n, 1e-6, 0.9, 0.999, 1e-8, k, 1.0, None, 1, s),
+        "adamw8": lambda k: L.call("uwu_adamw8_step", L.ptr(p), L.ptr(g), *(L.ptr(t) for t in st["adamw8"]), L.ptr(q1), L.ptr(q2),
+                                   L.ptr(shadow), n, 0, n, 1e-6, 0.9, 0.999, 1e-8, 0.01, k, 1.0, None, 1, s),
+        "lion8": lambda k: L.call("uwu_lion8_step", L.ptr(p), L.ptr(g), *(L.ptr(t) for t in st["lion8"]), L.ptr(q1),
+                                  L.ptr(shadow), n, 0, n, 1e-6, 0.9, 0.99, 0.01, 1.0, None, 1, s),
     }
     # Prodigy on moments of its own, with the demo config's options (bias correction, safeguard, decoupled decay)
     pm, pv, ps, p0 = f32().zero_(), f32().zero_(), f32().zero_(), p.clone()
@@ -74,6 +99,8 @@ def bench_size(n, reps, warmup):
     ms = {name: [] for name in launch}
     for _ in range(reps):
         for name, fn in launch.items():
+            if name in ("adamw8", "lion8"):
+                spread(name)
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
             for k in range(iters):
@@ -93,6 +120,8 @@ def bench_size(n, reps, warmup):
         raise SystemExit("bench_optim.py: Prodigy's last step returned early (d_denom == 0): its apply pass did no work")
     for name in ("prodigy_stats", "prodigy_apply"):  # plain streams: to be judged against the AdamW kernel of this run
         out[name]["GBps_vs_adamw"] = round(out[name]["GBps"] / out["adamw"]["GBps"], 3)
+    for name, ref in (("adamw8", "adamw"), ("lion8", "lion")):  # the 8-bit step against the fp32 step of the same run
+        out[name]["ms_vs_" + ref] = round(out[name]["ms"] / out[ref]["ms"], 3)
     return {"n": n, "launches_per_window": iters, "reps": reps, "kernels": out}
 
 
@@ -107,7 +136,7 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("bench_optim.py measures on the GPU; there is no CPU path")
     res = {"sizes": [bench_size(int(n), a.reps, a.warmup) for n in a.sizes.split(",")],
-           "state_bytes_sdxl_unet": {**{name: state * SDXL_UNET for name, (_, state) in KERNELS.items()},
+           "state_bytes_sdxl_unet": {**{name: int(state * SDXL_UNET) for name, (_, state) in KERNELS.items()},
                                      "prodigy": PRODIGY_STATE * SDXL_UNET},
            "weights_bytes_sdxl_unet": 4 * SDXL_UNET}
     for r in res["sizes"]:

@@ -84,6 +84,8 @@ _SIGS = {
     "uwu_adamw_fp16_step": (c_int, [P, P, P, P, P, c_int64, c_double, c_double, c_double, c_double, c_int, c_float, P,
                                     c_int, P]),
     "uwu_param_decay": (c_int, [P, P, c_int64, c_double, P]),
+    "uwu_adamw8_step": (c_int, [P] * 9 + [c_int64] * 3 + [c_double] * 5 + [c_int, c_float, P, c_int, P]),
+    "uwu_lion8_step": (c_int, [P] * 6 + [c_int64] * 3 + [c_double] * 4 + [c_float, P, c_int, P]),
     "uwu_prodigy_stats_blocks": (c_int, [c_int64]),
     "uwu_prodigy_stats": (c_int, [P] * 6 + [c_int64, P, P, c_int64, c_int64] + [c_double] * 5 + [c_int, c_double, c_int, c_int,
                                   c_float, P, c_int, P]),

@@ -4,7 +4,9 @@
 YAML, reference src/duwu/trainer/trainer.py:52-74, configs/demo_training_latent.yaml:30-39), ``FusedLion`` is
 ``lion_pytorch.Lion`` (the commented alternative of the reference's training YAMLs) and ``FusedAdamWFP16`` the reference's own
 ``duwu.trainer.optimizers.AdamWFP16`` (src/duwu/trainer/optimizers.py); ``FusedProdigy`` is ``prodigyopt.Prodigy``, whose step
-size comes from two sums over all parameters kept on the device.  ``FlatFusedOptimizer`` is what they share and what
+size comes from two sums over all parameters kept on the device; ``FusedAdamW8bit`` / ``FusedLion8bit`` keep the moments as 8-bit
+codes with one scale per block of 256 elements (the state layout of ``bitsandbytes.optim.AdamW8bit`` / ``Lion8bit``).
+``FlatFusedOptimizer`` is what they share and what
 the trainer's fused path asks for: Lightning's ``gradient_clip_val`` (global L2 norm, demo_training.yaml:12) as a device
 coefficient, one launch per flat parameter buffer (or per reduced chunk of it), the consumed gradient zeroed and the bf16
 shadow of the parameters (MFMA operands) refreshed by the same kernel.
@@ -332,6 +334,190 @@ class FusedProdigy(FlatFusedOptimizer):
     def d(self):
         """The current step size estimate.  Reads the device scalar: a host synchronisation, meant for logging only."""
         return self.scalars()["d"]
+
+
+QBLOCK = 256  # elements per quantisation block of the 8-bit state (one wave at 4 elements per lane in the kernels)
+
+
+def dynamic_map(signed):
+    """The 256-entry code table of the 8-bit state, a restatement of bitsandbytes' ``create_dynamic_map(signed,
+    max_exponent_bits=7, total_bits=8)``: for each of 7 decades i the midpoints of ``linspace(0.1, 1, 2**i + 1)`` (unsigned:
+    ``2**(i + 1) + 1``) times ``10**(i - 6)``, with both signs when signed, plus 0 and 1, sorted.  fp32, strictly increasing.
+    Host only: needs no GPU."""
+    data = [0.0, 1.0]
+    for i in range(7):
+        k = 2 ** i + 1 if signed else 2 ** (i + 1) + 1
+        edges = [0.1 + 0.9 * j / (k - 1) for j in range(k)]
+        for lo, hi in zip(edges[:-1], edges[1:]):
+            v = 10.0 ** (i - 6) * ((lo + hi) / 2)
+            data += [v, -v] if signed else [v]
+    assert len(data) == 256
+    return torch.tensor(sorted(data), dtype=torch.float64).to(torch.float32)
+
+
+class BlockSchedule:
+    """Which quantisation blocks of an ``n``-element buffer may be updated, given the chunks handed over so far.  A block is given
+    out once, as part of a maximal run of whole blocks, and only when the chunks seen cover all of it: chunk offsets are multiples
+    of 4 elements, not of the block, and arrive in any order, so a block can straddle two chunks.  Pure python: needs no GPU."""
+
+    def __init__(self, n, block=QBLOCK):
+        self.n, self.block = int(n), int(block)
+        self.covered = []  # disjoint element ranges [a, b) the chunks cover, sorted, touching ones merged
+        self.done = []  # the same of the ranges given out
+
+    @staticmethod
+    def _merged(ranges):
+        out = []
+        for a, b in sorted(ranges):
+            if out and a <= out[-1][1]:
+                out[-1] = (out[-1][0], max(out[-1][1], b))
+            else:
+                out.append((a, b))
+        return out
+
+    def add(self, off, ln):
+        """chunk [off, off + ln) has arrived: the element ranges [(e0, e1), ...] to launch now (whole blocks; e1 may be n)"""
+        a, b = int(off), int(off) + int(ln)
+        if not 0 <= a < b <= self.n:
+            raise ValueError(f"chunk [{a}, {b}) reaches outside the buffer of {self.n} elements")
+        self.covered = self._merged(self.covered + [(a, b)])
+        a, b = next((x, y) for x, y in self.covered if x <= a and b <= y)  # the covered run the chunk now belongs to
+        e0 = -(-a // self.block) * self.block
+        e1 = b if b == self.n else b // self.block * self.block
+        out, cur = [], e0
+        for x, y in self.done:
+            if y <= cur or x >= e1:
+                continue
+            if x > cur:
+                out.append((cur, x))
+            cur = y
+        if cur < e1:
+            out.append((cur, e1))
+        self.done = self._merged(self.done + out)
+        return out
+
+    def pending(self):
+        """the element ranges chunks have touched that no launch has updated: the blocks only partly covered"""
+        out = []
+        for a, b in self.covered:
+            cur = a
+            for x, y in self.done:
+                if y <= cur or x >= b:
+                    continue
+                if x > cur:
+                    out.append((cur, x))
+                cur = y
+            if cur < b:
+                out.append((cur, b))
+        return out
+
+
+class _Flat8bit(FlatFusedOptimizer):
+    """What the 8-bit optimizers share: the state of ``MOMENTS`` moments as uint8 codes (``state1``, ``state2``), one fp32 scale
+    per block of 256 elements (``absmax1``, ``absmax2``) and the code tables (``qmap1``, ``qmap2``) under the package's keys, the
+    launches over whole blocks whatever the chunking, and the way back to uint8 after ``load_state_dict``."""
+
+    MOMENTS = ()  # ((key suffix, signed table), ...)
+
+    def __init__(self, params, defaults, name, percentile_clipping=100, block_wise=True, is_paged=False):
+        if percentile_clipping != 100:
+            raise NotImplementedError(f"{name}: percentile_clipping is not implemented")
+        if not block_wise:
+            raise NotImplementedError(f"{name}: block_wise=False is not implemented")
+        if is_paged:
+            raise NotImplementedError(f"{name}: is_paged=True is not implemented")
+        super().__init__(params, defaults)
+        self._sched = {}
+        self.register_load_state_dict_post_hook(_Flat8bit._codes_to_uint8)
+
+    def _codes_to_uint8(self):
+        """torch's ``load_state_dict`` casts every state tensor of a floating-point parameter to the parameter's dtype: the
+        restored codes arrive as fp32 holding 0..255, so the way back is lossless"""
+        for st in self.state.values():
+            for k in ("state1", "state2"):
+                if k in st and st[k].dtype != torch.uint8:
+                    st[k] = st[k].to(torch.uint8)
+
+    def _init_state(self, p, st):
+        blocks = -(-p.numel() // QBLOCK)
+        for k, signed in self.MOMENTS:
+            st["state" + k] = _zeros_like(p.data, dtype=torch.uint8)
+            st["absmax" + k] = _zeros_like(p.data[:blocks])  # 0: every code reads as 0
+            st["qmap" + k] = dynamic_map(signed).to(p.device)
+
+    def _launch_blocks(self, group, st, p_ptr, g_ptr, shadow_ptr, e0, e1, pre_scale, clip_ptr, zero_grad):
+        raise NotImplementedError
+
+    def _launch(self, group, st, p_ptr, g_ptr, shadow_ptr, off, ln, pre_scale, clip_ptr, zero_grad):
+        # the kernels take base pointers and a range of whole blocks: a block is launched once the chunks seen cover all of it
+        sched = self._sched.get(id(st))
+        if sched is None:
+            sched = self._sched[id(st)] = BlockSchedule(st["state1"].numel())
+        base_shadow = shadow_ptr - 2 * off if shadow_ptr is not None else None
+        for e0, e1 in sched.add(off, ln):
+            self._launch_blocks(group, st, p_ptr - 4 * off, g_ptr - 4 * off, base_shadow, e0, e1, pre_scale, clip_ptr, zero_grad)
+
+    def _finish(self, group, p, st, shadow):
+        sched = self._sched.pop(id(st), None)
+        left = sched.pending() if sched is not None else []
+        if left:
+            raise ValueError(f"{type(self).__name__}: the chunks leave blocks of {QBLOCK} elements partly covered (elements {left}); "
+                             f"their gradient was consumed by no launch")
+
+    @torch.no_grad()
+    def step(self, *args, **kwargs):
+        self._sched = {}  # (a step that raised between its launches leaves no schedule behind)
+        return super().step(*args, **kwargs)
+
+
+class FusedAdamW8bit(_Flat8bit):
+    """``bitsandbytes.optim.AdamW8bit`` on a flat buffer: AdamW whose two moments are kept as 8-bit codes of a 256-entry dynamic
+    table with one fp32 scale per block of 256 elements (2.03 B of state per parameter instead of 8).  The rule is written out at
+    ``uwu_adamw8_step`` (include/uwu_hip.h); the package is not installed here, so checkpoint interchange with it is not verified.
+
+    Blocks are counted from the start of the flat buffer and ignore tensor boundaries inside it.  ``min_8bit_size`` (the package
+    keeps smaller tensors in fp32) is accepted and ignored: every element of the buffer is quantised.  ``optim_bits`` and ``args``
+    are accepted for the signature and ignored; ``amsgrad``, ``percentile_clipping``, ``block_wise=False`` and ``is_paged`` are not
+    implemented."""
+
+    MOMENTS = (("1", True), ("2", False))
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False, optim_bits=32,
+                 args=None, min_8bit_size=4096, percentile_clipping=100, block_wise=True, is_paged=False):
+        if amsgrad:
+            raise NotImplementedError("FusedAdamW8bit: amsgrad=True is not implemented")
+        super().__init__(params, dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay), "FusedAdamW8bit",
+                         percentile_clipping, block_wise, is_paged)
+
+    def _init_state(self, p, st):
+        st["step"] = 0
+        super()._init_state(p, st)
+
+    def _launch_blocks(self, group, st, p_ptr, g_ptr, shadow_ptr, e0, e1, pre_scale, clip_ptr, zero_grad):
+        b1, b2 = group["betas"]
+        L.call("uwu_adamw8_step", p_ptr, g_ptr, L.ptr(st["state1"]), L.ptr(st["state2"]), L.ptr(st["absmax1"]),
+               L.ptr(st["absmax2"]), L.ptr(st["qmap1"]), L.ptr(st["qmap2"]), shadow_ptr, st["state1"].numel(), e0, e1,
+               float(group["lr"]), b1, b2, group["eps"], group["weight_decay"], st["step"], pre_scale, clip_ptr, zero_grad,
+               L.stream())
+
+
+class FusedLion8bit(_Flat8bit):
+    """``bitsandbytes.optim.Lion8bit`` on a flat buffer: ``FusedLion`` whose moment is kept as 8-bit codes of the signed dynamic
+    table with one fp32 scale per block of 256 elements (``uwu_lion8_step``).  Blocks, ``min_8bit_size`` and what is not
+    implemented as in ``FusedAdamW8bit``."""
+
+    MOMENTS = (("1", True),)
+
+    def __init__(self, params, lr=1e-4, betas=(0.9, 0.99), weight_decay=0, min_8bit_size=4096, percentile_clipping=100,
+                 block_wise=True, is_paged=False):
+        super().__init__(params, dict(lr=lr, betas=tuple(betas), weight_decay=weight_decay), "FusedLion8bit",
+                         percentile_clipping, block_wise, is_paged)
+
+    def _launch_blocks(self, group, st, p_ptr, g_ptr, shadow_ptr, e0, e1, pre_scale, clip_ptr, zero_grad):
+        b1, b2 = group["betas"]
+        L.call("uwu_lion8_step", p_ptr, g_ptr, L.ptr(st["state1"]), L.ptr(st["absmax1"]), L.ptr(st["qmap1"]), shadow_ptr,
+               st["state1"].numel(), e0, e1, float(group["lr"]), b1, b2, group["weight_decay"], pre_scale, clip_ptr, zero_grad,
+               L.stream())
 
 
 def cosine_lr(base_lr, step, T_max, eta_min):
