@@ -424,6 +424,37 @@ int uwu_adapter_dora_merge(const float* base, const float* p, const int64_t* tab
 int uwu_adapter_dora_grad(float* dw, const float* base, int64_t N, int64_t K, int kind, const float* p, float* g, int64_t pa,
                           int64_t pb, int64_t pc, int r, int out_k, int in_n, float scale, int64_t dora_off,
                           const float* norms, int wd_on_out, float* ws, int64_t ws_elems, void* stream);
+/* Convolution adapters on a 3x3 convolution weight stored [cout_store, 9, cin_store] (tap-major,
+ * channel-contiguous; rows >= cout and channels >= cin are padding: they hold zeros, get delta 0 and no gradient).  The
+ * adapter tensors are stored tap-major too, in the TRUE sizes (no padding), scale as above:
+ *   UWU_ADAPTER_CONV_LORA           delta[o,t,c] = scale sum_i up[o,i] down[i,t,c]     up = p+pa [cout, r], down = p+pb [r, 9, cin]
+ *   UWU_ADAPTER_CONV_TUCKER         as CONV_LORA with down := T,  T[i,t,c] = sum_j mid[i,t,j] dn[j,c]
+ *                                                                 up = p+pa [cout, r], dn = p+pb [r, cin], mid = p+pc [r, 9, r]
+ *   UWU_ADAPTER_CONV_LOKR           delta[a out_k + k, t, b in_n + l] = scale w1[a,b] w2[k,t,l]
+ *                                                                 w1 = p+pa [cout/out_k, cin/in_n], w2 = p+pb [out_k, 9, in_n]
+ *   UWU_ADAPTER_CONV_LOKR_LOWRANK   as CONV_LOKR with w2 = w2_a w2_b                   w2_a = p+pb [out_k, r], w2_b = p+pc [r, 9, in_n]
+ * Segment table of uwu_adapter_conv_merge: one row of 17 int64 per convolution -- the 13 fields of uwu_adapter_merge
+ * (rows = cout_store, cols = 9 cin_store), then cout, cin, cin_store, t_off (CONV_TUCKER: where T [r, 9, cin] of this
+ * segment lives in tws).  `table_host` is the same table in host memory: every row is checked before anything is launched.
+ * Two launches for all segments: T of every CONV_TUCKER segment into tws (nform workgroups; form_start [nseg + 1] = exclusive
+ * prefix sum of ceil(9 r cin / 256) for CONV_TUCKER rows, 0 for the others; nform = 0: no such launch), then W_eff = base +
+ * delta into eff / shadow as uwu_adapter_merge does (blk_start: ceil(rows * cols / 4096)).  eff may alias base. */
+#define UWU_ADAPTER_CONV_LORA 4
+#define UWU_ADAPTER_CONV_TUCKER 5
+#define UWU_ADAPTER_CONV_LOKR 6
+#define UWU_ADAPTER_CONV_LOKR_LOWRANK 7
+int uwu_adapter_conv_merge(const float* base, const float* p, const int64_t* table, const int64_t* table_host,
+                           const int64_t* blk_start, const int64_t* form_start, int nseg, int64_t nblocks, int64_t nform,
+                           float* tws, int64_t tws_elems, float* eff, void* shadow, void* stream);
+/* Adapter gradient of one adapted convolution from its fp32 weight gradient dw [cout_store, 9 cin_store], ACCUMULATED into
+ * g (offsets pa / pb / pc as in p).  dw is read once; partials go to ws and are added in a fixed order (no float atomics).
+ * CONV_TUCKER: T is formed in ws, d_up and dT come from the LoRA-shaped pass, one chain launch adds d_mid and d_dn.
+ * ws_elems, with K = 9 cin, W2 = 9 out_k in_n, out_l = cout / out_k, in_m = cin / in_n:
+ *   CONV_LORA:    ceil(K/256) cout r + ceil(cout/32) r K          CONV_TUCKER: that + 2 r K
+ *   CONV_LOKR*:   out_l ceil(W2 / 2048) in_m + out_l W2 + 2 W2 */
+int uwu_adapter_conv_grad(const float* dw, int64_t cout_store, int64_t cin_store, int64_t cout, int64_t cin, int kind,
+                          const float* p, float* g, int64_t pa, int64_t pb, int64_t pc, int r, int out_k, int in_n,
+                          float scale, float* ws, int64_t ws_elems, void* stream);
 
 /* ------------------------------------------------------------------ gradient exchange (section 8e)
  * One RCCL communicator per rank (librccl resolved at run time), created once; uwu_allreduce_flat sums a slice of the

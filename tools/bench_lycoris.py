@@ -2,7 +2,9 @@
 bf16, fused AdamW): ms/step and peak memory of each mode, and the two adapter kernels alone (merge of every adapted
 tensor, adapter gradient of every adapted Linear) with the bytes they move.  One JSON line.  DESIGN.md section 4.21.
 With a weight-decomposed config (--lycoris configs/lycoris/sdxl-diffusers-dora.toml, section 4.39) the merge figure covers
-its three launches and the summed time of uwu_adapter_dora_grad is reported on its own.
+its three launches and the summed time of uwu_adapter_dora_grad is reported on its own.  With a convolution preset
+(--lycoris configs/lycoris/sdxl-diffusers-conv.toml, section 4.41) the convolution merge (uwu_adapter_conv_merge alone) and the
+adapter gradients of the adapted convolutions (uwu_adapter_conv_grad from an fp32 dW of each stored shape) are reported too.
 
     python tools/bench_lycoris.py [--batch 12] [--steps 5] [--warmup 2] [--mode both|full|lycoris] [--lycoris PATH]
 
@@ -96,7 +98,7 @@ def run_mode(mode, B, steps, warmup, toml=TOML):
     n_dora = sum(int(torch.tensor(model.P.registry[n][1]).prod()) for n in ad.dora)
     merge_bytes += n_dora * 4  # the norm pass reads the decomposed base elements once more
     # adapter gradients of every adapted Linear from an fp32 dW of its shape (reads dW once + the factors + small partials)
-    grads_names = [n for n in ad.names if ad.seg[n][1] != 0]
+    grads_names = [n for n in ad.names if ad.seg[n][1] != 0 and n not in ad.convs]
     dws = {}
     for n in grads_names:
         shape = tuple(model.P.registry[n][1])
@@ -104,13 +106,15 @@ def run_mode(mode, B, steps, warmup, toml=TOML):
             dws[shape] = torch.randn(shape, device=dev)
     if net.flat.grad is None:
         net.flat.grad = torch.zeros_like(net.flat.data)
-    ad.grad_rows(model.P, grads_names[:1], dws[tuple(model.P.registry[grads_names[0]][1])])
-    ev[0].record()
-    for n in grads_names:
-        ad.grad_rows(model.P, [n], dws[tuple(model.P.registry[n][1])])
-    ev[1].record()
-    torch.cuda.synchronize()
-    t_grad = ev[0].elapsed_time(ev[1])
+    t_grad = 0.0
+    if grads_names:
+        ad.grad_rows(model.P, grads_names[:1], dws[tuple(model.P.registry[grads_names[0]][1])])
+        ev[0].record()
+        for n in grads_names:
+            ad.grad_rows(model.P, [n], dws[tuple(model.P.registry[n][1])])
+        ev[1].record()
+        torch.cuda.synchronize()
+        t_grad = ev[0].elapsed_time(ev[1])
     grad_bytes = sum(int(torch.tensor(model.P.registry[n][1]).prod()) * 4 for n in grads_names)
     if ad.dora:  # the stage in front of uwu_adapter_grad alone: G read twice, base read once, G written once
         ev[0].record()
@@ -121,10 +125,35 @@ def run_mode(mode, B, steps, warmup, toml=TOML):
         t_dora = ev[0].elapsed_time(ev[1])
         out.update({"decomposed_elements": n_dora, "dora_grad_ms_per_step": round(t_dora, 3),
                     "dora_grad_bytes": n_dora * 16, "dora_grad_GBps": round(n_dora * 16 / t_dora / 1e6, 1)})
+    if ad.convs:  # section 4.41: the convolution merge (T of the Tucker segments + merge) and the convolution adapter
+        # gradients alone, from an fp32 dW of each stored shape (read once)
+        n_conv = sum(int(torch.tensor(model.P.registry[n][1]).prod()) for n in ad.convs)
+        shadow = model.P.shadow
+        ad._launch_merge(model.P, None, None, ad.eff, shadow, ad.ctab)
+        ev[0].record()
+        for _ in range(reps):
+            ad._launch_merge(model.P, None, None, ad.eff, shadow, ad.ctab)
+        ev[1].record()
+        torch.cuda.synchronize()
+        t_cm = ev[0].elapsed_time(ev[1]) / reps
+        for n in ad.convs:
+            shape = tuple(model.P.registry[n][1])
+            if shape not in dws:
+                dws[shape] = torch.randn(shape, device=dev)
+        ad.conv_grad_rows(model.P, ad.convs[0], dws[tuple(model.P.registry[ad.convs[0]][1])])
+        ev[0].record()
+        for n in ad.convs:
+            ad.conv_grad_rows(model.P, n, dws[tuple(model.P.registry[n][1])])
+        ev[1].record()
+        torch.cuda.synchronize()
+        t_cg = ev[0].elapsed_time(ev[1])
+        out.update({"adapted_convs": len(ad.convs), "conv_elements": n_conv, "conv_merge_ms": round(t_cm, 3),
+                    "conv_merge_GBps": round(n_conv * 6 / t_cm / 1e6, 1), "conv_adapter_grad_ms_per_step": round(t_cg, 3),
+                    "conv_adapter_grad_dW_bytes": n_conv * 4, "conv_adapter_grad_GBps": round(n_conv * 4 / t_cg / 1e6, 1)})
     out.update({"adapted_elements": n_el, "merge_ms": round(t_merge, 3), "merge_bytes": merge_bytes,
                 "merge_GBps": round(merge_bytes / t_merge / 1e6, 1), "adapter_grad_ms_per_step": round(t_grad, 3),
                 "adapted_linears": len(grads_names), "adapter_grad_dW_bytes": grad_bytes,
-                "adapter_grad_GBps": round(grad_bytes / t_grad / 1e6, 1)})
+                "adapter_grad_GBps": round(grad_bytes / t_grad / 1e6, 1) if t_grad else None})
     return out
 
 

@@ -1,4 +1,4 @@
-"""LyCORIS adapters (LoRA, LoKr, norm) on the flat UNet: configuration, layer matching, one flat adapter parameter.
+"""LyCORIS adapters (LoRA, LoKr, norm; LoCon / Tucker / LoKr on the 3x3 convolutions) on the flat UNet: configuration, layer matching, one flat adapter parameter.
 
 The reference trainer wraps the UNet with the ``lycoris`` library (reference src/duwu/trainer/trainer.py:148-169): a
 ``config`` table (algo, dims, alpha, ...) and a ``preset`` table (which module classes / names are adapted).  The library
@@ -12,6 +12,14 @@ is not a dependency of this build; the subset below is this project's contract (
   * dora_wd (on LoRA / LoKr): W' = m (W + dW) / (||W + dW|| + eps), one magnitude m (``dora_scale``) and one norm per
            output row (wd_on_out) or per input column, eps = 2^-23 added to the norm; m starts at the base weight's norm
            
+
+  * 3x3 convolutions (``enable_conv``; ``conv_dim`` / ``conv_alpha``), W [Cout, Cin, 3, 3]:
+           LoRA    down [dim, Cin, 3, 3], up [Cout, dim, 1, 1]: dW = alpha / dim * up @ down.view(dim, -1)
+           Tucker  (``use_tucker``) down [dim, Cin, 1, 1], mid [dim, dim, 3, 3] kaiming-uniform, up [Cout, dim, 1, 1]:
+                   dW[p, c, kh, kw] = alpha / dim * sum_ij up[p, i] mid[i, j, kh, kw] down[j, c]
+           LoKr    w1 [out_l, in_m], w2 [out_k, in_n, 3, 3] (or w2_a [out_k, dim] @ w2_b [dim, in_n * 9]) on the
+                   factorizations of Cout and Cin: dW[a out_k + c, b in_n + d, kh, kw] = scale * w1[a, b] w2[c, d, kh, kw]
+           the buffer holds these tap-major (Spec.internal), the state dict in the shapes above
 
 so a freshly attached network leaves the model's output unchanged (with dora_wd: to rounding).  Every adapter tensor is a named view of ONE flat
 fp32 parameter (the fused AdamW and the gradient exchange work on it as on the UNet's flat buffer); the UNet merges them
@@ -34,6 +42,7 @@ BOOL_KEYS = ("dora_wd", "wd_on_out")
 PRESET_KEYS = ("target_module", "target_name", "enable_conv", "module_algo_map")
 ALGOS = ("lora", "lokr")
 KIND_NORM, KIND_LORA, KIND_LOKR, KIND_LOKR_LOWRANK = 0, 1, 2, 3  # UWU_ADAPTER_* of include/uwu_hip.h
+KIND_CONV_LORA, KIND_CONV_TUCKER, KIND_CONV_LOKR, KIND_CONV_LOKR_LOWRANK = 4, 5, 6, 7  # UWU_ADAPTER_CONV_*
 MAX_RANK = 128
 
 
@@ -150,15 +159,87 @@ def module_classes(unet):
 
 class Spec:
     """One adapted layer: ``name`` (module), ``algo`` ('lora' / 'lokr' / 'norm'), ``shape`` ([out, in] or [C]), the
-    adapter tensors [(tensor name, shape)], and the factors the kernels need."""
+    adapter tensors [(tensor name, shape)], and the factors the kernels need.
 
-    def __init__(self, name, algo, shape, dim=0, alpha=1.0, factor=-1, full_matrix=False, dora_wd=False, wd_on_out=True):
+    A 3x3 convolution (``conv``: its (cin, cout, stored cin, stored cout)) has ``shape`` = the true
+    (Cout, Cin); ``tensors`` holds the PUBLIC shapes (the state dict's), ``internal`` the tap-major shapes the flat buffer
+    and the kernels use ([A, B, 3, 3] is stored [A, 9, B], [A, B, 1, 1] as [A, B], lokr_w2_b [dim, in_n * 9] as
+    [dim, 9, in_n]); ``to_internal`` / ``to_public`` permute between the two."""
+
+    def __init__(self, name, algo, shape, dim=0, alpha=1.0, factor=-1, full_matrix=False, dora_wd=False, wd_on_out=True,
+                 conv=None, use_tucker=False):
         self.name, self.algo, self.shape = name, algo, tuple(shape)
         self.dim, self.alpha, self.r, self.out_k, self.in_n, self.lowrank = 0, None, 0, 0, 0, False
         self.dora, self.wd_on_out = bool(dora_wd) and algo != "norm", bool(wd_on_out)
+        self.conv, self.tucker, self.internal = conv, False, {}
+        if conv is not None:
+            self._conv_factors(dim, alpha, factor, full_matrix, use_tucker)
+            return
         self._factors(dim, alpha, factor, full_matrix)
         if self.dora:  # one magnitude per output row or per input column, always the last tensor
             self.tensors.append(("dora_scale", (self.shape[0], 1) if self.wd_on_out else (1, self.shape[1])))
+
+    def _conv_factors(self, dim, alpha, factor, full_matrix, use_tucker):
+        name, algo = self.name, self.algo
+        if self.dora:
+            raise NotImplementedError(f"{name}: dora_wd on a convolution adapter is not implemented")
+        out, inn = self.shape
+        dim = int(dim)
+        if dim < 1:
+            raise ValueError(f"{name}: conv_dim must be >= 1")
+        self.dim, self.alpha = dim, float(alpha)
+        too_wide = NotImplementedError(f"{name}: conv_dim {dim} > {MAX_RANK} is not implemented")
+        if algo == "lora":
+            if dim > MAX_RANK:
+                raise too_wide
+            self.r, self.scale, self.tucker = dim, self.alpha / dim, bool(use_tucker)
+            if self.tucker:
+                self.kind = KIND_CONV_TUCKER
+                self.tensors = [("lora_down.weight", (dim, inn, 1, 1)), ("lora_mid.weight", (dim, dim, 3, 3)),
+                                ("lora_up.weight", (out, dim, 1, 1))]
+            else:
+                self.kind = KIND_CONV_LORA
+                self.tensors = [("lora_down.weight", (dim, inn, 3, 3)), ("lora_up.weight", (out, dim, 1, 1))]
+        else:
+            out_l, out_k = factorization(out, factor)
+            in_m, in_n = factorization(inn, factor)
+            self.out_k, self.in_n = out_k, in_n
+            self.tensors = [("lokr_w1", (out_l, in_m))]
+            if not full_matrix and dim < max(out_k, in_n) / 2:
+                if use_tucker:
+                    raise NotImplementedError(f"{name}: low-rank LoKr with use_tucker (lokr_t2) is not implemented")
+                if dim > MAX_RANK:
+                    raise too_wide
+                self.kind, self.lowrank, self.r, self.scale = KIND_CONV_LOKR_LOWRANK, True, dim, self.alpha / dim
+                self.tensors += [("lokr_w2_a", (out_k, dim)), ("lokr_w2_b", (dim, in_n * 9))]
+            else:
+                self.kind, self.scale = KIND_CONV_LOKR, 1.0
+                self.tensors += [("lokr_w2", (out_k, in_n, 3, 3))]
+        for t, sh in self.tensors:
+            if len(sh) == 4:
+                self.internal[t] = (sh[0], 9, sh[1]) if sh[2] == 3 else (sh[0], sh[1])
+            elif t == "lokr_w2_b":
+                self.internal[t] = (sh[0], 9, sh[1] // 9)
+            else:
+                self.internal[t] = sh
+
+    def to_internal(self, t, v):
+        """a public tensor of this layer in the flat buffer's layout (a copy where the two differ)"""
+        sh = dict(self.tensors)[t]
+        if self.conv is None or self.internal[t] == sh:
+            return v
+        if len(sh) == 4:
+            return v.permute(0, 2, 3, 1).reshape(self.internal[t])
+        return v.reshape(sh[0], sh[1] // 9, 9).permute(0, 2, 1).contiguous()  # lokr_w2_b: columns (d, tap) -> (tap, d)
+
+    def to_public(self, t, v):
+        """the stored tensor `v` in the public shape: a view of `v`, except lokr_w2_b of a convolution (a copy)"""
+        sh = dict(self.tensors)[t]
+        if self.conv is None or self.internal[t] == sh:
+            return v
+        if len(sh) == 4:
+            return v.view(sh[0], sh[2], sh[3], sh[1]).permute(0, 3, 1, 2)
+        return v.permute(0, 2, 1).reshape(sh)
 
     def _factors(self, dim, alpha, factor, full_matrix):
         name, algo = self.name, self.algo
@@ -208,7 +289,8 @@ def match_layers(unet, lycoris_config):
     A Linear takes the algo (and settings) of its nearest ancestor listed in ``module_algo_map``; otherwise the
     ``config`` algo, if an ancestor's class is in ``target_module`` or its name matches ``target_name``.  With
     ``train_norm`` every LayerNorm / GroupNorm inside a target gets a norm adapter.  3x3 convolutions inside a target:
-    skipped, or NotImplementedError with ``enable_conv``."""
+    skipped, or with ``enable_conv`` adapted on ``conv_dim`` / ``conv_alpha`` (``use_tucker``: the Tucker form of LoRA);
+    1x1 convolutions are Linears here."""
     config, preset = lycoris_config if isinstance(lycoris_config, tuple) else load_config(lycoris_config)
     classes = module_classes(unet)
     tmod, tname, amap = set(preset["target_module"]), list(preset["target_name"]), preset["module_algo_map"]
@@ -234,10 +316,18 @@ def match_layers(unet, lycoris_config):
         elif kind in ("LayerNorm", "GroupNorm"):
             if cfg["train_norm"]:
                 specs.append(Spec(leaf, "norm", registry[leaf + ".weight"][1]))
-        elif kind == "Conv2d":
-            if preset["enable_conv"]:
-                raise NotImplementedError(f"lycoris_config: enable_conv reaches the 3x3 convolution {leaf!r}; "
-                                          "convolution adapters are not implemented")
+        elif kind == "Conv2d" and preset["enable_conv"]:
+            if cfg["conv_dim"] is None:
+                raise NotImplementedError(f"lycoris_config: enable_conv reaches the 3x3 convolution {leaf!r} and conv_dim "
+                                          "is not set; the fallback of conv_dim to linear_dim is not implemented")
+            if cfg["dora_wd"]:
+                raise NotImplementedError(f"lycoris_config: dora_wd reaches the 3x3 convolution {leaf!r}; weight "
+                                          "decomposition of convolution adapters is not implemented")
+            meta = unet._conv_meta[leaf]  # (cin, cout, stored cin, stored cout)
+            specs.append(Spec(leaf, cfg["algo"], (meta[1], meta[0]), dim=cfg["conv_dim"],
+                              alpha=cfg["linear_alpha"] if cfg["conv_alpha"] is None else cfg["conv_alpha"],
+                              factor=cfg["factor"], full_matrix=cfg["full_matrix"], conv=meta,
+                              use_tucker=cfg["use_tucker"]))
     if not specs:
         raise ValueError("lycoris_config matches no layer of the UNet")
     order = {n: i for i, n in enumerate(registry)}
@@ -250,6 +340,16 @@ def grad_ws_elems(spec, N, K):
     if spec.algo == "lora":
         return -(-K // 256) * N * spec.r + -(-N // 32) * spec.r * K
     out_l, in_m, W2 = N // spec.out_k, K // spec.in_n, spec.out_k * spec.in_n
+    return out_l * -(-W2 // 2048) * in_m + out_l * W2 + 2 * W2
+
+
+def conv_grad_ws_elems(spec):
+    """floats of uwu_adapter_conv_grad's workspace (include/uwu_hip.h)"""
+    cout, cin = spec.shape
+    K = 9 * cin
+    if spec.algo == "lora":
+        return -(-K // 256) * cout * spec.r + -(-cout // 32) * spec.r * K + (2 * spec.r * K if spec.tucker else 0)
+    out_l, in_m, W2 = cout // spec.out_k, cin // spec.in_n, 9 * spec.out_k * spec.in_n
     return out_l * -(-W2 // 2048) * in_m + out_l * W2 + 2 * W2
 
 
@@ -267,6 +367,7 @@ class LycorisNetwork(nn.Module):
     def __init__(self, unet, lycoris_config, device=None):
         super().__init__()
         self.specs = match_layers(unet, lycoris_config)
+        self._by_name = {s.name: s for s in self.specs}
         self.offsets = {}  # (spec name, tensor name) -> (offset, shape)
         n = 0
         for s in self.specs:
@@ -283,22 +384,54 @@ class LycorisNetwork(nn.Module):
         self.reset_parameters(unet)
 
     # ------------------------------------------------------------------ views / init
-    def view(self, spec_name, tensor, buf=None):
+    def stored(self, spec_name, tensor, buf=None):
+        """the tensor as the flat buffer holds it (a convolution adapter: tap-major, Spec.internal), always a view"""
         off, shape = self.offsets[(spec_name, tensor)]
+        shape = self._by_name[spec_name].internal.get(tensor, shape)
         return (self.flat.data if buf is None else buf)[off:off + math.prod(shape)].view(shape)
+
+    def view(self, spec_name, tensor, buf=None):
+        """the tensor in its public shape: a view of the buffer, except lokr_w2_b of a convolution (a copy: ``write`` is
+        the way in)"""
+        return self._by_name[spec_name].to_public(tensor, self.stored(spec_name, tensor, buf))
+
+    @torch.no_grad()
+    def write(self, spec_name, tensor, value, buf=None):
+        """`value` (public shape) into the buffer"""
+        self.stored(spec_name, tensor, buf).copy_(self._by_name[spec_name].to_internal(tensor, value))
+
+    @torch.no_grad()
+    def conv_delta(self, spec_name, dtype=torch.float64):
+        """dW of one adapted convolution in the STORED layout [Cout_store, 9, Cin_store] (zeros in the padding), computed
+        by torch from the buffer: what uwu_adapter_conv_merge adds to the base weight (the host-side statement of it)"""
+        s = self._by_name[spec_name]
+        cin, cout, ci, co = s.conv
+        T = lambda t: self.stored(spec_name, t).to(dtype)
+        if s.algo == "lora":
+            down = T("lora_down.weight")  # [dim, 9, Cin]; Tucker: [dim, Cin], taken through mid [dim, 9, dim] first
+            if s.tucker:
+                down = torch.einsum("itj,jc->itc", T("lora_mid.weight"), down)
+            d = torch.einsum("oi,itc->otc", T("lora_up.weight"), down)
+        else:
+            w2 = torch.einsum("kr,rtl->ktl", T("lokr_w2_a"), T("lokr_w2_b")) if s.lowrank else T("lokr_w2")
+            d = torch.einsum("ab,ktl->aktbl", T("lokr_w1"), w2).reshape(cout, 9, cin)
+        out = torch.zeros(co, 9, ci, dtype=dtype, device=d.device)
+        out[:cout, :, :cin] = d * s.scale
+        return out
 
     @torch.no_grad()
     def reset_parameters(self, unet=None):
-        """kaiming_uniform(a=sqrt 5) on lora_down / lokr_w1 / lokr_w2_a (torch's default generator), zeros elsewhere:
+        """kaiming_uniform(a=sqrt 5) on lora_down / lora_mid / lokr_w1 / lokr_w2_a (torch's default generator, drawn in
+        the public shape: a convolution's fan-in counts its taps), zeros elsewhere:
         dW = 0 and the adapted model computes what the bare one does.  dora_scale: the norms of the base weights of
         ``unet`` (default: the UNet the network is attached to)."""
         self.flat.data.zero_()
         for s in self.specs:
             for t, shape in s.tensors:
-                if t in ("lora_down.weight", "lokr_w1", "lokr_w2_a"):
+                if t in ("lora_down.weight", "lora_mid.weight", "lokr_w1", "lokr_w2_a"):
                     w = torch.empty(shape, dtype=torch.float32)
                     nn.init.kaiming_uniform_(w, a=math.sqrt(5))
-                    self.view(s.name, t).copy_(w)
+                    self.write(s.name, t, w)
         self._init_dora(unet if unet is not None else self.__dict__.get("_unet"))
         self.mark_dirty()
 
@@ -327,7 +460,7 @@ class LycorisNetwork(nn.Module):
         sd = destination if destination is not None else {}
         for s in self.specs:
             for t, _ in s.tensors:
-                sd[f"{prefix}{s.key}.{t}"] = self.view(s.name, t).detach().clone()
+                sd[f"{prefix}{s.key}.{t}"] = self.view(s.name, t).detach().clone(memory_format=torch.contiguous_format)
             if s.alpha is not None:
                 sd[f"{prefix}{s.key}.alpha"] = torch.tensor(s.alpha)
         return sd
@@ -349,7 +482,7 @@ class LycorisNetwork(nn.Module):
                         error_msgs.append(f"size mismatch for {k}: checkpoint {tuple(v.shape)}, adapter {tuple(shape)}")
                         dora_loaded &= t != "dora_scale"
                         continue
-                    self.view(s.name, t).copy_(v.float())
+                    self.write(s.name, t, v.float())
                 if s.alpha is not None:
                     k = f"{prefix}{s.key}.alpha"
                     mine.add(k)

@@ -101,7 +101,7 @@ class FlatAverage:
         sd = {}
         for s in o.specs:  # (the order and the alpha entries of LycorisNetwork.state_dict)
             for t, _ in s.tensors:
-                sd[f"{s.key}.{t}"] = o.view(s.name, t, buf=self.avg).detach().clone()
+                sd[f"{s.key}.{t}"] = o.view(s.name, t, buf=self.avg).detach().clone(memory_format=torch.contiguous_format)
             if s.alpha is not None:
                 sd[f"{s.key}.alpha"] = torch.tensor(s.alpha)
         return sd
@@ -122,8 +122,13 @@ class FlatAverage:
         if missing or unexpected or wrong:
             raise RuntimeError(f"averaged weights do not fit {type(o).__name__}: missing {missing[:5]}, unexpected {unexpected[:5]}, "
                                f"size mismatch {wrong[:5]}")
-        for k, v in views.items():
-            v.copy_(sd[k])
+        if isinstance(o, FlatModule):
+            for k, v in views.items():
+                v.copy_(sd[k])
+        else:  # (a convolution adapter's public shape is not always a view of the buffer: LycorisNetwork.write permutes)
+            for s in o.specs:
+                for t, _ in s.tensors:
+                    o.write(s.name, t, sd[f"{s.key}.{t}"].to(self.avg.device), buf=self.avg)
 
 
 class WeightAveraging:

@@ -10,6 +10,9 @@
 //   dora:  weight decomposition on top of LoRA / LoKr (section 4.39): W' = m (W + dW) / (||W + dW|| + eps) per row or column --
 //          the norms of every decomposed tensor (one launch), the merge with the factor m / n (one launch), and per layer the
 //          stage in front of `grad` that turns dL/dW' into dL/d(W + dW) in place and adds dL/dm.  Fixed-order fp64 sums.
+//   conv:  the same on a 3x3 convolution weight stored [Cout_store, 9, Cin_store] (section 4.41): LoCon, its Tucker form and LoKr
+//          with the adapter tensors tap-major -- T = mid . down of every Tucker segment (one launch) and the merge of every
+//          convolution (one launch); per layer the LoRA / LoKr gradient kernels above through a column map, plus the Tucker chain.
 #include "common.h"
 
 namespace {
@@ -87,16 +90,26 @@ __global__ void __launch_bounds__(256) adapter_merge_kernel(const float* __restr
 constexpr int LR_RT = 32, LR_CT = 256;  // dW tile of one workgroup: 32 rows x 256 columns, staged in LDS
 
 // partials: du_part[ct][n][r] = sum_{c in tile ct} dW[n,c] down[t,c];  dd_part[rt][t][k] = sum_{i in tile rt} up[i,t] dW[i,k]
+// CONV (section 4.41): dw is a stored convolution gradient [>= N rows, 9 cin_store]; column j = t cin + c of the [N, K = 9 cin]
+// problem is read from column t cin_store + c (row stride ld), so padded rows and channels are never touched.
+template <bool CONV>
 __global__ void __launch_bounds__(256) lora_grad_partial_kernel(const float* __restrict__ dw, int N, int K,
                                                                 const float* __restrict__ up,
                                                                 const float* __restrict__ down, int r,
                                                                 float* __restrict__ du_part,
-                                                                float* __restrict__ dd_part) {
+                                                                float* __restrict__ dd_part, int ld, int cin,
+                                                                int cin_store) {
   __shared__ float tile[LR_RT][LR_CT + 1];
   const int ct = blockIdx.x, rt = blockIdx.y, tid = threadIdx.x;
   const int i0 = rt * LR_RT, j0 = ct * LR_CT;
   const int nr = min(LR_RT, N - i0), nc = min(LR_CT, K - j0);
-  for (int i = 0; i < LR_RT; ++i) tile[i][tid] = (i < nr && tid < nc) ? dw[(int64_t)(i0 + i) * K + j0 + tid] : 0.f;
+  if constexpr (CONV) {
+    const int t = (j0 + tid) / cin;
+    const int src = t * cin_store + (j0 + tid - t * cin);
+    for (int i = 0; i < LR_RT; ++i) tile[i][tid] = (i < nr && tid < nc) ? dw[(int64_t)(i0 + i) * ld + src] : 0.f;
+  } else {
+    for (int i = 0; i < LR_RT; ++i) tile[i][tid] = (i < nr && tid < nc) ? dw[(int64_t)(i0 + i) * K + j0 + tid] : 0.f;
+  }
   __syncthreads();
   if (tid < nc) {
     for (int t = 0; t < r; ++t) {
@@ -117,7 +130,7 @@ __global__ void __launch_bounds__(256) lora_grad_partial_kernel(const float* __r
 __global__ void __launch_bounds__(256) lora_grad_reduce_kernel(const float* __restrict__ du_part,
                                                                const float* __restrict__ dd_part, int N, int K, int r,
                                                                int nct, int nrt, float scale, float* __restrict__ gu,
-                                                               float* __restrict__ gd) {
+                                                               float* __restrict__ gd, int gd_accumulate) {
   const int64_t o = (int64_t)blockIdx.x * 256 + threadIdx.x;
   const int64_t nu = (int64_t)N * r, nd = (int64_t)r * K;
   if (o < nu) {
@@ -128,7 +141,8 @@ __global__ void __launch_bounds__(256) lora_grad_reduce_kernel(const float* __re
     const int64_t q = o - nu;
     float acc = 0.f;
     for (int c = 0; c < nrt; ++c) acc += dd_part[(int64_t)c * nd + q];
-    gd[q] += scale * acc;
+    if (gd_accumulate) gd[q] += scale * acc;
+    else gd[q] = scale * acc;  // (Tucker: dT, a workspace)
   }
 }
 
@@ -149,13 +163,16 @@ __global__ void __launch_bounds__(256) lokr_form_w2_kernel(const float* __restri
 // workgroup (g, i): the w2 elements [g*2048, (g+1)*2048) of every Kronecker block (i, j), j = 0..in_m-1.
 //   p1[(i*G + g)*in_m + j] = sum_{e in group} dW[i,k,j,l] w2[e]      (partial of dw1[i,j])
 //   p2[i*W2 + e]           = sum_j w1[i,j] dW[i,k,j,l]                (partial of dw2[e])
+// CONV (section 4.41): w2 is [out_k, 9, in_n]; its element (k, t, l) of block (i, j) is dW[i out_k + k][t cin_store + j in_n + l]
+// of the stored convolution gradient (K: its row stride 9 cin_store).
+template <bool CONV>
 __global__ void __launch_bounds__(256) lokr_grad_partial_kernel(const float* __restrict__ dw, int K, int out_k,
                                                                 int in_n, int in_m, const float* __restrict__ w1,
                                                                 const float* __restrict__ w2, float* __restrict__ p1,
-                                                                float* __restrict__ p2) {
+                                                                float* __restrict__ p2, int cin_store) {
   __shared__ float red[4];
   const int g = blockIdx.x, i = blockIdx.y, G = gridDim.x, tid = threadIdx.x;
-  const int W2 = out_k * in_n;
+  const int W2 = CONV ? 9 * out_k * in_n : out_k * in_n;
   float acc[8], w2v[8];
   int64_t roff[8];
 #pragma unroll
@@ -165,8 +182,13 @@ __global__ void __launch_bounds__(256) lokr_grad_partial_kernel(const float* __r
     w2v[q] = 0.f;
     roff[q] = -1;
     if (e < W2) {
-      const int k = e / in_n, l = e - k * in_n;
-      roff[q] = (int64_t)(i * out_k + k) * K + l;
+      if constexpr (CONV) {
+        const int k = e / (9 * in_n), tl = e - k * 9 * in_n, t = tl / in_n;
+        roff[q] = (int64_t)(i * out_k + k) * K + t * cin_store + (tl - t * in_n);
+      } else {
+        const int k = e / in_n, l = e - k * in_n;
+        roff[q] = (int64_t)(i * out_k + k) * K + l;
+      }
       w2v[q] = w2[e];
     }
   }
@@ -517,7 +539,224 @@ const char* ad_dora_check_rows(const int64_t* t, int nseg) {
   return nullptr;
 }
 
+// ---------------------------------------------------------------------------------------------------------------- conv
+// Convolution adapters.  The stored weight is [cout_store, 9, cin_store]; the adapter tensors are
+// tap-major in the true sizes, so plain LoRA is the 2-D problem [cout, 9 cin] read through a column map, Tucker is LoRA
+// with down := T = mid . dn (formed first), and LoKr's w2 carries the taps between its two axes.  A segment row has 17
+// fields: the 13 of the merge, then cout, cin, cin_store, t_off (T in the workspace).
+constexpr int AD_CNF = 17;
+
+__device__ __forceinline__ float ad_conv_delta(const int64_t* __restrict__ row, const float* __restrict__ p,
+                                               const float* __restrict__ tws, int e) {
+  const int kind = (int)row[0];
+  const int cols = (int)row[2];
+  const int cout = (int)row[13], cin = (int)row[14], cs = (int)row[15];
+  const int o = e / cols, j = e - o * cols;
+  const int t = j / cs, c = j - t * cs;
+  if (o >= cout || c >= cin) return 0.f;  // padding: base + 0 stays the zero it holds
+  const float scale = __int_as_float((int)row[12]);
+  const int r = (int)row[9];
+  if (kind == UWU_ADAPTER_CONV_LORA || kind == UWU_ADAPTER_CONV_TUCKER) {
+    const float* up = p + row[6] + (int64_t)o * r;
+    const float* down = (kind == UWU_ADAPTER_CONV_TUCKER ? tws + row[16] : p + row[7]) + t * cin + c;
+    const int64_t ld = 9 * (int64_t)cin;
+    float acc = 0.f;
+    for (int i = 0; i < r; ++i) acc += up[i] * down[i * ld];
+    return acc * scale;
+  }
+  const int out_k = (int)row[10], in_n = (int)row[11], in_m = cin / in_n;
+  const int a = o / out_k, k = o - a * out_k, b = c / in_n, l = c - b * in_n;
+  const float w1 = p[row[6] + (int64_t)a * in_m + b];
+  float w2;
+  if (kind == UWU_ADAPTER_CONV_LOKR) {
+    w2 = p[row[7] + ((int64_t)k * 9 + t) * in_n + l];
+  } else {  // w2 = w2_a [out_k, r] . w2_b [r, 9, in_n]
+    const float* wa = p + row[7] + (int64_t)k * r;
+    const float* wb = p + row[8] + t * in_n + l;
+    w2 = 0.f;
+    for (int i = 0; i < r; ++i) w2 += wa[i] * wb[(int64_t)i * 9 * in_n];
+  }
+  return (w1 * w2) * scale;
+}
+
+// T[(i, t), c] = sum_j mid[(i, t), j] dn[j, c] of every Tucker segment: one thread per element of T
+__global__ void __launch_bounds__(256) adapter_conv_form_kernel(const float* __restrict__ p, const int64_t* __restrict__ table,
+                                                                const int64_t* __restrict__ form_start, int nseg,
+                                                                float* __restrict__ tws) {
+  const int64_t bid = blockIdx.x;
+  const int lo = ad_find_segment(form_start, nseg, bid);
+  const int64_t* row = table + (int64_t)lo * AD_CNF;
+  const int r = (int)row[9], cin = (int)row[14];
+  const int e = (int)(bid - form_start[lo]) * 256 + threadIdx.x;
+  if (row[0] != UWU_ADAPTER_CONV_TUCKER || e >= 9 * r * cin) return;
+  const int it = e / cin, c = e - it * cin;
+  const float* mid = p + row[8] + (int64_t)it * r;
+  const float* dn = p + row[7] + c;
+  float acc = 0.f;
+  for (int j = 0; j < r; ++j) acc += mid[j] * dn[(int64_t)j * cin];
+  tws[row[16] + e] = acc;
+}
+
+__global__ void __launch_bounds__(256) adapter_conv_merge_kernel(const float* __restrict__ base, const float* __restrict__ p,
+                                                                 const int64_t* __restrict__ table,
+                                                                 const int64_t* __restrict__ blk_start, int nseg,
+                                                                 const float* __restrict__ tws, float* __restrict__ eff,
+                                                                 bf16_t* __restrict__ shadow) {
+  const int64_t bid = blockIdx.x;
+  const int lo = ad_find_segment(blk_start, nseg, bid);
+  const int64_t* row = table + (int64_t)lo * AD_CNF;
+  const int n = (int)(row[1] * row[2]);
+  const int64_t boff = row[3], eoff = row[4], soff = row[5];
+  const int e0 = (int)(bid - blk_start[lo]) * AD_MERGE_ELEMS;
+#pragma unroll
+  for (int it = 0; it < AD_MERGE_ELEMS / 1024; ++it) {
+    const int e = e0 + it * 1024 + 4 * threadIdx.x;
+    if (e >= n) break;
+    if (e + 4 <= n) {
+      f32x4 v = load4(base + boff + e);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) v[q] += ad_conv_delta(row, p, tws, e + q);
+      if (eoff >= 0) store4(eff + eoff + e, v);
+      if (shadow && soff >= 0) store4(shadow + soff + e, v);
+    } else {
+      for (int q = e; q < n; ++q) {
+        const float v = base[boff + q] + ad_conv_delta(row, p, tws, q);
+        if (eoff >= 0) eff[eoff + q] = v;
+        if (shadow && soff >= 0) shadow[soff + q] = (bf16_t)v;
+      }
+    }
+  }
+}
+
+bool ad_is_conv_kind(int64_t k) { return k >= UWU_ADAPTER_CONV_LORA && k <= UWU_ADAPTER_CONV_LOKR_LOWRANK; }
+bool ad_conv_is_lokr(int64_t k) { return k == UWU_ADAPTER_CONV_LOKR || k == UWU_ADAPTER_CONV_LOKR_LOWRANK; }
+
+// the host copy of a convolution segment table: every row is checked before anything is launched
+const char* ad_conv_check_rows(const int64_t* t, int nseg, int64_t tws_elems) {
+  for (int s = 0; s < nseg; ++s) {
+    const int64_t* r = t + (int64_t)s * AD_CNF;
+    if (!ad_is_conv_kind(r[0])) return "kind";
+    if (r[1] < 1 || r[2] < 1 || r[1] * r[2] >= (1ll << 31)) return "shape";
+    if (r[15] < 1 || r[2] != 9 * r[15] || r[13] < 1 || r[13] > r[1] || r[14] < 1 || r[14] > r[15]) return "channels";
+    if (r[0] != UWU_ADAPTER_CONV_LOKR && (r[9] < 1 || r[9] > AD_MAX_RANK)) return "rank outside [1, 128]";
+    if (ad_conv_is_lokr(r[0]) && (r[10] < 1 || r[11] < 1 || r[13] % r[10] || r[14] % r[11])) return "LoKr factors";
+    if (r[3] < 0 || r[3] % 64 || (r[4] >= 0 && r[4] % 64) || (r[5] >= 0 && r[5] % 64)) return "misaligned base / eff / shadow offset";
+    if (r[6] < 0 || r[7] < 0 || r[8] < 0) return "negative offset";
+    if (r[0] == UWU_ADAPTER_CONV_TUCKER && (r[16] < 0 || r[16] + 9 * r[9] * r[14] > tws_elems)) return "T outside the workspace";
+  }
+  return nullptr;
+}
+
+// workspace of uwu_adapter_conv_grad in floats (mirrored by uwudiff_amd/adapters.py: conv_grad_ws_elems)
+int64_t ad_conv_grad_ws_elems(int kind, int64_t cout, int64_t cin, int r, int out_k, int in_n) {
+  const int64_t K = 9 * cin;
+  if (!ad_conv_is_lokr(kind)) {
+    const int64_t nct = (K + LR_CT - 1) / LR_CT, nrt = (cout + LR_RT - 1) / LR_RT;
+    return nct * cout * r + nrt * r * K + (kind == UWU_ADAPTER_CONV_TUCKER ? 2 * r * K : 0);
+  }
+  const int64_t out_l = cout / out_k, in_m = cin / in_n, W2 = 9 * (int64_t)out_k * in_n;
+  const int64_t G = (W2 + LK_GROUP - 1) / LK_GROUP;
+  return out_l * G * in_m + out_l * W2 + 2 * W2;
+}
+
 }  // namespace
+
+extern "C" int uwu_adapter_conv_merge(const float* base, const float* p, const int64_t* table, const int64_t* table_host,
+                                      const int64_t* blk_start, const int64_t* form_start, int nseg, int64_t nblocks,
+                                      int64_t nform, float* tws, int64_t tws_elems, float* eff, void* shadow, void* stream) {
+  UWU_CHECK_ARG(base && p && table && table_host && blk_start && nseg > 0 && nblocks > 0 && nblocks < (1ll << 31) &&
+                    nform >= 0 && nform < (1ll << 31) && tws_elems >= 0,
+                "adapter_conv_merge: bad args (nseg=%d nblocks=%lld nform=%lld)", nseg, (long long)nblocks, (long long)nform);
+  UWU_CHECK_ARG(eff || shadow, "adapter_conv_merge: no output");
+  const char* why = ad_conv_check_rows(table_host, nseg, tws ? tws_elems : 0);
+  UWU_CHECK_ARG(!why, "adapter_conv_merge: bad segment table: %s", why);
+  int64_t want = 0, wantf = 0;
+  for (int s = 0; s < nseg; ++s) {
+    const int64_t* r = table_host + (int64_t)s * AD_CNF;
+    want += (r[1] * r[2] + AD_MERGE_ELEMS - 1) / AD_MERGE_ELEMS;
+    if (r[0] == UWU_ADAPTER_CONV_TUCKER) wantf += (9 * r[9] * r[14] + 255) / 256;
+  }
+  UWU_CHECK_ARG(want == nblocks && wantf == nform && (nform == 0 || form_start),
+                "adapter_conv_merge: nblocks %lld / nform %lld, the table needs %lld / %lld", (long long)nblocks,
+                (long long)nform, (long long)want, (long long)wantf);
+  hipStream_t st = (hipStream_t)stream;
+  if (nform > 0)
+    hipLaunchKernelGGL(adapter_conv_form_kernel, dim3((unsigned)nform), dim3(256), 0, st, p, table, form_start, nseg, tws);
+  hipLaunchKernelGGL(adapter_conv_merge_kernel, dim3((unsigned)nblocks), dim3(256), 0, st, base, p, table, blk_start, nseg,
+                     tws, eff, (bf16_t*)shadow);
+  UWU_LAUNCH_CHECK("adapter_conv_merge");
+  return UWU_OK;
+}
+
+extern "C" int uwu_adapter_conv_grad(const float* dw, int64_t cout_store, int64_t cin_store, int64_t cout, int64_t cin,
+                                     int kind, const float* p, float* g, int64_t pa, int64_t pb, int64_t pc, int r, int out_k,
+                                     int in_n, float scale, float* ws, int64_t ws_elems, void* stream) {
+  UWU_CHECK_ARG(dw && p && g && ws && cout >= 1 && cout <= cout_store && cin >= 1 && cin <= cin_store &&
+                    cout_store < (1 << 24) && cin_store < (1 << 24) && cout_store * 9 * cin_store < (1ll << 31),
+                "adapter_conv_grad: bad args");
+  UWU_CHECK_ARG(ad_is_conv_kind(kind), "adapter_conv_grad: bad kind %d", kind);
+  UWU_CHECK_ARG(pa >= 0 && pb >= 0 && pc >= 0, "adapter_conv_grad: negative offset");
+  const bool lokr = ad_conv_is_lokr(kind);
+  UWU_CHECK_ARG(kind == UWU_ADAPTER_CONV_LOKR || (r >= 1 && r <= AD_MAX_RANK), "adapter_conv_grad: rank %d outside [1, %d]", r,
+                AD_MAX_RANK);
+  UWU_CHECK_ARG(!lokr || (out_k >= 1 && in_n >= 1 && cout % out_k == 0 && cin % in_n == 0),
+                "adapter_conv_grad: LoKr shape %lldx%lld / (%d, %d)", (long long)cout, (long long)cin, out_k, in_n);
+  const int64_t need = ad_conv_grad_ws_elems(kind, cout, cin, r, out_k, in_n);
+  UWU_CHECK_ARG(ws_elems >= need, "adapter_conv_grad: workspace %lld < %lld floats", (long long)ws_elems, (long long)need);
+  hipStream_t st = (hipStream_t)stream;
+  const int N = (int)cout, K = (int)(9 * cin), ld = (int)(9 * cin_store);
+  if (!lokr) {
+    const bool tucker = kind == UWU_ADAPTER_CONV_TUCKER;
+    const int nct = (K + LR_CT - 1) / LR_CT, nrt = (N + LR_RT - 1) / LR_RT;
+    float* du = ws;
+    float* dd = du + (int64_t)nct * N * r;
+    float* T = dd + (int64_t)nrt * r * K;  // Tucker: T [r, 9, cin], then dT
+    float* dT = T + (int64_t)r * K;
+    const float* down = p + pb;
+    if (tucker) {  // T [(i, t), c] = mid [(i, t), j] . dn [j, c]: the low-rank product of LoKr with out_k = 9 r, in_n = cin
+      hipLaunchKernelGGL(lokr_form_w2_kernel, dim3((unsigned)(((int64_t)r * K + 255) / 256)), dim3(256), 0, st, p + pc, p + pb,
+                         9 * r, (int)cin, r, T);
+      down = T;
+    }
+    hipLaunchKernelGGL(lora_grad_partial_kernel<true>, dim3(nct, nrt), dim3(256), 0, st, dw, N, K, p + pa, down, r, du, dd, ld,
+                       (int)cin, (int)cin_store);
+    const int64_t nout = (int64_t)N * r + (int64_t)r * K;
+    hipLaunchKernelGGL(lora_grad_reduce_kernel, dim3((unsigned)((nout + 255) / 256)), dim3(256), 0, st, du, dd, N, K, r, nct,
+                       nrt, scale, g + pa, tucker ? dT : g + pb, tucker ? 0 : 1);
+    if (tucker) {  // d_mid[(i, t), j] += sum_c dT[(i, t), c] dn[j, c];  d_dn[j, c] += sum_(i, t) mid[(i, t), j] dT[(i, t), c]
+      const int64_t n2 = (int64_t)9 * r * r + (int64_t)r * cin;
+      hipLaunchKernelGGL(lokr_grad_lowrank_kernel, dim3((unsigned)((n2 + 255) / 256)), dim3(256), 0, st, dT, p + pc, p + pb,
+                         9 * r, (int)cin, r, g + pc, g + pb);
+    }
+    UWU_LAUNCH_CHECK("adapter_conv_grad");
+    return UWU_OK;
+  }
+  const bool low = kind == UWU_ADAPTER_CONV_LOKR_LOWRANK;
+  const int out_l = (int)(cout / out_k), in_m = (int)(cin / in_n);
+  const int W2 = 9 * out_k * in_n;
+  const int G = (W2 + LK_GROUP - 1) / LK_GROUP;
+  float* p1 = ws;
+  float* p2 = p1 + (int64_t)out_l * G * in_m;
+  float* w2f = p2 + (int64_t)out_l * W2;  // low-rank: the formed w2, then dw2
+  float* dw2 = w2f + W2;
+  const float* w2 = p + pb;
+  if (low) {
+    hipLaunchKernelGGL(lokr_form_w2_kernel, dim3((W2 + 255) / 256), dim3(256), 0, st, p + pb, p + pc, out_k, 9 * in_n, r, w2f);
+    w2 = w2f;
+  }
+  hipLaunchKernelGGL(lokr_grad_partial_kernel<true>, dim3(G, out_l), dim3(256), 0, st, dw, ld, out_k, in_n, in_m, p + pa, w2,
+                     p1, p2, (int)cin_store);
+  const int64_t nout = (int64_t)out_l * in_m + W2;
+  hipLaunchKernelGGL(lokr_grad_reduce_kernel, dim3((unsigned)((nout + 255) / 256)), dim3(256), 0, st, p1, p2, out_l, in_m, W2,
+                     G, scale, g + pa, low ? dw2 : g + pb, low ? 0 : 1);
+  if (low) {
+    const int64_t n2 = (int64_t)out_k * r + (int64_t)r * 9 * in_n;
+    hipLaunchKernelGGL(lokr_grad_lowrank_kernel, dim3((unsigned)((n2 + 255) / 256)), dim3(256), 0, st, dw2, p + pb, p + pc,
+                       out_k, 9 * in_n, r, g + pb, g + pc);
+  }
+  UWU_LAUNCH_CHECK("adapter_conv_grad");
+  return UWU_OK;
+}
 
 extern "C" int uwu_adapter_merge(const float* base, const float* p, const int64_t* table, const int64_t* blk_start,
                                  int nseg, int64_t nblocks, float* eff, void* shadow, void* stream) {
@@ -543,11 +782,11 @@ extern "C" int uwu_adapter_grad(const float* dw, int64_t N, int64_t K, int kind,
     UWU_CHECK_ARG(ws_elems >= need, "adapter_grad: workspace %lld < %lld floats", (long long)ws_elems, (long long)need);
     float* du = ws;
     float* dd = ws + (int64_t)nct * N * r;
-    hipLaunchKernelGGL(lora_grad_partial_kernel, dim3(nct, nrt), dim3(256), 0, st, dw, (int)N, (int)K, p + pa, p + pb, r,
-                       du, dd);
+    hipLaunchKernelGGL(lora_grad_partial_kernel<false>, dim3(nct, nrt), dim3(256), 0, st, dw, (int)N, (int)K, p + pa, p + pb,
+                       r, du, dd, 0, 0, 0);
     const int64_t nout = N * r + (int64_t)r * K;
     hipLaunchKernelGGL(lora_grad_reduce_kernel, dim3((unsigned)((nout + 255) / 256)), dim3(256), 0, st, du, dd, (int)N,
-                       (int)K, r, nct, nrt, scale, g + pa, g + pb);
+                       (int)K, r, nct, nrt, scale, g + pa, g + pb, 1);
     UWU_LAUNCH_CHECK("adapter_grad");
     return UWU_OK;
   }
@@ -570,8 +809,8 @@ extern "C" int uwu_adapter_grad(const float* dw, int64_t N, int64_t K, int kind,
     hipLaunchKernelGGL(lokr_form_w2_kernel, dim3((W2 + 255) / 256), dim3(256), 0, st, p + pb, p + pc, out_k, in_n, r, w2f);
     w2 = w2f;
   }
-  hipLaunchKernelGGL(lokr_grad_partial_kernel, dim3(G, out_l), dim3(256), 0, st, dw, (int)K, out_k, in_n, in_m, p + pa, w2,
-                     p1, p2);
+  hipLaunchKernelGGL(lokr_grad_partial_kernel<false>, dim3(G, out_l), dim3(256), 0, st, dw, (int)K, out_k, in_n, in_m, p + pa,
+                     w2, p1, p2, 0);
   const int64_t nout = (int64_t)out_l * in_m + W2;
   hipLaunchKernelGGL(lokr_grad_reduce_kernel, dim3((unsigned)((nout + 255) / 256)), dim3(256), 0, st, p1, p2, out_l, in_m,
                      W2, G, scale, g + pa, low ? dw2 : g + pb, low ? 0 : 1);

@@ -102,6 +102,9 @@ _SIGS = {
     "uwu_adapter_dora_merge": (c_int, [P, P, P, P, P, c_int, c_int64, P, P, P, P]),
     "uwu_adapter_dora_grad": (c_int, [P, P, c_int64, c_int64, c_int, P, P, c_int64, c_int64, c_int64, c_int, c_int, c_int,
                                       c_float, c_int64, P, c_int, P, c_int64, P]),
+    "uwu_adapter_conv_merge": (c_int, [P, P, P, P, P, P, c_int, c_int64, c_int64, P, c_int64, P, P, P]),
+    "uwu_adapter_conv_grad": (c_int, [P, c_int64, c_int64, c_int64, c_int64, c_int, P, P, c_int64, c_int64, c_int64, c_int,
+                                      c_int, c_int, c_float, P, c_int64, P]),
     "uwu_comm_unique_id": (c_int, [P]),
     "uwu_comm_init": (c_int, [P, c_int, c_int, ctypes.POINTER(c_void_p)]),
     "uwu_allreduce_flat": (c_int, [P, P, c_int64, P]),

@@ -156,7 +156,11 @@ class _Adapters:
     Weight decomposition (``dora_wd``): ``dora``: name of every decomposed weight -> (offset of its
     dora_scale in the adapter buffer, offset of its norms in ``norms``).  Those segments leave the plain table for a second
     one; ``merge`` then is three launches (plain merge, norms, decomposed merge), and ``norms`` -- refreshed by every merge,
-    not state -- is what the backward of that forward divides by."""
+    not state -- is what the backward of that forward divides by.
+
+    Convolution adapters (``enable_conv``): ``convs``: the adapted 3x3 convolution weights.  They have a
+    table of their own (17 fields) and one more entry point in ``merge`` (uwu_adapter_conv_merge: two launches for all of them);
+    ``conv_grad`` is what _Conv3x3Fn.backward calls for one of them."""
 
     def __init__(self, net, P, fp32_names):
         from .adapters import KIND_LOKR, KIND_LOKR_LOWRANK, KIND_LORA, KIND_NORM
@@ -168,6 +172,11 @@ class _Adapters:
             if s.algo == "norm":
                 self.seg[s.name + ".weight"] = (s, KIND_NORM, off(s, "w_norm"), 0, 0)
                 self.seg[s.name + ".bias"] = (s, KIND_NORM, off(s, "b_norm"), 0, 0)
+            elif s.conv is not None:  # a 3x3 convolution: up / w1, then down / w2 (w2_a), then mid / w2_b (section 4.41)
+                t = [off(s, n) for n in {"lora": ("lora_up.weight", "lora_down.weight", "lora_mid.weight"),
+                                         "lokr": ("lokr_w1", "lokr_w2_a" if s.lowrank else "lokr_w2", "lokr_w2_b")}[s.algo]
+                     if (s.name, n) in net.offsets]
+                self.seg[s.name + ".weight"] = (s, s.kind, *(t + [0])[:3])
             elif s.algo == "lora":
                 self.seg[s.name + ".weight"] = (s, KIND_LORA, off(s, "lora_up.weight"), off(s, "lora_down.weight"), 0)
             elif s.lowrank:
@@ -183,7 +192,8 @@ class _Adapters:
             if s.dora:
                 self.dora[nm] = (off(s, "dora_scale"), n)
                 n += pad64(s.shape[0] if s.wd_on_out else s.shape[1])
-        self.plain = [nm for nm in self.names if nm not in self.dora]
+        self.convs = [nm for nm in self.names if self.seg[nm][0].conv is not None]
+        self.plain = [nm for nm in self.names if nm not in self.dora and self.seg[nm][0].conv is None]
         self.norms_n, self.norms = n, None
         self.key = None
         self.eff, self.eff_off = None, {}
@@ -228,8 +238,33 @@ class _Adapters:
         return (host.to(dev), host, torch.tensor(nblk, dtype=torch.int64).to(dev), nblk[-1],
                 torch.tensor(mblk, dtype=torch.int64).to(dev), mblk[-1], len(rows))
 
-    def _launch_merge(self, P, tab, dtab, eff, shadow):
+    def _conv_table(self, P, eff_off, shadow):
+        """the 17-field rows of the convolution segments: (device table, host copy, merge blk_start, merge workgroups,
+        form blk_start, form workgroups, segments, T workspace); None: there is none"""
+        if not self.convs:
+            return None
+        rows, blk, fblk, nt = [], [0], [0], 0
+        for nm in self.convs:
+            spec = self.seg[nm][0]
+            cin, cout, ci, co = spec.conv
+            row = self._row(P, nm, eff_off, shadow) + [cout, cin, ci, nt]
+            rows.append(row)
+            blk.append(blk[-1] + -(-(row[1] * row[2]) // 4096))
+            fblk.append(fblk[-1] + (-(-(9 * spec.r * cin) // 256) if spec.tucker else 0))
+            if spec.tucker:
+                nt += pad64(9 * spec.r * cin)
+        dev = P.flat.device
+        host = torch.tensor(rows, dtype=torch.int64)
+        tws = torch.empty(nt, device=dev, dtype=torch.float32) if nt else None
+        return (host.to(dev), host, torch.tensor(blk, dtype=torch.int64).to(dev), blk[-1],
+                torch.tensor(fblk, dtype=torch.int64).to(dev), fblk[-1], len(rows), tws)
+
+    def _launch_merge(self, P, tab, dtab, eff, shadow, ctab=None):
         base, p = L.ptr(P.flat.data), L.ptr(self.net.flat.data)
+        if ctab is not None:  # every convolution: T of the Tucker segments, then the merge (two launches)
+            t, host, blk, nb, fblk, nf, nseg, tws = ctab
+            L.call("uwu_adapter_conv_merge", base, p, L.ptr(t), host.data_ptr(), L.ptr(blk), L.ptr(fblk), nseg, nb, nf,
+                   L.ptr(tws), tws.numel() if tws is not None else 0, L.ptr(eff), L.ptr(shadow), L.stream())
         if tab is not None:
             t, blk, nseg, nblocks = tab
             L.call("uwu_adapter_merge", base, p, L.ptr(t), L.ptr(blk), nseg, nblocks, L.ptr(eff), L.ptr(shadow), L.stream())
@@ -252,22 +287,25 @@ class _Adapters:
         self.eff = torch.empty(max(n, 64), device=P.flat.device, dtype=torch.float32)
         self.tab = self._table(P, self.eff_off, P.bf16)
         self.dtab = self._dora_table(P, self.eff_off, P.bf16)
+        self.ctab = self._conv_table(P, self.eff_off, P.bf16)
         self.key, self.version = key, None
 
     def needs_merge(self, P):
         return self.key != (P.flat.device, P.bf16) or self.net._dirty or self.version != self.net.flat._version
 
     def merge(self, P):
-        """W_eff = W + dW of every adapted tensor: one launch (with decomposed weights: three)"""
+        """W_eff = W + dW of every adapted tensor: one launch (with decomposed weights: three; with convolutions: one more,
+        and one in front of it that forms T of the Tucker segments)"""
         self.prepare(P)
-        self._launch_merge(P, self.tab, self.dtab, self.eff, P.shadow if P.bf16 else None)
+        self._launch_merge(P, self.tab, self.dtab, self.eff, P.shadow if P.bf16 else None, self.ctab)
         self.net._dirty = False
         self.version = self.net.flat._version
 
     def fold(self, P):
         """W += dW in the base fp32 weights themselves (in place: every element is read and written by one thread)"""
         eff_off = {nm: P.registry[nm][0] for nm in self.names}
-        self._launch_merge(P, self._table(P, eff_off, False), self._dora_table(P, eff_off, False), P.flat.data, None)
+        self._launch_merge(P, self._table(P, eff_off, False), self._dora_table(P, eff_off, False), P.flat.data, None,
+                           self._conv_table(P, eff_off, False))
 
     def eff_view(self, P, name):
         first, n = name if isinstance(name, tuple) else (name, 1)
@@ -306,6 +344,29 @@ class _Adapters:
         else:
             ops.gemm_wgrad_shared(dy, x, dW, blocks=_wgrad_blocks(x.shape[0], N, K))
         self.grad_rows(P, names, dW)
+
+    def conv_grad(self, P, wname, dy, x, B, H, W, C, stride, implicit):
+        """fp32 dW [Cout_store, 9 Cin_store] of an adapted 3x3 convolution into a zeroed scratch (implicit-GEMM or im2col
+        path, no bias gradient), then the adapter gradients from it"""
+        cin, cout, ci, co = self.seg[wname][0].conv
+        dW = _memset_zero(torch.empty(co, 9 * ci, device=dy.device, dtype=torch.float32))
+        if implicit:
+            ops.conv3x3_wgrad(dy, x, dW, None, B, H, W, C, co, stride)
+        else:
+            col = ops.im2col3x3(x, B, H, W, C, stride)
+            ops.gemm_wgrad(dy, col, dW, blocks=_wgrad_blocks(col.shape[0], co, col.shape[1]))
+        self.conv_grad_rows(P, wname, dW)
+
+    def conv_grad_rows(self, P, wname, dW):
+        """the adapter gradients of convolution `wname` from its fp32 weight gradient, added to the adapter gradient"""
+        from .adapters import conv_grad_ws_elems
+
+        spec, kind, pa, pb, pc = self.seg[wname]
+        cin, cout, ci, co = spec.conv
+        ws = torch.empty(max(conv_grad_ws_elems(spec), 1), device=dW.device, dtype=torch.float32)
+        L.call("uwu_adapter_conv_grad", L.ptr(dW), co, ci, cout, cin, kind, L.ptr(self.net.flat.data),
+               L.ptr(self.net.flat.grad), pa, pb, pc, spec.r, spec.out_k, spec.in_n, float(spec.scale), L.ptr(ws), ws.numel(),
+               L.stream())
 
     def dora_grad(self, P, nm, dW):
         """decomposed weight `nm`: dW (dL/dW', its rows of the layer's fp32 weight gradient) becomes dL/d(W + dW) in place
@@ -401,7 +462,8 @@ class _LinearFn(torch.autograd.Function):
 
 class _Conv3x3Fn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, P, wname, bname, B, H, W_, C, stride):
+    def forward(ctx, x, P, wname, bname, B, H, W_, C, stride, anchor):
+        # `anchor` (P.anchor): records the op when x needs no gradient (conv_in under an adapter)
         Wt = P.w(wname)
         # implicit GEMM (the ring kernel gathers its activation rows pixel by pixel; no column matrix) where the shape
         # allows it: bf16, channel counts that are multiples of 32 -- every convolution of the SDXL shape except conv_in
@@ -422,27 +484,29 @@ class _Conv3x3Fn(torch.autograd.Function):
         dy = dy.contiguous()
         Wt = P.w(wname)
         dx = None
-        frozen = P.ad is not None  # (convolutions are never adapted: no weight gradient while the base is frozen)
+        frozen = P.ad is not None  # frozen base: dX with W + dW; the adapter gradients of an adapted convolution
         if frozen and ctx.needs_input_grad[0]:
             if implicit:
                 dx = ops.conv3x3_dgrad(dy, Wt, B, H, W_, C, Wt.shape[0], stride)
             else:
                 dx = ops.col2im3x3(ops.gemm(dy, Wt, trans_b=True), B, H, W_, C, stride)
         if frozen:
-            return (dx,) + (None,) * 8
+            if P.adapted(wname):
+                P.on_side(lambda: P.ad.conv_grad(P, wname, dy, x, B, H, W_, C, stride, implicit), dy, x)
+            return (dx,) + (None,) * 9
         if implicit:
             Cout = Wt.shape[0]
             if ctx.needs_input_grad[0]:
                 dx = ops.conv3x3_dgrad(dy, Wt, B, H, W_, C, Cout, stride)
             P.on_side(lambda: ops.conv3x3_wgrad(dy, x, P.g(wname), P.g(bname), B, H, W_, C, Cout, stride), dy, x)
-            return (dx,) + (None,) * 8
+            return (dx,) + (None,) * 9
         if ctx.needs_input_grad[0]:
             dcol = ops.gemm(dy, Wt, trans_b=True)
             dx = ops.col2im3x3(dcol, B, H, W_, C, stride)
         col = ops.im2col3x3(x, B, H, W_, C, stride)  # recomputed: cheaper than keeping 9x the activation
         ops.gemm_wgrad(dy, col, P.g(wname), blocks=_wgrad_blocks(col.shape[0], Wt.shape[0], col.shape[1]),
                        bias_grad=P.g(bname))
-        return (dx,) + (None,) * 8
+        return (dx,) + (None,) * 9
 
 
 class _GroupNormFn(torch.autograd.Function):
@@ -952,7 +1016,8 @@ class UNet2DConditionModel(FlatModule):
         return _LinearFn.apply(x, self.P, name + ".weight", name + ".bias" if bias else None, fp32, self.P.anchor(name + ".weight"))
 
     def _conv(self, x, name, B, H, W, C, stride=1):
-        return _Conv3x3Fn.apply(x, self.P, name + ".weight", name + ".bias", B, H, W, C, stride)
+        return _Conv3x3Fn.apply(x, self.P, name + ".weight", name + ".bias", B, H, W, C, stride,
+                                self.P.anchor(name + ".weight"))
 
     def _resnet(self, x, emb_act, name, cin, cout, B, H, W):
         HW = H * W
