@@ -370,6 +370,32 @@ int uwu_ema_update(float* avg, const float* p, int64_t n, float keep, float take
  * avg and p 16-byte aligned, p_bf16 8-byte aligned, n > 0; avg == p and overlapping [avg, avg + n) / [p, p + n) are refused. */
 int uwu_ema_swap(float* avg, float* p, void* p_bf16, int64_t n, int mode, void* stream);
 
+/* schedulefree.AdamWScheduleFree (Defazio et al., "The Road Less Scheduled"; AdamWScheduleFree.step, single-tensor path, package
+ * 1.4) on flat buffers.  The package is not a dependency: the rule is restated here.  y is the parameter as training holds it (the
+ * gradient is taken there), z the base iterate, v the second moment.  Per step the host advances, as python floats (doubles):
+ *   sched = (k+1)/warmup_steps if k < warmup_steps else 1 ; bc2 = 1 - beta2^(k+1) ; lr_t = lr * sched
+ *   lr_max = max(lr_t, lr_max) ; weight = (k+1)^r * lr_max^weight_lr_power ; weight_sum += weight
+ *   c = weight / weight_sum   (0 when weight_sum == 0)
+ * and the launch does, per element, with g = g * pre_scale * clip[1] (clip may be NULL; the fp32 factor of uwu_adamw_step):
+ *   v  = beta2*v + (1-beta2)*g*g
+ *   gn = g / (sqrt(v / bc2) + eps) + weight_decay*y                       (y BEFORE the interpolation below)
+ *   y  = lerp(y, z, c)      torch.lerp: y + c*(z - y) for c < 0.5, else z - (z - y)*(1 - c): at c = 1 (the first step) exactly z
+ *   y  = y + lr_t*(beta1*(1-c) - 1) * gn
+ *   z  = z - lr_t*gn
+ * lr_t*(beta1*(1-c) - 1), 1/bc2, 1 - beta2 and 1 - c are formed in double on the host and rounded to fp32 once; the arithmetic
+ * per element is fp32 with every multiply-add fused by hand, so a result does not depend on the grid or on the chunk it was
+ * launched in.  p_bf16 (may be NULL) receives the new y as uwu_cast_f32_to_bf16 rounds, zero_grad leaves g zeroed.  c in [0, 1],
+ * bc2 in (0, 1], n > 0; y, g, z, v 16-byte aligned, p_bf16 8-byte aligned.  16 B read + 12 B written per parameter (+ 2 B for
+ * the shadow, + 4 B for the zeroed gradient): the traffic of uwu_adamw_step. */
+int uwu_sfadamw_step(float* y, float* g, float* z, float* v, void* p_bf16, int64_t n, double lr_t, double beta1, double beta2,
+                     double eps, double weight_decay, double c, double bc2, float pre_scale, const float* clip, int zero_grad,
+                     void* stream);
+
+/* out[i] = lerp(y[i], z[i], weight), torch.lerp's two branches as above, out of place: the weights to evaluate under the
+ * schedule-free rule are x = lerp(y, z, 1 - 1/beta1).  weight and 1 - weight are rounded to fp32 once from double.  y and z are
+ * only read; out must not partly overlap them.  All three 16-byte aligned, n > 0.  8 B read + 4 B written per parameter. */
+int uwu_sf_average(const float* y, const float* z, float* out, int64_t n, double weight, void* stream);
+
 int uwu_cast_f32_to_bf16(const float* src, void* dst, int64_t n, void* stream);
 int uwu_cast_bf16_to_f32(const void* src, float* dst, int64_t n, void* stream);
 

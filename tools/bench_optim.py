@@ -1,9 +1,9 @@
-"""The flat-buffer update kernels (AdamW, Lion, AdamWFP16, the 8-bit block-wise AdamW and Lion, and Prodigy's three:
-uwudiff_amd/csrc/optimizer.hip) alone, with the bf16
+"""The flat-buffer update kernels (AdamW, Lion, AdamWFP16, the 8-bit block-wise AdamW and Lion, Prodigy's three, and schedule-free
+AdamW's step and its out-of-place average: uwudiff_amd/csrc/optimizer.hip) alone, with the bf16
 shadow and ``zero_grad`` on, at DiT-S/2's parameter count and at the SDXL-shape UNet's 2.57 G: ms per launch, bytes moved per
 parameter and GB/s, and the optimizer-state bytes of the SDXL-shape UNet under each optimizer.  Prodigy is shown as its statistics
 pass, its one-workgroup finalize and its apply pass separately, and as the whole step (the three on one stream), next to the AdamW
-kernel of the same run.  One JSON line.  DESIGN.md sections 4.28, 4.36 and 4.40.
+kernel of the same run.  One JSON line.  DESIGN.md sections 4.28, 4.36, 4.40 and 4.42.
 
     python tools/bench_optim.py [--sizes 32966464,2570000000] [--reps 5] [--warmup 3]
 
@@ -21,7 +21,10 @@ DIT_S2, SDXL_UNET = 32_966_464, 2_570_000_000
 # bytes per parameter: (read + written by the update rule, optimizer state held)
 KERNELS = {"adamw": (16 + 12, 8), "lion": (12 + 8, 4), "adamw_fp16": (12 + 8, 4),
            # 8-bit codes + one fp32 scale per 256 elements and moment (the scales' traffic, 1/32 B per parameter, is left out)
-           "adamw8": (10 + 6, 2 + 8 / 256), "lion8": (9 + 5, 1 + 4 / 256)}
+           "adamw8": (10 + 6, 2 + 8 / 256), "lion8": (9 + 5, 1 + 4 / 256),
+           # schedule-free AdamW: y, g, z, v read, y, z, v written; z and v held, and the spare buffer x is written into (4 B)
+           "sfadamw": (16 + 12, 8 + 4)}
+SF_AVERAGE = 8 + 4  # uwu_sf_average: y and z read, x written out of place (no shadow, no gradient)
 EXTRA = 2 + 4  # bf16 shadow written, consumed gradient zeroed
 # Prodigy's passes: bytes per parameter with the extras (statistics: p, g, p0, exp_avg, exp_avg_sq, s read, the three moments
 # written, + 4 for the zeroed gradient; apply: p, exp_avg, exp_avg_sq read, p written, + 2 for the shadow); 16 B of state
@@ -91,6 +94,11 @@ def bench_size(n, reps, warmup):
     # one whole Prodigy step while g is still nonzero (every kernel leaves it zeroed): s is nonzero from here on, so no later step
     # returns early and the apply pass does its full work in every window (checked below)
     launch["prodigy_step"](0)
+    # schedule-free AdamW on a z and v of its own, past its warm-up (0 < c < 1: the first branch of the lerp, as in a long run)
+    sz, sv, sx = p.clone(), f32().zero_(), f32()
+    launch["sfadamw"] = lambda k: L.call("uwu_sfadamw_step", L.ptr(p), L.ptr(g), L.ptr(sz), L.ptr(sv), L.ptr(shadow), n, 1e-6, 0.9,
+                                         0.999, 1e-8, 0.01, 1.0 / (k + 1), 1.0 - 0.999 ** (k + 1), 1.0, None, 1, s)
+    launch["sf_average"] = lambda k: L.call("uwu_sf_average", L.ptr(p), L.ptr(sz), L.ptr(sx), n, 1.0 - 1.0 / 0.9, s)
     iters = max(4, min(200, int(2e11 / (34 * n))))  # a window of roughly 0.2 GB/param-byte: tens of ms at either size
     for k in range(1, warmup + 1):
         for fn in launch.values():
@@ -112,7 +120,7 @@ def bench_size(n, reps, warmup):
     for name, times in ms.items():
         times = sorted(times)
         med = times[len(times) // 2]
-        bpp = KERNELS[name][0] + EXTRA if name in KERNELS else PRODIGY[name]
+        bpp = KERNELS[name][0] + EXTRA if name in KERNELS else SF_AVERAGE if name == "sf_average" else PRODIGY[name]
         out[name] = {"ms": round(med, 4), "ms_min": round(times[0], 4), "ms_max": round(times[-1], 4),
                      "bytes_per_param": bpp, "GBps": round(bpp * n / med / 1e6, 1),
                      "GBps_min": round(bpp * n / times[-1] / 1e6, 1), "GBps_max": round(bpp * n / times[0] / 1e6, 1)}
@@ -120,7 +128,8 @@ def bench_size(n, reps, warmup):
         raise SystemExit("bench_optim.py: Prodigy's last step returned early (d_denom == 0): its apply pass did no work")
     for name in ("prodigy_stats", "prodigy_apply"):  # plain streams: to be judged against the AdamW kernel of this run
         out[name]["GBps_vs_adamw"] = round(out[name]["GBps"] / out["adamw"]["GBps"], 3)
-    for name, ref in (("adamw8", "adamw"), ("lion8", "lion")):  # the 8-bit step against the fp32 step of the same run
+    # the 8-bit step against the fp32 step of the same run; schedule-free AdamW moves AdamW's bytes and is judged against its time
+    for name, ref in (("adamw8", "adamw"), ("lion8", "lion"), ("sfadamw", "adamw")):
         out[name]["ms_vs_" + ref] = round(out[name]["ms"] / out[ref]["ms"], 3)
     return {"n": n, "launches_per_window": iters, "reps": reps, "kernels": out}
 

@@ -283,3 +283,61 @@ class EMAWeightAveraging(WeightAveraging):
 
     def coefficients(self, n_averaged):
         return self.decay, 1.0 - self.decay  # (1 - decay in double: 1 - 0.999f is off by 1.3e-5 relative)
+
+
+class ScheduleFreeMode:
+    """The two modes of ``FusedAdamWScheduleFree`` (optim.py) driven from the hooks of ``Fitter``, which installs
+    this by itself when the optimizer is one: training runs on ``y``, and every validation pass, every checkpoint's ``state_dict`` and
+    the module ``fit`` returns hold the average ``x``.  The spare buffer of the optimizer is the buffer of a ``FlatAverage`` over the
+    module that owns the trained flat buffer (``WeightAveraging._owner``'s rule), so ``x`` goes in place of ``y`` and back the way an
+    average does: no pointer moved, the bf16 shadow refreshed, the adapters merged again, ``y`` back bit for bit."""
+
+    def __init__(self, optimizer):
+        self.opt = optimizer
+        self.average = None
+
+    def _training(self):
+        return bool(self.opt.param_groups[0]["train_mode"])
+
+    def setup(self, fitter, module, stage=None):
+        owner, _ = WeightAveraging._owner(module)
+        self.average = FlatAverage(owner)
+        self.opt.use_average(self.average)
+        self.opt.train()  # (after a resume too: the module was loaded from current_model_state, which is y)
+
+    def on_validation_epoch_start(self, fitter, module):  # (the sanity check at step 0: x = y = z, nothing is exchanged)
+        self.opt.eval()
+
+    def on_validation_epoch_end(self, fitter, module):
+        self.opt.train()
+
+    def on_exception(self, fitter, module, exception):  # a pass that raised: training goes on (or is examined) on y
+        self.opt.train()
+
+    def on_train_end(self, fitter, module):
+        self.opt.eval()  # the module is left holding x, as the averaging callbacks leave the average
+
+    def on_save_checkpoint(self, fitter, module, ckpt):
+        """``state_dict`` carries ``x`` (what a loader of ``state_dict`` / ``unet.`` picks up), ``current_model_state`` ``y``.  Both are
+        read from where they are: while training ``x`` is written into the spare buffer, inside a validation pass ``y`` sits there.  No
+        weight is written while saving."""
+        if self.average is None:
+            return
+        owner, prefix = WeightAveraging._owner(module)
+        p = owner.flat
+        in_module = dict(ckpt["state_dict"])
+        training = self._training()
+        aside = self.opt.write_average(p) if training else self.opt.held_weights(p)
+        if aside is None:  # before the first step: x = y = z
+            ckpt["current_model_state"] = in_module
+            return
+        other = {**in_module, **{prefix + k: v.detach().cpu() for k, v in self.average.averaged_state().items()}}
+        ckpt["current_model_state"], ckpt["state_dict"] = (in_module, other) if training else (other, in_module)
+
+    def on_load_checkpoint(self, fitter, module, ckpt):
+        if "current_model_state" not in ckpt:
+            if fitter.global_rank == 0:
+                print("ScheduleFreeMode: the checkpoint has no current_model_state (it was written under another optimizer): training "
+                      "starts with y = the loaded weights", flush=True)
+            return
+        ckpt["state_dict"] = ckpt["current_model_state"]  # the module resumes from y; z, v and the scalars come with the optimizer state

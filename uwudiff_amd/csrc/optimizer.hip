@@ -3,6 +3,7 @@
 // AdamWFP16 20 B/param (+2 B/param for the bf16 shadow, +4 B/param for the zeroed gradient), the average's update 12 B/param.
 // Prodigy (further down) is three kernels round two global sums: 40 + 18 B/param with the shadow and the zeroed gradient.
 // The 8-bit block-wise AdamW / Lion (last section) keep 1 B per moment and parameter and one fp32 scale per 256: 16 / 14 B/param.
+// Schedule-free AdamW (next to the weight average, whose exchange kernel it uses) moves AdamW's 28 B/param; its average 12 B/param.
 // Reference: src/duwu/trainer/trainer.py:52-74 (torch.optim.AdamW + Lightning gradient_clip_val),
 // src/duwu/trainer/optimizers.py (AdamWFP16), lion_pytorch.Lion (configs/demo_training*.yaml, commented alternative).
 #include "common.h"
@@ -288,6 +289,87 @@ __global__ void __launch_bounds__(256) ema_swap_kernel(uint32_t* __restrict__ av
   }
 }
 
+// schedulefree.AdamWScheduleFree (Defazio et al., "The Road Less Scheduled"; the rule at uwu_sfadamw_step in include/uwu_hip.h):
+//   v = b2*v + (1-b2) g^2 ; gn = g / (sqrt(v/bc2) + eps) + wd*y ; y = lerp(y, z, c) + a*gn ; z = z - lr_t*gn
+// torch.lerp's two branches, chosen by the weight alone (uniform over the launch): at w = 1 the second gives `end` exactly.
+__device__ __forceinline__ float lerp2(float start, float end, float w, float omw) {
+  const float d = end - start;
+  return w < 0.5f ? __builtin_fmaf(w, d, start) : __builtin_fmaf(-d, omw, end);
+}
+
+// fp32 roundings on each output's path, counted for the tests' bounds (each hyper-parameter's own rounding to fp32 counts as one;
+// a fused multiply-add rounds once where the count takes the product and the sum apart):
+//   v:  the g^2 term carries gscale (1) and g*gscale (1) twice, omb2 (1) and its two products (2) = 7, v*b2 carries b2 (1) and the
+//       product (1); the sum adds 1 to both:                                              K_v = 8 on |v|
+//   gn: denom = sqrt(v*inv_bc2) + eps: (8 + inv_bc2 1 + product 1) / 2 = 5, sqrt 1, the sum 1 = 7 (eps's own rounding is on the
+//       smaller term); g/denom = 2 + 7 + the division 1 = 10; wd*y = 2 on a term lr_t*wd times |y|; the sum 1:  11 on |gn|
+//   z:  lr_t (1) + gn (11) + the fma (1) = 13 on lr_t*|gn|, 1 on |z|:                     K_z = 16 on |z| + lr_t*|gn|
+//   y:  lerp = z - y (1), c (1), product (1), sum (1) on at most |y| + |z|; a (1) + gn (11) + the fma (1) = 13 on |a|*|gn|,
+//       |a| <= lr_t:                                                                      K_y = 16 on |y| + |z| + lr_t*|gn|
+//   (16 = 13 and the division and square root taken as 2 units each instead of 1, should the build not round them correctly)
+__device__ __forceinline__ void sfadamw_elem(float& y, float g, float& z, float& v, float b2, float omb2, float inv_bc2,
+                                             float eps, float wd, float c, float omc, float a, float neg_lr) {
+  // every multiply-add is written out: the vector body and the scalar tail round alike, whatever the compiler would contract
+  const float vn = __builtin_fmaf(v, b2, (omb2 * g) * g);
+  const float gn = __builtin_fmaf(wd, y, g / (sqrtf(vn * inv_bc2) + eps));
+  y =__builtin_fmaf(a, gn, lerp2(y, z, c, omc));
+  z = __builtin_fmaf(neg_lr, gn, z);
+  v = vn;
+}
+
+__global__ void __launch_bounds__(256) sfadamw_kernel(float* __restrict__ y, float* __restrict__ g, float* __restrict__ z,
+                                                      float* __restrict__ v, bf16_t* __restrict__ pbf, int64_t n, float b2,
+                                                      float omb2, float inv_bc2, float eps, float wd, float c, float omc,
+                                                      float a, float neg_lr, float pre_scale,
+                                                      const float* __restrict__ clip, int zero_grad) {
+  const float gscale = pre_scale * (clip ? clip[1] : 1.f);
+  const int64_t n4 = n >> 2;
+  const int64_t stride = (int64_t)gridDim.x * 256;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
+    f32x4 yv = load4(y + 4 * i), gv = load4(g + 4 * i), zv = load4(z + 4 * i), vv = load4(v + 4 * i);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      float yy = yv[j], zz = zv[j], vn = vv[j];
+      sfadamw_elem(yy, gv[j] * gscale, zz, vn, b2, omb2, inv_bc2, eps, wd, c, omc, a, neg_lr);
+      yv[j] = yy;
+      zv[j] = zz;
+      vv[j] = vn;
+    }
+    store4(y + 4 * i, yv);
+    store4(z + 4 * i, zv);
+    store4(v + 4 * i, vv);
+    if (pbf) store4(pbf + 4 * i, yv);
+    if (zero_grad) store4(g + 4 * i, f32x4{0.f, 0.f, 0.f, 0.f});
+  }
+  if (blockIdx.x == 0) {
+    for (int64_t i = (n4 << 2) + threadIdx.x; i < n; i += 256) {
+      float yy = y[i], zz = z[i], vn = v[i];
+      sfadamw_elem(yy, g[i] * gscale, zz, vn, b2, omb2, inv_bc2, eps, wd, c, omc, a, neg_lr);
+      y[i] = yy;
+      z[i] = zz;
+      v[i] = vn;
+      if (pbf) pbf[i] = (bf16_t)yy;
+      if (zero_grad) g[i] = 0.f;
+    }
+  }
+}
+
+// out = lerp(y, z, w), out of place: the averaged weights x of the schedule-free rule at w = 1 - 1/beta1.  8 B read + 4 B written.
+__global__ void __launch_bounds__(256) sf_average_kernel(const float* __restrict__ y, const float* __restrict__ z,
+                                                         float* __restrict__ out, int64_t n, float w, float omw) {
+  const int64_t n4 = n >> 2;
+  const int64_t stride = (int64_t)gridDim.x * 256;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
+    f32x4 yv = load4(y + 4 * i), zv = load4(z + 4 * i);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) yv[j] = lerp2(yv[j], zv[j], w, omw);
+    store4(out + 4 * i, yv);
+  }
+  if (blockIdx.x == 0) {
+    for (int64_t i = (n4 << 2) + threadIdx.x; i < n; i += 256) out[i] = lerp2(y[i], z[i], w, omw);
+  }
+}
+
 template <typename TS, typename TD>
 __global__ void __launch_bounds__(256) cast_kernel(const TS* __restrict__ s, TD* __restrict__ d, int64_t n) {
   const int64_t n4 = n >> 2;
@@ -395,6 +477,34 @@ extern "C" int uwu_ema_swap(float* avg, float* p, void* p_bf16, int64_t n, int m
   hipLaunchKernelGGL(ema_swap_kernel, dim3(ew_grid(n / 4, 256)), dim3(256), 0, (hipStream_t)stream, (uint32_t*)avg,
                      (uint32_t*)p, (bf16_t*)p_bf16, n, mode == 0);
   UWU_LAUNCH_CHECK("ema_swap");
+  return UWU_OK;
+}
+
+extern "C" int uwu_sfadamw_step(float* y, float* g, float* z, float* v, void* p_bf16, int64_t n, double lr_t, double beta1,
+                                double beta2, double eps, double weight_decay, double c, double bc2, float pre_scale,
+                                const float* clip, int zero_grad, void* stream) {
+  UWU_CHECK_ARG(y && g && z && v, "sfadamw_step: null pointer");
+  UWU_CHECK_ARG(n > 0, "sfadamw_step: n must be positive");
+  UWU_CHECK_ARG((((uintptr_t)y | (uintptr_t)g | (uintptr_t)z | (uintptr_t)v) & 15) == 0,
+                "sfadamw_step: buffers must be 16-byte aligned");
+  UWU_CHECK_ARG(p_bf16 == nullptr || ((uintptr_t)p_bf16 & 7) == 0, "sfadamw_step: bf16 shadow must be 8-byte aligned");
+  UWU_CHECK_ARG(c >= 0.0 && c <= 1.0 && bc2 > 0.0 && bc2 <= 1.0, "sfadamw_step: c must be in [0, 1] and bc2 in (0, 1]");
+  // the folded factors in double on the host, as the package forms them with python floats; each is rounded to fp32 once
+  const double a = lr_t * (beta1 * (1.0 - c) - 1.0);
+  hipLaunchKernelGGL(sfadamw_kernel, dim3(ew_grid(n / 4, 256)), dim3(256), 0, (hipStream_t)stream, y, g, z, v,
+                     (bf16_t*)p_bf16, n, (float)beta2, (float)(1.0 - beta2), (float)(1.0 / bc2), (float)eps,
+                     (float)weight_decay, (float)c, (float)(1.0 - c), (float)a, (float)(-lr_t), pre_scale, clip, zero_grad);
+  UWU_LAUNCH_CHECK("sfadamw_step");
+  return UWU_OK;
+}
+
+extern "C" int uwu_sf_average(const float* y, const float* z, float* out, int64_t n, double weight, void* stream) {
+  UWU_CHECK_ARG(y && z && out, "sf_average: null pointer");
+  UWU_CHECK_ARG(n > 0, "sf_average: n must be positive");
+  UWU_CHECK_ARG((((uintptr_t)y | (uintptr_t)z | (uintptr_t)out) & 15) == 0, "sf_average: buffers must be 16-byte aligned");
+  hipLaunchKernelGGL(sf_average_kernel, dim3(ew_grid(n / 4, 256)), dim3(256), 0, (hipStream_t)stream, y, z, out, n,
+                     (float)weight, (float)(1.0 - weight));
+  UWU_LAUNCH_CHECK("sf_average");
   return UWU_OK;
 }
 

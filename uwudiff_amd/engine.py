@@ -4,7 +4,8 @@ global-norm clipping, optimizer + per-step LR schedule, rank-aware seeding, peri
 (``val_check_interval`` and its companions; a pass is :meth:`Fitter.validate`), and gradient accumulation
 (``accumulate_grad_batches``: an optimizer step every N-th batch on the summed gradient / N), and the callback
 hooks a weight average needs (``setup``, ``on_train_batch_end``, ``on_train_epoch_end``, ``on_train_end``, ``on_save_checkpoint``,
-``on_load_checkpoint``, ``on_exception``, a callback's own ``state_dict``: uwudiff_amd/averaging.py).
+``on_load_checkpoint``, ``on_exception``, a callback's own ``state_dict``: uwudiff_amd/averaging.py).  The same
+hooks carry the two modes of the schedule-free optimizer (``ScheduleFreeMode``, installed by ``fit`` itself: DESIGN.md section 4.42).
 
 Lightning's loop is third-party control plane; the hot path it drives (loss -> denoiser fwd/bwd -> all-reduce ->
 clip -> AdamW) is the part this build implements natively.  Checkpoint / resume follow Lightning's file layout
@@ -19,9 +20,9 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from .averaging import WeightAveraging
+from .averaging import ScheduleFreeMode, WeightAveraging
 from .gradsync import FlatGradSync
-from .optim import FlatFusedOptimizer
+from .optim import FlatFusedOptimizer, FusedAdamWScheduleFree
 from .preprocess import RaggedImages, ragged_to_device
 
 
@@ -123,7 +124,10 @@ class LearningRateMonitor:
         self.kw = kw
 
     def extra(self, opt):
-        return {"d": float(opt.d)} if hasattr(opt, "d") else {}
+        out = {"d": float(opt.d)} if hasattr(opt, "d") else {}
+        if "scheduled_lr" in opt.param_groups[0]:  # schedule-free AdamW: `lr` times its own warm-up (a host float, no sync)
+            out["scheduled_lr"] = float(opt.param_groups[0]["scheduled_lr"])
+        return out
 
 
 class GradualWarmupScheduler:
@@ -269,7 +273,8 @@ class Fitter:
         """Resume: parameters (+ bf16 shadow), optimizer moments / step count, scheduler, global_step."""
         module, opt, sched = self._fit_state
         ckpt = torch.load(path, map_location="cpu", weights_only=True)
-        if "current_model_state" in ckpt and not any(isinstance(cb, WeightAveraging) for cb in self.callbacks) and self.global_rank == 0:
+        two_sets = (WeightAveraging, ScheduleFreeMode)  # who reads current_model_state
+        if "current_model_state" in ckpt and not any(isinstance(cb, two_sets) for cb in self.callbacks) and self.global_rank == 0:
             print("resume: the checkpoint was written with weight averaging and this run has no such callback: the averaged weights "
                   "of state_dict are loaded, the trained weights under current_model_state were not used", flush=True)
         self._hook("on_load_checkpoint", module, ckpt)  # (may redirect ckpt["state_dict"])
@@ -429,6 +434,15 @@ class Fitter:
         opt = cfg["optimizer"] if isinstance(cfg, dict) else cfg
         sched = cfg["lr_scheduler"]["scheduler"] if isinstance(cfg, dict) and "lr_scheduler" in cfg else None
         fused = isinstance(opt, FlatFusedOptimizer)
+        # the schedule-free optimizer trains y and evaluates x: its two modes ride on the callback hooks, ahead of the user's callbacks
+        self.callbacks[:] = [cb for cb in self.callbacks if not isinstance(cb, ScheduleFreeMode)]  # (an earlier fit's)
+        if isinstance(opt, FusedAdamWScheduleFree):
+            averaging = [type(cb).__name__ for cb in self.callbacks if isinstance(cb, WeightAveraging)]
+            if averaging:
+                raise ValueError(f"{averaging[0]} together with {type(opt).__name__} (schedulefree.AdamWScheduleFree): the callback would "
+                                 f"average y, the point the gradient is taken at, which is no model to evaluate; the optimizer keeps "
+                                 f"its own average x and fit validates and saves that one.  Remove the callback")
+            self.callbacks.insert(0, ScheduleFreeMode(opt))
         sync = FlatGradSync(self.world_size)
         lyc = getattr(module, "lycoris_model", None)  # adapter training: the UNet is frozen, the adapter buffer trains
         if fused and lyc is None:  # the early (inside-backward) reduction is consumed by the fused optimizers' per-chunk waits only; a foreign

@@ -93,6 +93,8 @@ _SIGS = {
     "uwu_prodigy_apply": (c_int, [P, P, P, P, c_int64, P, c_double, c_double, c_int, P]),
     "uwu_ema_update": (c_int, [P, P, c_int64, c_float, c_float, P]),
     "uwu_ema_swap": (c_int, [P, P, P, c_int64, c_int, P]),
+    "uwu_sfadamw_step": (c_int, [P, P, P, P, P, c_int64] + [c_double] * 7 + [c_float, P, c_int, P]),
+    "uwu_sf_average": (c_int, [P, P, P, c_int64, c_double, P]),
     "uwu_cast_f32_to_bf16": (c_int, [P, P, c_int64, P]),
     "uwu_cast_bf16_to_f32": (c_int, [P, P, c_int64, P]),
     "uwu_adapter_merge": (c_int, [P, P, P, P, c_int, c_int64, P, P, P]),

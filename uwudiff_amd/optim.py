@@ -5,7 +5,9 @@ YAML, reference src/duwu/trainer/trainer.py:52-74, configs/demo_training_latent.
 ``lion_pytorch.Lion`` (the commented alternative of the reference's training YAMLs) and ``FusedAdamWFP16`` the reference's own
 ``duwu.trainer.optimizers.AdamWFP16`` (src/duwu/trainer/optimizers.py); ``FusedProdigy`` is ``prodigyopt.Prodigy``, whose step
 size comes from two sums over all parameters kept on the device; ``FusedAdamW8bit`` / ``FusedLion8bit`` keep the moments as 8-bit
-codes with one scale per block of 256 elements (the state layout of ``bitsandbytes.optim.AdamW8bit`` / ``Lion8bit``).
+codes with one scale per block of 256 elements (the state layout of ``bitsandbytes.optim.AdamW8bit`` / ``Lion8bit``);
+``FusedAdamWScheduleFree`` is ``schedulefree.AdamWScheduleFree``, whose trained weights ``y`` are not the weights ``x`` to evaluate
+(its docstring states the rule; ``eval()`` / ``train()`` put one in place of the other).
 ``FlatFusedOptimizer`` is what they share and what
 the trainer's fused path asks for: Lightning's ``gradient_clip_val`` (global L2 norm, demo_training.yaml:12) as a device
 coefficient, one launch per flat parameter buffer (or per reduced chunk of it), the consumed gradient zeroed and the bf16
@@ -518,6 +520,189 @@ class FusedLion8bit(_Flat8bit):
         L.call("uwu_lion8_step", p_ptr, g_ptr, L.ptr(st["state1"]), L.ptr(st["absmax1"]), L.ptr(st["qmap1"]), shadow_ptr,
                st["state1"].numel(), e0, e1, float(group["lr"]), b1, b2, group["weight_decay"], pre_scale, clip_ptr, zero_grad,
                L.stream())
+
+
+class FusedAdamWScheduleFree(FlatFusedOptimizer):
+    """``schedulefree.AdamWScheduleFree`` (Defazio et al., "The Road Less Scheduled") on a flat buffer: no learning-rate schedule,
+    the gradient taken at an interpolation ``y`` and the model to validate, checkpoint and sample from the average ``x``.  The package
+    is not installed here; the rule below follows ``AdamWScheduleFree.step`` (single-tensor path, package 1.4), is restated at
+    ``uwu_sfadamw_step`` (include/uwu_hip.h) and pinned by an fp64 oracle (tests/test_schedulefree_cpu.py).  Checkpoint interchange
+    with the package is not verified.
+
+    Per parameter group, python floats on the host, advanced once per optimizer step (never once per chunk)::
+
+        k (starts 0)    weight_sum (starts 0.0)    lr_max (starts -1.0)    train_mode (starts False)
+        sched       = (k + 1) / warmup_steps  if k < warmup_steps  else 1.0
+        bc2         = 1 - beta2 ** (k + 1)
+        lr_t        = lr * sched                      -> group["scheduled_lr"]
+        lr_max      = max(lr_t, lr_max)
+        weight      = (k + 1) ** r * lr_max ** weight_lr_power
+        weight_sum += weight
+        c           = weight / weight_sum             (0.0 when weight_sum == 0)
+
+    Per element, with ``y`` the parameter as training holds it, ``g`` the gradient after ``pre_scale`` and the clip coefficient, and
+    the state ``z`` (starts as a copy of the parameter) and ``exp_avg_sq`` (``v``, starts 0)::
+
+        v  = beta2 * v + (1 - beta2) * g * g
+        gn = g / (sqrt(v / bc2) + eps) + weight_decay * y       # y BEFORE the interpolation below
+        y  = lerp(y, z, c)                                      # torch.lerp's two branches: exactly z at c = 1 (the first step)
+        y  = y + lr_t * (beta1 * (1 - c) - 1) * gn
+        z  = z - lr_t * gn
+        k += 1   (after all elements)
+
+    ``step()`` while ``train_mode`` is False raises ``RuntimeError``, as the package does.  The two modes::
+
+        eval():   if train_mode:      p = lerp(y, z, 1 - 1/beta1)    # x, the average; train_mode = False
+        train():  if not train_mode:  p = y again;                   train_mode = True
+
+    One departure from the package: it gets ``y`` back from ``x`` with a second ``lerp``, which does not round-trip in fp32.  Here
+    ``eval()`` writes ``x`` out of place into a spare fp32 buffer as long as the parameter (``uwu_sf_average``) and exchanges the two
+    with ``uwu_ema_swap``, which also refreshes the bf16 shadow and moves no pointer; ``train()`` exchanges them back: ``y`` returns
+    bit for bit.  The spare buffer is allocated at the first ``eval()`` after a step, or is the buffer of a ``FlatAverage``
+    (averaging.py) handed over with ``use_average``: the exchange then goes through it, and the owner of the flat buffer learns
+    that its weights were written (the UNet merges its adapters again).  8 B of state per parameter and 4 B for the spare buffer.
+
+    ``foreach`` is accepted for the package's signature and ignored.  Not built: ``SGDScheduleFree``, ``RAdamScheduleFree``, the
+    closure / reference / wrapper classes, several parameter groups with different ``lr`` (the scalars are kept per group, but the
+    fit loop trains one flat buffer and nothing tests more), and the recalibration of BatchNorm statistics (no batch norm trains
+    here)."""
+
+    def __init__(self, params, lr=0.0025, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, warmup_steps=0, r=0.0,
+                 weight_lr_power=2.0, foreach=None):
+        if not 0.0 <= lr:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if not 0.0 <= eps:
+            raise ValueError(f"Invalid epsilon value: {eps}")
+        if not 0.0 < betas[0] < 1.0:  # (1 / beta1 gives the averaged weights)
+            raise ValueError(f"Invalid beta parameter at index 0: {betas[0]} (schedule-free AdamW needs 0 < beta1 < 1)")
+        if not 0.0 <= betas[1] < 1.0:
+            raise ValueError(f"Invalid beta parameter at index 1: {betas[1]}")
+        if not 0.0 <= weight_decay:
+            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+        super().__init__(params, dict(lr=lr, betas=tuple(betas), eps=eps, r=r, k=0, warmup_steps=warmup_steps, train_mode=False,
+                                      weight_sum=0.0, lr_max=-1.0, scheduled_lr=0.0, weight_lr_power=weight_lr_power,
+                                      weight_decay=weight_decay, foreach=foreach))
+        self._spare = {}  # parameter -> the spare fp32 buffer (x is written there; it holds y while the parameter holds x)
+        self._averages = {}  # parameter -> the FlatAverage whose buffer is the spare one (use_average)
+        self._held = set()  # parameters whose spare buffer holds y right now
+        self._now = {}  # id(group) -> (lr_t, c, bc2) of the step being launched
+        self.register_load_state_dict_post_hook(FusedAdamWScheduleFree._nothing_held)
+
+    @staticmethod
+    def step_scalars(group):
+        """The host side of one step from the group's scalars, none of them changed: (lr_t, lr_max, weight_sum, c, bc2).  Pure python:
+        needs no GPU."""
+        k, warmup = int(group["k"]), group["warmup_steps"]
+        sched = (k + 1) / warmup if k < warmup else 1.0
+        bc2 = 1 - group["betas"][1] ** (k + 1)
+        lr_t = group["lr"] * sched
+        lr_max = max(lr_t, group["lr_max"])
+        weight = ((k + 1) ** group["r"]) * (lr_max ** group["weight_lr_power"])
+        weight_sum = group["weight_sum"] + weight
+        c = weight / weight_sum if weight_sum != 0 else 0.0
+        return lr_t, lr_max, weight_sum, c, bc2
+
+    def _init_state(self, p, st):
+        st["z"] = torch.clone(p.data, memory_format=torch.preserve_format)
+        st["exp_avg_sq"] = _zeros_like(p.data)
+
+    def _launch(self, group, st, p_ptr, g_ptr, shadow_ptr, off, ln, pre_scale, clip_ptr, zero_grad):
+        b1, b2 = group["betas"]
+        lr_t, c, bc2 = self._now[id(group)]
+        L.call("uwu_sfadamw_step", p_ptr, g_ptr, L.ptr(st["z"]) + 4 * off, L.ptr(st["exp_avg_sq"]) + 4 * off, shadow_ptr, ln, lr_t,
+               b1, b2, float(group["eps"]), float(group["weight_decay"]), c, bc2, pre_scale, clip_ptr, zero_grad, L.stream())
+
+    @torch.no_grad()
+    def step(self, *args, **kwargs):
+        if not all(g["train_mode"] for g in self.param_groups):
+            raise RuntimeError("Optimizer was not in train mode when step is called. Please insert .train() and .eval() calls on the "
+                               "optimizer. See the schedulefree documentation for details.")
+        ahead = [self.step_scalars(g) for g in self.param_groups]  # once per step, before the first chunk's launch
+        self._now = {id(g): (float(lr_t), float(c), float(bc2)) for g, (lr_t, _, _, c, bc2) in zip(self.param_groups, ahead)}
+        try:
+            loss = super().step(*args, **kwargs)
+        finally:
+            self._now = {}
+        for g, (lr_t, lr_max, weight_sum, _, _) in zip(self.param_groups, ahead):  # (a step that raised advances nothing)
+            g["scheduled_lr"], g["lr_max"], g["weight_sum"] = lr_t, lr_max, weight_sum
+            g["k"] = int(g["k"]) + 1
+        return loss
+
+    # ------------------------------------------------------------------ the two modes
+    def use_average(self, average):
+        """``average`` (a ``FlatAverage`` over the module that owns the trained flat buffer) lends its buffer as the spare one and its
+        ``swap`` as the exchange.  Call it while in train mode (nothing is held in a spare buffer then)."""
+        p = average.owner.flat
+        if p in self._held:
+            raise RuntimeError("FusedAdamWScheduleFree.use_average: call train() first (the spare buffer holds the trained weights)")
+        self._averages[p] = average
+        self._spare.pop(p, None)
+
+    def _spare_of(self, p):
+        avg = self._averages.get(p)
+        if avg is not None:
+            return avg.avg
+        buf = self._spare.get(p)
+        if buf is None or buf.numel() != p.numel() or buf.device != p.device:
+            buf = self._spare[p] = torch.empty_like(p.data, memory_format=torch.contiguous_format)
+        return buf
+
+    def _exchange(self, p):
+        avg = self._averages.get(p)
+        if avg is not None:
+            avg.swap()
+            return
+        shadow = getattr(p, "_uwu_bf16_shadow", None)
+        if shadow is not None and shadow.numel() != p.numel():
+            shadow = None
+        L.call("uwu_ema_swap", L.ptr(self._spare[p]), L.ptr(p.data), L.ptr(shadow), p.numel(), 0, L.stream())
+
+    @torch.no_grad()
+    def write_average(self, p):
+        """``x = lerp(y, z, 1 - 1/beta1)`` of parameter ``p`` written into its spare buffer, which is returned; ``p`` is only read.
+        Train mode only (in eval mode ``p`` holds ``x`` already).  None before the first step: ``x`` is the parameter itself."""
+        group = next(g for g in self.param_groups if any(q is p for q in g["params"]))
+        if not group["train_mode"]:
+            raise RuntimeError("FusedAdamWScheduleFree.write_average: the parameter holds the average already (eval mode)")
+        if p not in self.state or "z" not in self.state[p]:
+            return None
+        spare = self._spare_of(p)
+        L.call("uwu_sf_average", L.ptr(p.data), L.ptr(self.state[p]["z"]), L.ptr(spare), p.numel(), 1.0 - 1.0 / group["betas"][0],
+               L.stream())
+        return spare
+
+    def held_weights(self, p):
+        """the buffer that holds ``y`` while ``p`` holds ``x`` (eval mode, after a step); None otherwise"""
+        return self._spare_of(p) if p in self._held else None
+
+    @torch.no_grad()
+    def eval(self):
+        """The parameters become the average ``x`` (and their bf16 shadow follows); ``y`` is kept aside.  Does nothing in eval mode."""
+        for group in self.param_groups:
+            if not group["train_mode"]:
+                continue
+            for p in group["params"]:
+                if self.write_average(p) is not None:  # (before the first step x = y = z: nothing to exchange)
+                    self._exchange(p)
+                    self._held.add(p)
+            group["train_mode"] = False
+
+    @torch.no_grad()
+    def train(self):
+        """The parameters become ``y`` again, bit for bit.  Does nothing in train mode.  After ``load_state_dict`` nothing is kept aside:
+        the parameters are taken to hold ``y`` (the fit loop resumes from ``current_model_state``)."""
+        for group in self.param_groups:
+            if group["train_mode"]:
+                continue
+            for p in group["params"]:
+                if p in self._held:
+                    self._exchange(p)
+                    self._held.discard(p)
+            group["train_mode"] = True
+
+    def _nothing_held(self):
+        """after ``load_state_dict``: whatever mode the state was saved in, no spare buffer holds a ``y`` of this optimizer"""
+        self._held.clear()
 
 
 def cosine_lr(base_lr, step, T_max, eta_min):
