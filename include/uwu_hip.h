@@ -224,6 +224,22 @@ int uwu_image_resize_crop(const void* src, int64_t src_bytes, const int64_t* src
 
 /* ------------------------------------------------------------------ optimizer (a15) */
 
+/* Roundings.  Every update rule below is one function of one element (csrc/optimizer_shared.h and the optimizer*.hip files), with
+ * each fused multiply-add and each separately rounded product written out and compiler contraction off.  An element's result
+ * therefore does not depend on where it sits in a launch (16-byte vector body, scalar head or tail, ragged 8-bit block), nor on
+ * n, the chunking or the grid.  fma(a, b, c) below is one rounding of a*b + c; every other operation rounds by itself:
+ *   AdamW       gs = gscale*g ; m = fma(1-beta1, fma(gscale, g, -m), m) ; v = fma(beta2, v, gs*((1-beta2)*gs))
+ *               p = fma(1 - lr*wd, p, -(lr/bc1) * (m / fma(1/sqrt(bc2), sqrt(v), eps)))         (8-bit AdamW: the same function)
+ *   Lion        c = fma(beta1, m, (1-beta1)*g) ; p = fma(1 - lr*wd, p, -(lr*sign(c))) ; m = fma(beta2, m, (1-beta2)*g)
+ *   AdamWFP16   m = fma(1-beta1, g, beta1*float(m16)) ; v = fma(beta2, float(v16), g*((1-beta2)*g))
+ *               p = fma(-step_size, m / (sqrt(v) + eps), p) ; m16 = half(m), v16 = half(v) of the fp32-rounded values
+ *   Prodigy     in double: g = fma(gscale, g, wd*p) ; sum += fma(p0 - p, g, .) ; exp_avg = fma(beta1, exp_avg, (d(1-beta1))*g) ;
+ *               exp_avg_sq = fma(beta2, exp_avg_sq, g*((d d (1-beta2))*g)) ; s = fma(beta3, s, cs*g) ; each stored as fp32 ;
+ *               in fp32: p = fma(p, 1 - wd*dlr, -(dlr * (exp_avg / (sqrt(exp_avg_sq) + d*eps))))
+ *   average     avg = fma(keep, avg, take*p) ; schedule-free AdamW: at uwu_sfadamw_step
+ * g in Lion, AdamWFP16 and schedule-free AdamW is the rounded product of the gradient and gscale = pre_scale * clip[1].
+ * 1 - lr*wd is fma(-lr, wd, 1) in fp32 on the device for uwu_adamw_step and a double difference on the host elsewhere. */
+
 /* Global L2 norm of a flat fp32 buffer (Lightning gradient_clip_val, demo_training.yaml:12):
  * out[0] = sum(g^2) * pre_scale^2 ; out[1] = clip coefficient min(1, max_norm/(sqrt(out[0])+1e-6))
  * (max_norm <= 0 -> 1).  partial: workspace of >= 1024 floats. */

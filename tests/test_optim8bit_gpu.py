@@ -1,4 +1,4 @@
-"""GPU: the 8-bit block-wise AdamW / Lion kernels (csrc/optimizer.hip: uwu_adamw8_step, uwu_lion8_step) one step at a time against
+"""GPU: the 8-bit block-wise AdamW / Lion kernels (csrc/optimizer_8bit.hip: uwu_adamw8_step, uwu_lion8_step) one step at a time against
 the fp64 oracle (tests/optim8bit_oracle.py) from the oracle's own starting state, above the grid cap, under chunking (the classes of
 uwudiff_amd/optim.py), on the fixed quadratic problem, and their refusals.
 

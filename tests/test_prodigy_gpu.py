@@ -1,4 +1,4 @@
-"""GPU: the fused Prodigy optimizer (uwu_prodigy_stats / _finalize / _apply, csrc/optimizer.hip; uwudiff_amd.optim.FusedProdigy)
+"""GPU: the fused Prodigy optimizer (uwu_prodigy_stats / _finalize / _apply, csrc/optimizer_prodigy.hip; uwudiff_amd.optim.FusedProdigy)
 against the fp64 restatement of tests/test_prodigy_cpu.py, one step at a time from the device's own previous state; the early
 return, the shadow and the zeroed gradient, chunked launches and run-to-run determinism, argument refusals, the fit loop
 (clip, accumulation, checkpoint resume), LyCORIS adapters and two ranks."""

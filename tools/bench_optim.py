@@ -1,5 +1,5 @@
 """The flat-buffer update kernels (AdamW, Lion, AdamWFP16, the 8-bit block-wise AdamW and Lion, Prodigy's three, and schedule-free
-AdamW's step and its out-of-place average: uwudiff_amd/csrc/optimizer.hip) alone, with the bf16
+AdamW's step and its out-of-place average: uwudiff_amd/csrc/optimizer*.hip) alone, with the bf16
 shadow and ``zero_grad`` on, at DiT-S/2's parameter count and at the SDXL-shape UNet's 2.57 G: ms per launch, bytes moved per
 parameter and GB/s, and the optimizer-state bytes of the SDXL-shape UNet under each optimizer.  Prodigy is shown as its statistics
 pass, its one-workgroup finalize and its apply pass separately, and as the whole step (the three on one stream), next to the AdamW

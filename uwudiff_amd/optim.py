@@ -1,4 +1,4 @@
-"""Fused flat-buffer optimizers + global-norm clip on the HIP kernels (csrc/optimizer.hip).
+"""Fused flat-buffer optimizers + global-norm clip on the HIP kernels (csrc/optimizer*.hip).
 
 ``FusedAdamW`` mirrors ``torch.optim.AdamW`` single-tensor semantics (the reference instantiates ``torch.optim.AdamW`` from
 YAML, reference src/duwu/trainer/trainer.py:52-74, configs/demo_training_latent.yaml:30-39), ``FusedLion`` is
@@ -30,14 +30,31 @@ def _zeros_like(t, dtype=None):
     return z
 
 
+def _shadow_of(p):
+    """the bf16 shadow the kernels refresh along with ``p``: the one attached to it, if it covers the whole buffer"""
+    shadow = getattr(p, "_uwu_bf16_shadow", None)
+    return shadow if shadow is not None and shadow.numel() == p.numel() else None
+
+
 class FlatFusedOptimizer(torch.optim.Optimizer):
     """Base of the optimizers that update a flat fp32 parameter buffer with one HIP kernel.  A subclass gives the state
     (``_init_state``) and the launch over one sub-range (``_launch``); ``_finish`` runs once per parameter after the
     launches of all chunks."""
 
+    STATE_DTYPES = {}  # state key -> the dtype it is kept in, where that is not the parameter's
+
     def __init__(self, params, defaults):
         super().__init__(params, defaults)
         self._norm_ws = {}
+        self.register_load_state_dict_post_hook(FlatFusedOptimizer._restore_state_dtypes)
+
+    def _restore_state_dtypes(self):
+        """torch's ``load_state_dict`` casts every floating-point or integer state tensor of a floating-point parameter to the
+        parameter's dtype: fp16 moments and uint8 codes arrive as fp32 holding the same values, so the way back is lossless"""
+        for st in self.state.values():
+            for k, dtype in self.STATE_DTYPES.items():
+                if k in st and st[k].dtype != dtype:
+                    st[k] = st[k].to(dtype)
 
     def _ws(self, device):
         w = self._norm_ws.get(device)
@@ -85,9 +102,7 @@ class FlatFusedOptimizer(torch.optim.Optimizer):
                     self._init_state(p, st)
                 if "step" in st:
                     st["step"] += 1
-                shadow = getattr(p, "_uwu_bf16_shadow", None)
-                if shadow is not None and shadow.numel() != p.numel():
-                    shadow = None
+                shadow = _shadow_of(p)
                 clip_ptr = L.ptr(clip) if clip is not None else None
                 for i, (off, ln) in enumerate(chunks or [(0, p.numel())]):
                     if before_chunk is not None:
@@ -167,6 +182,7 @@ class FusedAdamWFP16(FlatFusedOptimizer):
     floats (a tensor in optimizer state would be cast to the parameter's dtype and device by ``load_state_dict``)."""
 
     decay_threshold = 1e-2
+    STATE_DTYPES = {"exp_avg": torch.float16, "exp_avg_sq": torch.float16}
 
     def __init__(self, params, *, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, differentiable=False,
                  segments=None):
@@ -185,15 +201,6 @@ class FusedAdamWFP16(FlatFusedOptimizer):
         self.segments = [(int(o), int(n)) for o, n in segments] if segments is not None else None
         if self.segments is not None and sum(len(g["params"]) for g in self.param_groups) != 1:
             raise ValueError("segments describe one flat parameter buffer")
-        self.register_load_state_dict_post_hook(FusedAdamWFP16._moments_to_fp16)
-
-    def _moments_to_fp16(self):
-        """torch's ``load_state_dict`` casts floating-point state to the parameter's dtype: the restored fp16 moments arrive as
-        fp32 holding fp16 values, so the way back is lossless"""
-        for st in self.state.values():
-            for k in ("exp_avg", "exp_avg_sq"):
-                if k in st and st[k].dtype != torch.float16:
-                    st[k] = st[k].to(torch.float16)
 
     def _segments_of(self, p):
         segs = self.segments if self.segments is not None else [(0, p.numel())]
@@ -318,8 +325,8 @@ class FusedProdigy(FlatFusedOptimizer):
         self._slots = 0  # (a step that raised between its launches leaves no slots behind)
         for group in self.param_groups:  # the entry points take raw pointers: the shadow's dtype is checked here, before any launch
             for p in group["params"]:
-                shadow = getattr(p, "_uwu_bf16_shadow", None)
-                if shadow is not None and shadow.numel() == p.numel() and shadow.dtype != torch.bfloat16:
+                shadow = _shadow_of(p)
+                if shadow is not None and shadow.dtype != torch.bfloat16:
                     raise L.UwuError(f"uwu_prodigy_apply: the shadow must be bfloat16, got {shadow.dtype}")
         return super().step(*args, **kwargs)
 
@@ -420,6 +427,7 @@ class _Flat8bit(FlatFusedOptimizer):
     launches over whole blocks whatever the chunking, and the way back to uint8 after ``load_state_dict``."""
 
     MOMENTS = ()  # ((key suffix, signed table), ...)
+    STATE_DTYPES = {"state1": torch.uint8, "state2": torch.uint8}
 
     def __init__(self, params, defaults, name, percentile_clipping=100, block_wise=True, is_paged=False):
         if percentile_clipping != 100:
@@ -430,15 +438,6 @@ class _Flat8bit(FlatFusedOptimizer):
             raise NotImplementedError(f"{name}: is_paged=True is not implemented")
         super().__init__(params, defaults)
         self._sched = {}
-        self.register_load_state_dict_post_hook(_Flat8bit._codes_to_uint8)
-
-    def _codes_to_uint8(self):
-        """torch's ``load_state_dict`` casts every state tensor of a floating-point parameter to the parameter's dtype: the
-        restored codes arrive as fp32 holding 0..255, so the way back is lossless"""
-        for st in self.state.values():
-            for k in ("state1", "state2"):
-                if k in st and st[k].dtype != torch.uint8:
-                    st[k] = st[k].to(torch.uint8)
 
     def _init_state(self, p, st):
         blocks = -(-p.numel() // QBLOCK)
@@ -652,10 +651,7 @@ class FusedAdamWScheduleFree(FlatFusedOptimizer):
         if avg is not None:
             avg.swap()
             return
-        shadow = getattr(p, "_uwu_bf16_shadow", None)
-        if shadow is not None and shadow.numel() != p.numel():
-            shadow = None
-        L.call("uwu_ema_swap", L.ptr(self._spare[p]), L.ptr(p.data), L.ptr(shadow), p.numel(), 0, L.stream())
+        L.call("uwu_ema_swap", L.ptr(self._spare[p]), L.ptr(p.data), L.ptr(_shadow_of(p)), p.numel(), 0, L.stream())
 
     @torch.no_grad()
     def write_average(self, p):
