@@ -524,7 +524,8 @@ int uwu_gemm(const void* A, const void* B, void* C, void* C2, const float* bias,
              int c_dtype, int epilogue, int split_k, void* stream);
 /* Name of the kernel family that the most recent GEMM launch of this process went to ("" before the first): "gemm" (128x128),
  * "gemm_r3_256" / "gemm_r3_128" (ring, 256x128 / 128x128 tiles), "gemm_big" (256x256), "gemm_wide" (192x384), "gemm_m64"
- * (64x128), "gemm_as" (A-stationary), "gemm_p8" / "gemm_p8n" (8-phase 256x256 / 128x384), and the fp8 / weight-gradient
+ * (64x128), "gemm_as" (A-stationary), "gemm_p8" / "gemm_p8n" (8-phase 256x256 / 128x384), the fp8 kernels "gemm_f8" /
+ * "gemm_f8(emit)" / "gemm_f8(split-K)" (two-stage) and "gemm_p8f" / "gemm_p8f(split-K)" (8-phase), and the weight-gradient
  * families' own names.  A static string; for tests that must know which kernel a dispatch rule chose. */
 const char* uwu_gemm_last_kernel(void);
 
@@ -550,6 +551,7 @@ int uwu_gemm_fp8(const void* A, const void* B, void* C, void* C2, const float* b
  *   UWU_EPI_DGELU:     v = (A.B^T) * gelu'(aux); C must be NULL (no bf16 copy); colsum[N] += column sums of v if non-NULL;
  *                      q8 / q8t = e5m2(v * q_scale[0])
  * q_amax (optional) receives max |value| by atomic max (the next step's scale).  Either of q8 / q8t may be NULL.
+ * Values saturate to the format's +-max and a NaN stays a NaN byte (see uwu_fp8_quantize for the non-finite contract).
  * M, N multiples of 16; ldq >= N, ldqt >= M, multiples of 16.  Reference: the MLP of the transformer block,
  * rope_unet.py:399-411 (nn.Linear -> GELU(tanh) -> nn.Linear under autocast); the fp8 path is this build's (config 5). */
 int uwu_gemm_fp8_emit(const void* A, const void* B, void* C, float* colsum, const float* bias, const void* aux, int M, int N,
@@ -586,7 +588,20 @@ int uwu_conv3x3_wgrad(const void* dy, const void* x, float* dw, float* db, int B
  * (otherwise the previous scale, or 1), then amax[i] = 0 -- the "delayed scaling" step between two training steps, or
  * the second half of just-in-time scaling.  quantize: one pass over x [M,K] (bf16 / fp32, row-major, ldx) writing any
  * of out [M,K] (ldo), out_t [K,M] (ldt; the operand layout of a contraction over M), colsum[K] += column sums of x
- * (fp32 atomics; a bias gradient), amax.  Values are saturated to the format's largest finite number. */
+ * (fp32 atomics; a bias gradient), amax.  Values are saturated to the format's largest finite number.
+ * Non-finite input (the contract of the whole fp8 chain; tests/test_fp8_chain_gpu.py):
+ *   quantize       x * scale is rounded to nearest even; +-inf and everything past +-max give the code of +-max; a NaN gives
+ *                  a byte that decodes to NaN (which of the NaN codes is not specified), in out and out_t alike.  The column
+ *                  sum of a column that holds a NaN is NaN.
+ *   amax           (uwu_fp8_amax and the amax of quantize / the emitting kernels) an Inf element makes it +inf; a NaN
+ *                  element is NOT recorded -- the bytes keep a NaN visible, amax does not.
+ *   update_scales  stores q = FMT_MAX / (amax * margin), formed in fp32, only where amax > 0 and q is finite and positive
+ *                  (q overflows for amax below ~1.3e-36 e4m3 / 1.7e-34 e5m2 and is 0 where amax * margin overflows; a NaN or
+ *                  Inf amax never qualifies); otherwise the previous scale stays if it is finite and positive, else 1.
+ *                  amax is reset in every case, and a stored scale is always finite and positive.
+ *   emitters       uwu_gemm_fp8_emit and uwu_add_ln_modulate_fwd_q8 saturate and keep NaN exactly as quantize does: a NaN
+ *                  code in an operand row makes that row of q8 (that column of q8t) and of C decode to NaN; a NaN in a
+ *                  LayerNorm input row makes its mean, rstd and every byte of the row NaN; other rows are unaffected. */
 int uwu_fp8_amax(const void* x, int dtype, int64_t n, float* amax, void* stream);
 int uwu_fp8_update_scales(float* amax, float* scale, const int* fmt, int n, float margin, void* stream);
 int uwu_fp8_quantize(const void* x, int dtype, int M, int K, int ldx, const float* scale, int fmt, void* out, int ldo,
@@ -672,7 +687,8 @@ int uwu_add_ln_modulate_fwd(const void* x_in, const void* y, const float* gate, 
                             int B, int T, int D, float eps, int affine, int dtype, void* stream);
 /* fp8 mode, delayed scaling: the same LayerNorm whose output leaves ONLY as the e4m3 operand of the next GEMMs -- q8 [B*T, D]
  * (contraction over D) and q8t [D, B*T] (the weight gradient's contraction over the tokens) = sat(h * q_scale[0]); q_amax
- * (optional) receives max |h|.  bf16 tensors, per-sample shift / scale required, B*T a multiple of 64, D <= 1536. */
+ * (optional) receives max |h|.  sat keeps NaN (uwu_fp8_quantize's contract): a NaN in a row makes all its bytes NaN.
+ * bf16 tensors, per-sample shift / scale required, B*T a multiple of 64, D <= 1536. */
 int uwu_add_ln_modulate_fwd_q8(const void* x_in, const void* y, const float* gate, const float* shift, const float* scale,
                                int mod_ld, void* x_out, void* q8, int ldq, void* q8t, int ldqt, const float* q_scale,
                                float* q_amax, float* mean, float* rstd, int B, int T, int D, float eps, void* stream);

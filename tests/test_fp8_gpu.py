@@ -43,7 +43,14 @@ def test_quantize_matches_torch_float8(fmt, dtype, M, K):
         _, out_t = ops.fp8_quantize(xd, scale, fmt, rowmajor=False, transposed=True)
         assert torch.equal(out_t.cpu(), want.view(torch.uint8).t().contiguous())
     assert float(amax) == float(x.float().abs().max())
-    torch.testing.assert_close(cs.cpu(), x.float().sum(0), rtol=1e-4, atol=1e-2 * 1e6 * 1e-4)
+    # per column, the worst case of its fp32 adds: a value passes 3 adds in its thread (4 rows), 3 shuffle adds (8 row groups),
+    # 3 across the waves and one atomic per 128-row tile, each rounding by at most half an ulp of a partial sum that never
+    # exceeds the column's absolute sum S: (9 + tiles) * 2^-24 * S, in whatever order the atomics land.  The two 1e6 outliers
+    # loosen their own columns only (0.6 .. 1.0) -- every other column is held to ~1e-3 where one bar of 1 stood.
+    ref_cs = x.double().sum(0)
+    bar = (9 + (M + 127) // 128) * 2.0 ** -24 * x.double().abs().sum(0)
+    err = (cs.cpu().double() - ref_cs).abs()
+    assert bool((err <= bar).all()), float((err / bar).max())
     a2 = ops.fp8_amax(xd)
     assert float(a2) == float(x.float().abs().max())
 

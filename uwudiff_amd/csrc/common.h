@@ -68,6 +68,15 @@ __device__ __forceinline__ float from_f32<float>(float v) { return v; }
 template <>
 __device__ __forceinline__ bf16_t from_f32<bf16_t>(float v) { return (bf16_t)v; }  // RNE, NaN-safe (v_cvt_pk_bf16_f32)
 
+// Saturation in front of the fp8 converts (quant.hip, gemm_f8.hip, norm.hip): clamp to +-mx, NaN passes through.
+// fminf(fmaxf(x, -mx), mx) alone returns -mx for a NaN (fmaxf drops it), which turned a diverged activation into the finite
+// code of -448 / -57344; the hardware convert gives the NaN code for a NaN input, as torch's cast does.
+// IEEE 754-2019 maximum / minimum propagate NaN and are one instruction each on gfx950 (v_maximum3_f32 / v_minimum3_f32): two
+// VALU operations per element where the old clamp folded into one v_med3_f32 (which returns min3 for a NaN).
+__device__ __forceinline__ float f8_sat(float x, float mx) {
+  return __builtin_elementwise_minimum(__builtin_elementwise_maximum(x, -mx), mx);
+}
+
 // ---- wave / block reductions ------------------------------------------------------------
 // Whole-wave reductions as six DPP steps + one v_readlane (result uniform in every lane).  __shfl_xor compiles to
 // ds_bpermute_b32 -- a trip through the LDS crossbar and an lgkmcnt wait per step; the LayerNorm kernels ran two such

@@ -36,8 +36,8 @@ constexpr int F8_EMIT_LDS = 2 * 256 * F8Q_PITCH + 2 * 256 * 4 + 64;
 template <int FMT>
 __device__ __forceinline__ unsigned f8_pack4(const f32x4& v, float s) {
   const float mx = FMT == 0 ? 448.f : 57344.f;
-  float a = fminf(fmaxf(v[0] * s, -mx), mx), b = fminf(fmaxf(v[1] * s, -mx), mx);
-  float c = fminf(fmaxf(v[2] * s, -mx), mx), d = fminf(fmaxf(v[3] * s, -mx), mx);
+  float a = f8_sat(v[0] * s, mx), b = f8_sat(v[1] * s, mx);
+  float c = f8_sat(v[2] * s, mx), d = f8_sat(v[3] * s, mx);
   int r;
   if constexpr (FMT == 0) {
     r = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, 0, false);
@@ -319,6 +319,7 @@ int launch_f8_part(GemmArgs g, const float* sa, const float* sb, void* scratch, 
   constexpr auto kern = gemm_f8_kernel<float, UWU_EPI_NONE, FA, true>;
   constexpr int LDS = 2 * 4 * TILE_BYTES;
   RETURN_IF(gemm_lds_optin<kern>("gemm_f8(split-K)", LDS));
+  g_uwu_gemm_last_kernel.store("gemm_f8(split-K)", std::memory_order_relaxed);
   g.tiles_m = (g.M + 255) / 256;
   g.tiles_n = (g.N + 255) / 256;
   const int tiles = g.tiles_m * g.tiles_n, steps = g.K / 128;

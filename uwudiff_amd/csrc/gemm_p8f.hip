@@ -374,6 +374,7 @@ template <typename TC, int EPI, int FA, bool PART>
 int launch_p8f(GemmArgs g, const float* sa, const float* sb, hipStream_t st) {
   constexpr auto kern = gemm_p8f_kernel<TC, EPI, FA, PART>;
   RETURN_IF(gemm_lds_optin<kern>("gemm_p8f", P8_LDS));  // (the profiler scope is the caller's: uwu_gemm_fp8, gemm_f8.hip)
+  g_uwu_gemm_last_kernel.store(PART ? "gemm_p8f(split-K)" : "gemm_p8f", std::memory_order_relaxed);
   const int units = g.tiles_m * g.tiles_n * (PART ? g.wide : 1), ncu = uwu_p8_cus();
   hipLaunchKernelGGL(kern, dim3(units < ncu ? units : ncu), dim3(512), P8_LDS, st, g, sa, sb);
   UWU_LAUNCH_CHECK("gemm_p8f");

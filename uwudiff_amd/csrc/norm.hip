@@ -204,10 +204,10 @@ __global__ void __launch_bounds__(256) add_ln_mod_fwd16_kernel(const T* __restri
 // that copy -- 16 dwords, consecutive lanes consecutive dwords -- transposes the four 4 x 4 byte blocks with v_perm_b32 and
 // stores 16 contiguous bytes of each of its 4 columns of the transposed image (64-byte runs along the tokens per tile).
 __device__ __forceinline__ unsigned q8_pack4(float a, float b, float c, float d, float s) {
-  a = fminf(fmaxf(a * s, -448.f), 448.f);
-  b = fminf(fmaxf(b * s, -448.f), 448.f);
-  c = fminf(fmaxf(c * s, -448.f), 448.f);
-  d = fminf(fmaxf(d * s, -448.f), 448.f);
+  a = f8_sat(a * s, 448.f);
+  b = f8_sat(b * s, 448.f);
+  c = f8_sat(c * s, 448.f);
+  d = f8_sat(d * s, 448.f);
   int r = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, 0, false);
   return (unsigned)__builtin_amdgcn_cvt_pk_fp8_f32(c, d, r, true);
 }

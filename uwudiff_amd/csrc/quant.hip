@@ -22,8 +22,8 @@ constexpr float F8_MAX[2] = {448.f, 57344.f};  // OCP e4m3fn / e5m2
 template <int FMT>
 __device__ __forceinline__ unsigned cvt2(float a, float b) {  // two fp8 bytes in the low 16 bits
   const float mx = FMT == 0 ? 448.f : 57344.f;
-  a = fminf(fmaxf(a, -mx), mx);
-  b = fminf(fmaxf(b, -mx), mx);
+  a = f8_sat(a, mx);
+  b = f8_sat(b, mx);
   if constexpr (FMT == 0) return (unsigned)__builtin_amdgcn_cvt_pk_fp8_f32(a, b, 0, false) & 0xFFFFu;
   else return (unsigned)__builtin_amdgcn_cvt_pk_bf8_f32(a, b, 0, false) & 0xFFFFu;
 }
@@ -70,9 +70,12 @@ __global__ void update_scales_kernel(float* __restrict__ amax, float* __restrict
                                      int n, float margin) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const float a = amax[i];
-  if (a > 0.f && isfinite(a)) scale[i] = F8_MAX[fmt[i] & 1] / (a * margin);
-  else if (!(scale[i] > 0.f)) scale[i] = 1.f;  // nothing seen yet: keep a previous scale, else 1
+  // The quotient is stored only where it is finite and positive: it overflows to inf for an amax below ~1.3e-36 (e4m3) /
+  // 1.7e-34 (e5m2) and is 0 where amax * margin overflows, and 0 * inf = NaN would then reach every byte of the tensor.
+  // A NaN amax fails both compares.  A stored scale is always finite and positive.
+  const float a = amax[i], q = F8_MAX[fmt[i] & 1] / (a * margin), prev = scale[i];
+  if (a > 0.f && q > 0.f && isfinite(q)) scale[i] = q;
+  else if (!(prev > 0.f && isfinite(prev))) scale[i] = 1.f;  // nothing usable seen: keep a previous scale, else 1
   amax[i] = 0.f;
 }
 
