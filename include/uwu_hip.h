@@ -41,6 +41,12 @@ extern "C" {
 #define UWU_PT_SAMPLE 2
 #define UWU_PT_RF 3
 
+/* element losses of the fused objective (the reference's `loss` argument, src/duwu/loss/diffusion.py:27): uwu_loss_elem_fwd_bwd */
+#define UWU_LOSS_MSE 0
+#define UWU_LOSS_L1 1
+#define UWU_LOSS_HUBER 2     /* loss_param = delta > 0 */
+#define UWU_LOSS_SMOOTH_L1 3 /* loss_param = beta > 0 (beta = 0 is UWU_LOSS_L1) */
+
 /* GEMM epilogues */
 #define UWU_EPI_NONE 0
 #define UWU_EPI_BIAS 1       /* C = A.B + bias[n]                                        */
@@ -124,6 +130,19 @@ int uwu_loss_fwd_bwd(const float* x, const float* noise, const float* xt, const 
                      int out_dtype, const float* coef, int pred_type, int target_type, int force_convert,
                      int B, int64_t n, float* losses, float* loss_mean, void* grad_out, float* pred,
                      float* target, void* stream);
+/* The same with the element loss chosen: losses[b] = w_b * mean_i rho(d_bi), grad_out = w_b c_b rho'(d) / (n B), d = pred - target,
+ * c_b = d pred / d model_output.  loss_kind is a UWU_LOSS_*; loss_param is Huber's delta / SmoothL1's beta (FLT_MIN <= loss_param <= FLT_MAX:
+ * positive, normal and finite; ignored by MSE and L1):
+ *   MSE       rho = d^2                                              rho' = 2 d
+ *   L1        rho = |d|                                              rho' = sign(d), 0 at d == 0
+ *   HUBER     rho = |d| < delta ? d^2 / 2 : delta (|d| - delta / 2)  rho' = |d| < delta ? d : delta sign(d)
+ *   SMOOTH_L1 rho = |d| < beta ? d^2 / (2 beta) : |d| - beta / 2     rho' = |d| < beta ? d / beta : sign(d)
+ * A NaN in d is a NaN in that element of grad_out and in losses[b] for every kind (torch's L1Loss gives gradient 0 there);
+ * d = +-inf gives rho = inf and rho' = +-delta / +-1.  uwu_loss_fwd_bwd is this entry with UWU_LOSS_MSE. */
+int uwu_loss_elem_fwd_bwd(const float* x, const float* noise, const float* xt, const void* model_output,
+                          int out_dtype, const float* coef, int pred_type, int target_type, int force_convert,
+                          int loss_kind, float loss_param, int B, int64_t n, float* losses, float* loss_mean,
+                          void* grad_out, float* pred, float* target, void* stream);
 
 /* y[i] *= *scale (device scalar); used when autograd hands a non-unit upstream gradient. */
 int uwu_scale_inplace(void* y, int dtype, int64_t n, const float* scale, void* stream);

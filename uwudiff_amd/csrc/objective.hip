@@ -1,6 +1,8 @@
 // Objective kernels: schedule gather, RF time sampling, q-sample, fused loss fwd+bwd.
 // HBM-bound elementwise + wavefront-shuffle reductions.  Reference: src/duwu/loss/diffusion.py,
 // src/duwu/loss/rectified_flow.py (line cites at each kernel).
+#include <cfloat>
+
 #include "common.h"
 
 // ---------------------------------------------------------------------------------------
@@ -293,21 +295,36 @@ __device__ __forceinline__ float pred_coeff(int ptype, int ttype, bool convert, 
   }
 }
 
-// One workgroup per sample: pass over the sample computes pred/target, the squared-error sum
+// One workgroup per sample: pass over the sample computes pred/target, the element-loss sum
 // (wave shuffle + LDS reduce) and writes d loss / d out in the same pass -- the gradient only
 // needs per-sample scalars known up front (w_b, c_b, 1/(n*B)).  diffusion.py:177-193.
-template <typename TO, int NT>
+//
+// The element loss rho (the reference's `loss` constructor argument, diffusion.py:27 / :186) is the compile-time LOSS, one
+// instantiation per kind, chosen on the host like the dtype; `lp` is Huber's delta / SmoothL1's beta.  With d = pred - target:
+//   MSE       rho = d d                                            rho' = 2 d
+//   L1        rho = |d|                                            rho' = sign(d)
+//   Huber     rho = |d| < delta ? d d / 2 : delta (|d| - delta/2)  rho' = |d| < delta ? d : delta sign(d)
+//   SmoothL1  rho = |d| < beta ? d d / (2 beta) : |d| - beta/2     rho' = |d| < beta ? d / beta : sign(d)
+// (the comparisons are torch's); losses[b] = w_b mean_i rho(d_bi), grad = w_b c_b rho'(d) / (n B).  sign(d) is +-1, 0 at d == 0,
+// and NaN at a NaN: a NaN in d is a NaN in that element's gradient and in that sample's loss for every kind.  torch's L1Loss and
+// SmoothL1Loss(beta=0) return gradient 0 there, which hides it; this kernel does not follow them.
+// d = +-inf gives rho = inf and rho' = +-delta (Huber) or +-1, as torch does.  The MSE instantiation is the expression the kernel
+// has always had (gs = 2 w c / (n B), acc += d d, gv = gs d), so its bits do not move.
+__device__ __forceinline__ float sign_nan(float d) { return d > 0.f ? 1.f : (d < 0.f ? -1.f : d); }
+
+template <typename TO, int NT, int LOSS>
 __global__ void __launch_bounds__(NT) loss_fwd_bwd_kernel(
     const float* __restrict__ x, const float* __restrict__ noise, const float* __restrict__ xt,
     const TO* __restrict__ mo, const float* __restrict__ coef, int ptype, int ttype, int convert, int B,
-    int64_t n, float* __restrict__ losses, TO* __restrict__ grad, float* __restrict__ pred_o,
+    int64_t n, float lp, float* __restrict__ losses, TO* __restrict__ grad, float* __restrict__ pred_o,
     float* __restrict__ target_o) {
   __shared__ float red[NT / 64];
   const int b = blockIdx.x;
   const float sigma = coef[4 * b], w = coef[4 * b + 1], sa = coef[4 * b + 2], sb = coef[4 * b + 3];
   const float scales = 1.f / sqrtf(sigma * sigma + 1.f);
   const float c = pred_coeff(ptype, ttype, convert != 0, sigma, scales, sa, sb);
-  const float gs = 2.f * w * c / ((float)n * (float)B);
+  const float gs = (LOSS == UWU_LOSS_MSE ? 2.f * w * c : w * c) / ((float)n * (float)B);
+  const float inv_lp = LOSS == UWU_LOSS_SMOOTH_L1 ? 1.f / lp : 1.f, half_lp = 0.5f * lp;
   const int64_t base = (int64_t)b * n;
   float acc = 0.f;
   for (int64_t i = (int64_t)threadIdx.x * 4; i < n; i += (int64_t)NT * 4) {
@@ -326,10 +343,27 @@ __global__ void __launch_bounds__(NT) loss_fwd_bwd_kernel(
       }
       float t = target_of(ttype, xv[j], nv[j], sa, sb);
       float d = p - t;
-      acc += d * d;
+      if constexpr (LOSS == UWU_LOSS_MSE) {
+        acc += d * d;
+        gv[j] = gs * d;
+      } else if constexpr (LOSS == UWU_LOSS_L1) {
+        acc += fabsf(d);
+        gv[j] = gs * sign_nan(d);
+      } else {  // both branches are evaluated and one selected: no divergent branch in the element loop
+        const float a = fabsf(d), sg = sign_nan(d), h = 0.5f * d * d;
+        const bool quad = a < lp;
+        if constexpr (LOSS == UWU_LOSS_HUBER) {
+          const float lin = lp * (a - half_lp), glin = lp * sg;
+          acc += quad ? h : lin;
+          gv[j] = gs * (quad ? d : glin);
+        } else {
+          const float q = h * inv_lp, lin = a - half_lp, gq = d * inv_lp;
+          acc += quad ? q : lin;
+          gv[j] = gs * (quad ? gq : sg);
+        }
+      }
       pv[j] = p;
       tv[j] = t;
-      gv[j] = gs * d;
     }
     store4(grad + base + i, gv);
     if (pred_o) store4(pred_o + base + i, pv);
@@ -512,34 +546,68 @@ extern "C" int uwu_ctx_place(const void* src, int dtype, const int64_t* mask, fl
   return UWU_OK;
 }
 
-extern "C" int uwu_loss_fwd_bwd(const float* x, const float* noise, const float* xt, const void* model_output,
-                                int out_dtype, const float* coef, int pred_type, int target_type, int force_convert,
-                                int B, int64_t n, float* losses, float* loss_mean, void* grad_out, float* pred,
-                                float* target, void* stream) {
+template <int LOSS>
+static void launch_loss(int out_dtype, const float* x, const float* noise, const float* xt, const void* model_output, const float* coef,
+                        int pred_type, int target_type, int convert, int B, int64_t n, float lp, float* losses, void* grad_out,
+                        float* pred, float* target, hipStream_t st) {
+  constexpr int NT = 256;
+  if (out_dtype == UWU_F32)
+    hipLaunchKernelGGL((loss_fwd_bwd_kernel<float, NT, LOSS>), dim3(B), dim3(NT), 0, st, x, noise, xt, (const float*)model_output,
+                       coef, pred_type, target_type, convert, B, n, lp, losses, (float*)grad_out, pred, target);
+  else
+    hipLaunchKernelGGL((loss_fwd_bwd_kernel<bf16_t, NT, LOSS>), dim3(B), dim3(NT), 0, st, x, noise, xt, (const bf16_t*)model_output,
+                       coef, pred_type, target_type, convert, B, n, lp, losses, (bf16_t*)grad_out, pred, target);
+}
+
+extern "C" int uwu_loss_elem_fwd_bwd(const float* x, const float* noise, const float* xt, const void* model_output,
+                                     int out_dtype, const float* coef, int pred_type, int target_type, int force_convert,
+                                     int loss_kind, float loss_param, int B, int64_t n, float* losses, float* loss_mean,
+                                     void* grad_out, float* pred, float* target, void* stream) {
   UWU_CHECK_ARG(x && noise && model_output && coef && losses && grad_out, "loss_fwd_bwd: null pointer");
   UWU_CHECK_ARG(B > 0 && n > 0 && n % 4 == 0, "loss_fwd_bwd: n=%lld must be a positive multiple of 4", (long long)n);
   UWU_CHECK_ARG(pred_type >= 0 && pred_type <= 3 && target_type >= 0 && target_type <= 3,
                 "loss_fwd_bwd: Unsupported prediction/target type %d/%d", pred_type, target_type);
   int convert = (force_convert || pred_type != target_type) ? 1 : 0;
   UWU_CHECK_ARG(!convert || xt, "loss_fwd_bwd: xt required when prediction_type != target_type");
-  constexpr int NT = 256;
-  if (out_dtype == UWU_F32) {
-    hipLaunchKernelGGL((loss_fwd_bwd_kernel<float, NT>), dim3(B), dim3(NT), 0, (hipStream_t)stream, x, noise, xt,
-                       (const float*)model_output, coef, pred_type, target_type, convert, B, n, losses,
-                       (float*)grad_out, pred, target);
-  } else if (out_dtype == UWU_BF16) {
-    hipLaunchKernelGGL((loss_fwd_bwd_kernel<bf16_t, NT>), dim3(B), dim3(NT), 0, (hipStream_t)stream, x, noise, xt,
-                       (const bf16_t*)model_output, coef, pred_type, target_type, convert, B, n, losses,
-                       (bf16_t*)grad_out, pred, target);
-  } else {
-    UWU_CHECK_ARG(false, "loss_fwd_bwd: bad dtype %d", out_dtype);
+  UWU_CHECK_ARG(out_dtype == UWU_F32 || out_dtype == UWU_BF16, "loss_fwd_bwd: bad dtype %d", out_dtype);
+  UWU_CHECK_ARG(loss_kind >= UWU_LOSS_MSE && loss_kind <= UWU_LOSS_SMOOTH_L1, "loss_fwd_bwd: unknown element loss %d", loss_kind);
+  const bool has_param = loss_kind == UWU_LOSS_HUBER || loss_kind == UWU_LOSS_SMOOTH_L1;
+  // (a NaN fails `>=`; an infinite threshold is no threshold; below FLT_MIN SmoothL1's 1 / beta is inf, and 0 * inf a NaN at d == 0)
+  UWU_CHECK_ARG(!has_param || (loss_param >= FLT_MIN && loss_param <= FLT_MAX),
+                "loss_fwd_bwd: element loss %d needs a positive, normal, finite delta / beta, got %g", loss_kind, (double)loss_param);
+  hipStream_t st = (hipStream_t)stream;
+  switch (loss_kind) {
+    case UWU_LOSS_MSE:
+      launch_loss<UWU_LOSS_MSE>(out_dtype, x, noise, xt, model_output, coef, pred_type, target_type, convert, B, n, 0.f, losses,
+                                grad_out, pred, target, st);
+      break;
+    case UWU_LOSS_L1:
+      launch_loss<UWU_LOSS_L1>(out_dtype, x, noise, xt, model_output, coef, pred_type, target_type, convert, B, n, 0.f, losses,
+                               grad_out, pred, target, st);
+      break;
+    case UWU_LOSS_HUBER:
+      launch_loss<UWU_LOSS_HUBER>(out_dtype, x, noise, xt, model_output, coef, pred_type, target_type, convert, B, n, loss_param,
+                                  losses, grad_out, pred, target, st);
+      break;
+    default:
+      launch_loss<UWU_LOSS_SMOOTH_L1>(out_dtype, x, noise, xt, model_output, coef, pred_type, target_type, convert, B, n,
+                                      loss_param, losses, grad_out, pred, target, st);
+      break;
   }
   UWU_LAUNCH_CHECK("loss_fwd_bwd");
   if (loss_mean) {
-    hipLaunchKernelGGL(mean_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, losses, B, loss_mean);
+    hipLaunchKernelGGL(mean_kernel, dim3(1), dim3(256), 0, st, losses, B, loss_mean);
     UWU_LAUNCH_CHECK("loss_mean");
   }
   return UWU_OK;
+}
+
+extern "C" int uwu_loss_fwd_bwd(const float* x, const float* noise, const float* xt, const void* model_output,
+                                int out_dtype, const float* coef, int pred_type, int target_type, int force_convert,
+                                int B, int64_t n, float* losses, float* loss_mean, void* grad_out, float* pred,
+                                float* target, void* stream) {
+  return uwu_loss_elem_fwd_bwd(x, noise, xt, model_output, out_dtype, coef, pred_type, target_type, force_convert, UWU_LOSS_MSE,
+                               0.f, B, n, losses, loss_mean, grad_out, pred, target, stream);
 }
 
 template <typename T>

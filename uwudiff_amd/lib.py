@@ -14,6 +14,7 @@ LIB_PATH = os.path.join(_HERE, "libuwu_hip.so")
 
 F32, BF16, I64 = 0, 1, 2
 PT = {"epsilon": 0, "v_prediction": 1, "sample": 2, "rectified_flow": 3}
+LOSS_MSE, LOSS_L1, LOSS_HUBER, LOSS_SMOOTH_L1 = 0, 1, 2, 3  # UWU_LOSS_*
 EPI_NONE, EPI_BIAS, EPI_BIAS_GELU, EPI_DGELU, EPI_BIAS_SILU, EPI_ACCUM = 0, 1, 2, 3, 4, 5
 ACT = {"quick_gelu": 0, "gelu": 1}  # UWU_ACT_QUICK_GELU, UWU_ACT_GELU_ERF
 GATE = {"gated-gelu": 0}  # UWU_GATE_GELU_TANH
@@ -59,6 +60,7 @@ _SIGS = {
     "uwu_qsample_norm": (c_int, [P, P, P, c_int, c_int64, c_float, c_float, P, P, P]),
     "uwu_ctx_place": (c_int, [P, c_int, P, P] + [c_int] * 7 + [P]),
     "uwu_loss_fwd_bwd": (c_int, [P, P, P, P, c_int, P, c_int, c_int, c_int, c_int, c_int64, P, P, P, P, P, P]),
+    "uwu_loss_elem_fwd_bwd": (c_int, [P, P, P, P, c_int, P, c_int, c_int, c_int, c_int, c_float, c_int, c_int64, P, P, P, P, P, P]),
     "uwu_scale_inplace": (c_int, [P, c_int, c_int64, P, P]),
     "uwu_scale_into": (c_int, [P, P, c_int, c_int64, P, P]),
     "uwu_cast_i64_to_f32": (c_int, [P, P, c_int64, P]),

@@ -8,8 +8,11 @@ Mirrors the reference operator interface (same names, arguments and error behavi
 
 What changed underneath: the B host syncs per step of ``get_sigmas_for_timesteps`` (diffusion.py:58) and the
 Python ``torch.stack`` loops (:146,:159) are one ``uwu_schedule_gather`` launch; q-sample is one fused kernel;
-prediction conversion + target + per-sample MSE + SNR weights + d loss/d model_output are one fused kernel.
+prediction conversion + target + per-sample element loss + SNR weights + d loss/d model_output are one fused kernel.
+The element loss is the reference's ``loss`` constructor argument (diffusion.py:27): ``nn.MSELoss`` (the default), ``nn.L1Loss``,
+``nn.HuberLoss`` or ``nn.SmoothL1Loss``, each with ``reduction="none"``, each one instantiation of that kernel.
 """
+import ctypes
 from typing import Any, NamedTuple, Optional
 
 import torch
@@ -34,11 +37,45 @@ class DiffusionLossAuxOutput(NamedTuple):
     noisy_latent: torch.Tensor
 
 
+def _fp32_threshold_ok(v):
+    """the kernel takes delta / beta as a float: the range check is on the value it will see (1e-50 rounds to 0, 1e39 to inf;
+    below the smallest normal number SmoothL1's 1 / beta overflows), so that the refusal comes at construction"""
+    f = ctypes.c_float(v).value
+    return 1.1754943508222875e-38 <= f < float("inf")  # FLT_MIN; a NaN fails both
+
+
+def element_loss_kind(loss):
+    """``(UWU_LOSS_* kind, parameter)`` of the reference's element-loss module (diffusion.py:27, applied at :186 as
+    ``self.loss(pred, target)`` before ``flatten(1).mean(1)``).  Refuses, by name, what the kernel has no instantiation for."""
+    if not isinstance(loss, (nn.MSELoss, nn.L1Loss, nn.HuberLoss, nn.SmoothL1Loss)):
+        what = type(loss).__name__ if isinstance(loss, nn.Module) else repr(loss)
+        raise NotImplementedError(f"element loss {what}: the HIP objective implements nn.MSELoss, nn.L1Loss, nn.HuberLoss and "
+                                  f"nn.SmoothL1Loss")
+    if loss.reduction != "none":
+        # with mean / sum the per-sample weights would scale one scalar and aux.losses would not be [B] (diffusion.py:186-191)
+        raise NotImplementedError(f"{type(loss).__name__}(reduction={loss.reduction!r}): only reduction='none' is implemented")
+    if isinstance(loss, nn.MSELoss):
+        return L.LOSS_MSE, 0.0
+    if isinstance(loss, nn.L1Loss):
+        return L.LOSS_L1, 0.0
+    if isinstance(loss, nn.HuberLoss):
+        delta = float(loss.delta)
+        if not _fp32_threshold_ok(delta):
+            raise ValueError(f"HuberLoss(delta={loss.delta!r}): delta must be positive and a normal, finite number in fp32")
+        return L.LOSS_HUBER, delta
+    beta = float(loss.beta)
+    if beta == 0.0:  # torch defines beta = 0 as L1Loss
+        return L.LOSS_L1, 0.0
+    if not _fp32_threshold_ok(beta):
+        raise ValueError(f"SmoothL1Loss(beta={loss.beta!r}): beta must be zero, or positive and a normal, finite number in fp32")
+    return L.LOSS_SMOOTH_L1, beta
+
+
 class _FusedLoss(torch.autograd.Function):
-    """loss = mean_b w_b * mean((pred-target)^2); the gradient wrt model_output is produced in the forward pass."""
+    """loss = mean_b w_b * mean(rho(pred-target)); the gradient wrt model_output is produced in the forward pass."""
 
     @staticmethod
-    def forward(ctx, model_output, x, noise, xt, coef, pred_type, target_type, force_convert):
+    def forward(ctx, model_output, x, noise, xt, coef, pred_type, target_type, force_convert, loss_kind, loss_param):
         B = x.shape[0]
         n = x[0].numel()
         mo = model_output.contiguous()
@@ -49,9 +86,9 @@ class _FusedLoss(torch.autograd.Function):
         grad = torch.empty_like(mo)
         pred = torch.empty_like(x)
         target = torch.empty_like(x)
-        L.call("uwu_loss_fwd_bwd", L.ptr(x), L.ptr(noise), L.ptr(xt), L.ptr(mo), L.dt(mo), L.ptr(coef),
-               pred_type, target_type, int(force_convert), B, n, L.ptr(losses), L.ptr(loss), L.ptr(grad),
-               L.ptr(pred), L.ptr(target), L.stream())
+        L.call("uwu_loss_elem_fwd_bwd", L.ptr(x), L.ptr(noise), L.ptr(xt), L.ptr(mo), L.dt(mo), L.ptr(coef),
+               pred_type, target_type, int(force_convert), loss_kind, loss_param, B, n, L.ptr(losses), L.ptr(loss),
+               L.ptr(grad), L.ptr(pred), L.ptr(target), L.stream())
         ctx.save_for_backward(grad)
         ctx.out_dtype = model_output.dtype
         ctx.mark_non_differentiable(losses, pred, target)
@@ -62,7 +99,7 @@ class _FusedLoss(torch.autograd.Function):
     def backward(ctx, g_loss, *_):
         (saved,) = ctx.saved_tensors
         if g_loss is None:  # (materialize_grads is off: nobody asked for d loss)
-            return (None,) * 8
+            return (None,) * 10
         g = g_loss.to(device=saved.device, dtype=torch.float32).contiguous()
         # scaled INTO a new tensor: a second backward through the same graph (retain_graph / accumulation helpers) must see the
         # unscaled gradient again, and the returned tensor must not alias the saved one
@@ -70,7 +107,7 @@ class _FusedLoss(torch.autograd.Function):
         L.call("uwu_scale_into", L.ptr(saved), L.ptr(grad), L.dt(grad), grad.numel(), L.ptr(g), L.stream())
         if grad.dtype != ctx.out_dtype:
             grad = grad.to(ctx.out_dtype)
-        return grad, None, None, None, None, None, None, None
+        return (grad,) + (None,) * 9
 
 
 class DiffusionLoss(nn.Module):
@@ -85,8 +122,8 @@ class DiffusionLoss(nn.Module):
         loss: Optional[nn.Module] = None,
     ):
         super().__init__()
-        if loss is not None and not (isinstance(loss, nn.MSELoss) and loss.reduction == "none"):
-            raise NotImplementedError("only nn.MSELoss(reduction='none') is implemented on the HIP path")
+        self.loss = nn.MSELoss(reduction="none") if loss is None else loss  # diffusion.py:27
+        self.loss_kind, self.loss_param = element_loss_kind(self.loss)
         self.scheduler = scheduler
         self.prepare_scheduler_for_custom_training()
         self.use_snr_weight = use_snr_weight
@@ -232,7 +269,8 @@ class DiffusionLoss(nn.Module):
             noise = noise.out
         model_output = unet(noisy, timesteps, **unet_kwargs)[0]
         # NB the reference hands the *clean* x to get_prediction_for_training as `xt` (diffusion.py:177)
-        loss, losses, pred, target = _FusedLoss.apply(model_output, x, noise, x, coef, pt, tt, False)
+        loss, losses, pred, target = _FusedLoss.apply(model_output, x, noise, x, coef, pt, tt, False,
+                                                      self.loss_kind, self.loss_param)
         aux = DiffusionLossAuxOutput(losses=losses, timesteps=timesteps, pred=pred, target=target,
                                      noisy_latent=noisy)
         return loss, aux
@@ -326,7 +364,7 @@ class RectifiedFlowLoss(DiffusionLoss):
         x, noises, timesteps, coef, noisy = self._forward_process(x)
         model_output = unet(noisy, timesteps, **unet_kwargs)[0]
         loss, losses, pred, target = _FusedLoss.apply(model_output, x, noises, noisy, coef, pt, L.PT["rectified_flow"],
-                                                      True)
+                                                      True, self.loss_kind, self.loss_param)
         aux = DiffusionLossAuxOutput(losses=losses, timesteps=timesteps, pred=pred, target=target,
                                      noisy_latent=noisy)
         return loss, aux
@@ -345,7 +383,7 @@ class NNWeightedRFLossAuxOutput(NamedTuple):
 
 class NNWeightedRFLoss(RectifiedFlowLoss):
     """reference src/duwu/loss/rectified_flow.py:144-203: a second network predicts the log of the per-sample RF loss;
-    ``losses = rf / exp(s_hat).clamp(1e-4) + (log rf - s_hat)^2``.
+    ``losses = rf / exp(s_hat).clamp(1e-4) + (log rf - s_hat)^2``, ``rf`` being the per-sample mean of the element loss.
 
     The denoiser-side term ``rf_b / pred_loss_b`` is the fused loss kernel with ``1/pred_loss_b`` in its per-sample
     weight slot (so the gradient wrt the model output comes out of the same single pass); the ``[B]``-sized
@@ -365,7 +403,8 @@ class NNWeightedRFLoss(RectifiedFlowLoss):
         coef_w = coef.clone()
         coef_w[:, 1] = 1.0 / pred_loss
         rescaled_mean, rescaled, pred, target = _FusedLoss.apply(model_output, x, noises, noisy, coef_w,
-                                                                 pt, L.PT["rectified_flow"], True)
+                                                                 pt, L.PT["rectified_flow"], True, self.loss_kind,
+                                                                 self.loss_param)
         rf_losses = rescaled * pred_loss
         ls_pred_loss = (rf_losses.log() - log_ls_pred).square()
         loss = rescaled_mean + ls_pred_loss.mean()
