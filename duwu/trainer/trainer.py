@@ -12,7 +12,7 @@ import torch.optim.lr_scheduler as lr_sch
 from duwu.loader import load_any
 from duwu.utils import instantiate_any
 from uwudiff_amd.engine import GradualWarmupScheduler
-from uwudiff_amd.optim import FusedAdamW, FusedAdamWFP16, flat_segments
+from uwudiff_amd.optim import FusedAdafactor, FusedAdamW, FusedAdamWFP16, flat_segments, flat_tensors
 
 
 class BaseTrainer(nn.Module):
@@ -49,6 +49,14 @@ class BaseTrainer(nn.Module):
             owner = lyc if lyc is not None else getattr(self, "unet", None)
             if owner is not None and (hasattr(owner, "offsets") or hasattr(owner, "P")):
                 opt_config["segments"] = flat_segments(owner)
+        if isinstance(opt_cls, type) and issubclass(opt_cls, FusedAdafactor):
+            # Adafactor's rule is per tensor: the tensors of the flat buffer that trains, with their shapes as stored
+            owner = lyc if lyc is not None else getattr(self, "unet", None)
+            if "tensors" not in opt_config and owner is not None and (hasattr(owner, "offsets") or hasattr(owner, "P")):
+                opt_config["tensors"] = flat_tensors(owner)
+            if self.lr is None and (self.lr_sch is not None or self.use_warm_up):
+                raise ValueError("Adafactor with relative_step computes its own step size (lr: null): set lr_scheduler: null and "
+                                 "use_warm_up: false (AdafactorSchedule is not built)")
         optimizer = opt_cls(params, lr=self.lr, **opt_config)
         if lyc is not None:  # every step changes the adapters: the UNet merges them again before its next forward
             optimizer.register_step_post_hook(lambda opt, args, kwargs: lyc.mark_dirty())

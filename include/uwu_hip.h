@@ -390,6 +390,85 @@ int uwu_prodigy_finalize(double* scalars, const double* ws, int64_t nslots, doub
 int uwu_prodigy_apply(float* p, const float* exp_avg, const float* exp_avg_sq, void* p_bf16, int64_t n, const double* scalars,
                       double eps, double weight_decay, int decouple, void* stream);
 
+/* transformers.optimization.Adafactor (Shazeer & Stern, "Adafactor: Adaptive Learning Rates with Sublinear Memory Cost") on flat
+ * buffers.  The rule is per tensor: the flat buffer's tensors are described by a table, and a step is, per set of tensors whose
+ * gradient is complete, uwu_adafactor_stats, then uwu_adafactor_norm, then uwu_adafactor_apply on one stream: four kernel launches
+ * whatever the number of tensors, nothing read back, no atomics.  With g = g * pre_scale * clip[1] (clip may be NULL; the fp32
+ * factor of uwu_adamw_step), step t (1-based) and the host's doubles
+ *   beta2t = 1 - t^decay_rate ; lr_t = lr, or with relative_step min(warmup_init ? 1e-6 t : 1e-2, 1/sqrt(t))
+ * the package's step of one tensor W, seen as [R, C] = [shape[0], prod(shape[1:])] when it has two or more dimensions, is
+ *   U = g^2 + eps0
+ *   factored:    row[i] = beta2t row[i] + (1 - beta2t) mean_j U[i,j] ; col[j] = beta2t col[j] + (1 - beta2t) mean_i U[i,j]
+ *                u[i,j] = (rsqrt(row[i] / mean_i row[i]) * rsqrt(col[j])) * g[i,j]
+ *   unfactored:  v = beta2t v + (1 - beta2t) U ; u = rsqrt(v) * g
+ *   u /= max(1, RMS(u) / clip_threshold) ; u *= alpha      RMS(x) = ||x||_2 / sqrt(numel)
+ *                                                          alpha = lr_t * (scale_parameter ? max(eps1, RMS(W)) : 1)
+ *   beta1 given: m = beta1 m + (1 - beta1) u ; u = m
+ *   W -= weight_decay * alpha * W ; W -= u
+ * row * col is never formed (a tensor without gradient has both near eps0 = 1e-30: the product underflows fp32).
+ *
+ * Table: UWU_ADAFACTOR_FIELDS int64 per tensor, the same on the host (table_host) and on the device (table):
+ *   0 offset in the flat buffer (a multiple of 4 elements)    1 R (0: a 1-D tensor)    2 C (1-D: the length)
+ *   3 offset of row[R] in `row`    4 offset of col[C] in `col`    5 offset of v[C] in `v` (1-D only)
+ *   6 offset of uwu_adafactor_ws_floats(R, C) floats in `fws`     7 offset of uwu_adafactor_ws_doubles(R, C) doubles in `dws`
+ * Rows ascend: every range of row i + 1 (flat buffer, state, workspaces) starts at or behind the end of row i's.  R * C < 2^31.
+ * Launch list (launch_host, and the same words on the device: launch): 3 * nready + 2 int64 --
+ *   [0, nready)                 the tensors to update, as ascending table indices
+ *   [nready, 2 nready + 1)      prefix sums of uwu_adafactor_tiles(R, C) over them (workgroup starts; the total last)
+ *   [2 nready + 1, 3 nready + 2)  prefix sums of uwu_adafactor_moment_blocks(R, C) likewise
+ * Every entry point checks the listed rows on the host copies before it launches anything: ranges inside the buffers whose lengths
+ * the descriptor gives, offsets that are multiples of 4, R * C < 2^31, no overlap, consistent starts.  Nothing outside the listed
+ * tensors is read or written: the gaps between tensors (padding) are never touched.
+ * Determinism: workgroup b serves tile b - start[s] of the s-th listed tensor, the tiling and the order of every sum are functions
+ * of (R, C) alone, and per-tensor sums are double partials (one per workgroup) that each consumer adds in a fixed order: a
+ * tensor's result is bit-identical whichever launch it was part of. */
+#define UWU_ADAFACTOR_FIELDS 8
+typedef struct {
+  float* p;              /* the flat parameters, n elements, 16-byte aligned */
+  float* g;              /* their gradient, n elements, 16-byte aligned */
+  void* p_bf16;          /* the bf16 shadow of p (n elements, 8-byte aligned) or NULL */
+  float* row;            /* exp_avg_sq_row of all factored tensors, n_row floats */
+  float* col;            /* exp_avg_sq_col likewise, n_col floats */
+  float* v;              /* exp_avg_sq of all 1-D tensors, n_v floats */
+  float* m;              /* exp_avg (beta1), n elements laid out as p, 16-byte aligned; NULL without beta1 */
+  float* rms;            /* RMS(W) per tensor as of its last step with scale_parameter, ntensors floats */
+  float* fws;            /* workspace: tile partials of the row and column sums, n_fws floats */
+  double* dws;           /* workspace: per-workgroup partials of sum W^2, sum u^2 and sum row, n_dws doubles */
+  const int64_t* table_host;
+  const int64_t* table;  /* the device copy */
+  int32_t ntensors;
+  int64_t n, n_row, n_col, n_v, n_fws, n_dws;
+} UwuAdafactorDesc;
+
+/* Functions of the shape alone (R = 0: 1-D of length C): workgroups of the tile passes, workgroups of the moments pass (0 for a
+ * 1-D tensor), workspace floats and doubles.  0 for R < 0 or C < 1. */
+int64_t uwu_adafactor_tiles(int64_t R, int64_t C);
+int64_t uwu_adafactor_moment_blocks(int64_t R, int64_t C);
+int64_t uwu_adafactor_ws_floats(int64_t R, int64_t C);
+int64_t uwu_adafactor_ws_doubles(int64_t R, int64_t C);
+
+/* Pass 1, two launches.  Per tile: partial row and column sums of U = g^2 + eps0 into fws (1-D: v = fma(beta2t, v, (1-beta2t) U)
+ * directly) and, when scale_parameter, a partial of sum W^2 in double.  Then one thread per row and per column: the tile partials
+ * added in tile order, mean = sum / count, moment = fma(beta2t, moment, (1-beta2t) mean), and one double partial of sum_i row[i]
+ * per workgroup.  p and g are only read.  beta2t in [0, 1), eps0 >= 0.  8 B read per parameter with scale_parameter, else 4. */
+int uwu_adafactor_stats(const UwuAdafactorDesc* d, const int64_t* launch_host, const int64_t* launch, int nready, double beta2t,
+                        double eps0, int scale_parameter, float pre_scale, const float* clip, void* stream);
+
+/* Pass 2: per tile a double partial of sum u^2, u before the clip from the finished moments of the whole tensor and mean(row)
+ * (the partials of pass 1 in order).  g is only read.  4 B read per parameter. */
+int uwu_adafactor_norm(const UwuAdafactorDesc* d, const int64_t* launch_host, const int64_t* launch, int nready, float pre_scale,
+                       const float* clip, void* stream);
+
+/* Pass 3: u again (the same expression: the same bits), u = (u / max(1, RMS(u) / clip_threshold)) * alpha, with use_beta1
+ * m = fma(beta1, m, (1-beta1) u) and u = m, W = fma(-(weight_decay alpha), W, W) when that factor is not 0, W -= u; p_bf16
+ * refreshed as uwu_cast_f32_to_bf16 rounds, g zeroed when zero_grad, rms[tensor] = RMS(W) (before the update) when
+ * scale_parameter.  A NaN sum keeps its NaN through both max().  clip_threshold > 0, beta1 in [0, 1) (ignored without
+ * use_beta1), d->m given with use_beta1.  8 B read + 4 B written per parameter (+ 8 for m, + 2 for the shadow, + 4 for the zeroed
+ * gradient). */
+int uwu_adafactor_apply(const UwuAdafactorDesc* d, const int64_t* launch_host, const int64_t* launch, int nready, double lr_t,
+                        double eps1, double clip_threshold, int scale_parameter, int use_beta1, double beta1, double weight_decay,
+                        float pre_scale, const float* clip, int zero_grad, void* stream);
+
 /* Weight averaging on flat buffers (torch.optim.swa_utils.AveragedModel as lightning.pytorch.callbacks.WeightAveraging /
  * EMAWeightAveraging drive it; uwudiff_amd/averaging.py):
  *   avg[i] = fma(keep, avg[i], take * p[i])      fp32: two roundings per element, 8 B read and 4 B written per parameter

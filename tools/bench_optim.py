@@ -8,7 +8,11 @@ kernel of the same run.  One JSON line.  DESIGN.md sections 4.28, 4.36, 4.40 and
     python tools/bench_optim.py [--sizes 32966464,2570000000] [--reps 5] [--warmup 3]
 
 Bytes per parameter are derived from the update rule (reads + writes of p, g and the state, + 2 for the shadow, + 4 for the zeroed
-gradient); the times are device events around a window of launches, the kernels alternating inside every repetition."""
+gradient); the times are device events around a window of launches, the kernels alternating inside every repetition.
+
+Adafactor is per tensor, so it is timed on the real tensor tables of DiT-S/2 and of the SDXL-shape UNet (their flat
+registries, no weights needed): its three passes alone and the whole step, in the kohya setting (no parameter scale, no first
+moment), next to the AdamW kernel over the same buffer in the same run.  ``--only adafactor`` / ``--only flat`` runs one half."""
 import argparse
 import json
 import os
@@ -31,6 +35,74 @@ EXTRA = 2 + 4  # bf16 shadow written, consumed gradient zeroed
 PRODIGY = {"prodigy_stats": 24 + 12 + 4, "prodigy_finalize": 0, "prodigy_apply": 12 + 4 + 2}
 PRODIGY["prodigy_step"] = sum(PRODIGY.values())
 PRODIGY_STATE = 16  # exp_avg, exp_avg_sq, s, p0
+# Adafactor's passes in the kohya setting: g read; g read; g and p read, p written, + 2 for the shadow, + 4 for the zeroed gradient.
+# (The tile partials written by the first pass and read by its second launch are 1/64 of that and left out.)
+ADAFACTOR = {"adafactor_stats": 4, "adafactor_norm": 4, "adafactor_apply": 8 + 4 + 2 + 4}
+ADAFACTOR["adafactor_step"] = sum(ADAFACTOR.values())
+
+
+def adafactor_models():
+    """name -> the flat-buffer model whose registry is the tensor table (the UNet on the meta device: only its layout is used)"""
+    from uwudiff_amd.dit import DiT, DiTConfig
+    from uwudiff_amd.unet import SDXL_UNET_CONFIG, UNet2DConditionModel
+
+    return {"dit_s2": lambda: DiT(DiTConfig(depth=12, hidden=384, heads=6, patch=2, cond_dim=1280)),
+            "unet_sdxl": lambda: UNet2DConditionModel(SDXL_UNET_CONFIG, init_weights=False, device="meta")}
+
+
+def bench_adafactor(name, reps, warmup):
+    import torch
+
+    from uwudiff_amd import lib as L
+    from uwudiff_amd.optim import FusedAdafactor, adafactor_state_elems, flat_tensors
+
+    model = adafactor_models()[name]()
+    tensors, n = flat_tensors(model), model.flat.numel()
+    del model
+    dev = torch.device("cuda", 0)
+    p = torch.nn.Parameter(torch.empty(n, device=dev, dtype=torch.float32).normal_())
+    p.grad = torch.empty(n, device=dev, dtype=torch.float32).normal_().mul_(1e-3)
+    p._uwu_bf16_shadow = torch.empty(n, device=dev, dtype=torch.bfloat16)
+    opt = FusedAdafactor([p], lr=1e-6, relative_step=False, scale_parameter=False, warmup_init=False, tensors=tensors)
+    opt.step(zero_grad=False)  # allocates the state, the table and the workspaces; the moments are those of a real gradient
+    st, group = opt.state[p], opt.param_groups[0]
+    desc = opt.descriptor(p, st, L.ptr(p.data), L.ptr(p.grad), L.ptr(p._uwu_bf16_shadow))
+    ids = list(range(len(tensors)))
+    m, v = torch.zeros_like(p.data), torch.zeros_like(p.data)
+    s = L.stream()
+    calls = dict(opt.pass_calls(group, 2, desc, ids, 1.0, None, 1))
+    launch = {"adafactor_" + k[len("uwu_adafactor_"):]: (lambda k=k: L.call(k, *calls[k])) for k in calls}
+    launch["adafactor_step"] = lambda: [L.call(k, *a) for k, a in calls.items()]
+    launch["adamw"] = lambda: L.call("uwu_adamw_step", L.ptr(p.data), L.ptr(p.grad), L.ptr(m), L.ptr(v), L.ptr(p._uwu_bf16_shadow),
+                                     n, 1e-6, 0.9, 0.999, 1e-8, 0.01, 2, 1.0, None, 1, s)
+    iters = max(4, min(200, int(2e11 / (34 * n))))
+    for _ in range(warmup):
+        for fn in launch.values():
+            fn()
+    torch.cuda.synchronize()
+    ms = {k: [] for k in launch}
+    for _ in range(reps):
+        for k, fn in launch.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(iters):
+                fn()
+            e1.record()
+            e1.synchronize()
+            ms[k].append(e0.elapsed_time(e1) / iters)
+    out = {}
+    for k, times in ms.items():
+        times = sorted(times)
+        med = times[len(times) // 2]
+        bpp = ADAFACTOR[k] if k in ADAFACTOR else KERNELS["adamw"][0] + EXTRA
+        out[k] = {"ms": round(med, 4), "ms_min": round(times[0], 4), "ms_max": round(times[-1], 4), "bytes_per_param": bpp,
+                  "GBps": round(bpp * n / med / 1e6, 1)}
+    out["adafactor_step"]["ms_vs_adamw"] = round(out["adafactor_step"]["ms"] / out["adamw"]["ms"], 3)
+    if not torch.isfinite(p.detach()).all():
+        raise SystemExit("bench_optim.py: Adafactor left non-finite parameters")
+    elems = adafactor_state_elems(tensors)
+    return {"model": name, "n": n, "tensors": len(tensors), "launches_per_window": iters, "reps": reps, "kernels": out,
+            "state_bytes": 4 * sum(elems.values()), "workspace_bytes": 4 * opt._dev["fws"].numel() + 8 * opt._dev["dws"].numel()}
 
 
 def bench_size(n, reps, warmup):
@@ -139,12 +211,14 @@ def main():
     ap.add_argument("--sizes", default=f"{DIT_S2},{SDXL_UNET}")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--only", choices=["flat", "adafactor"], default=None, help="run one half of the tool")
     a = ap.parse_args()
     import torch
 
     if not torch.cuda.is_available():
         raise SystemExit("bench_optim.py measures on the GPU; there is no CPU path")
-    res = {"sizes": [bench_size(int(n), a.reps, a.warmup) for n in a.sizes.split(",")],
+    res = {"sizes": [bench_size(int(n), a.reps, a.warmup) for n in a.sizes.split(",")] if a.only != "adafactor" else [],
+           "adafactor": [bench_adafactor(m, a.reps, a.warmup) for m in adafactor_models()] if a.only != "flat" else [],
            "state_bytes_sdxl_unet": {**{name: int(state * SDXL_UNET) for name, (_, state) in KERNELS.items()},
                                      "prodigy": PRODIGY_STATE * SDXL_UNET},
            "weights_bytes_sdxl_unet": 4 * SDXL_UNET}
@@ -152,6 +226,12 @@ def main():
         for name, k in r["kernels"].items():
             print(f"n = {r['n']:>13,}  {name:<16} {k['ms']:9.4f} ms ({k['ms_min']:.4f} .. {k['ms_max']:.4f})  "
                   f"{k['bytes_per_param']} B/param  {k['GBps']:8.1f} GB/s ({k['GBps_min']:.1f} .. {k['GBps_max']:.1f})")
+    for r in res["adafactor"]:
+        for name, k in r["kernels"].items():
+            print(f"{r['model']:<9} n = {r['n']:>13,}  {name:<16} {k['ms']:9.4f} ms ({k['ms_min']:.4f} .. {k['ms_max']:.4f})  "
+                  f"{k['bytes_per_param']} B/param  {k['GBps']:8.1f} GB/s")
+        print(f"{r['model']:<9} {r['tensors']} tensors; Adafactor state {r['state_bytes'] / 1e6:.2f} MB, workspace "
+              f"{r['workspace_bytes'] / 1e6:.2f} MB; the step takes {r['kernels']['adafactor_step']['ms_vs_adamw']} of AdamW's time")
     for name, b in res["state_bytes_sdxl_unet"].items():
         print(f"SDXL-shape UNet optimizer state under {name:<11}: {b / 1e9:6.2f} GB (weights {4 * SDXL_UNET / 1e9:.2f} GB)")
     print(json.dumps(res))

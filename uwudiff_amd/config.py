@@ -32,6 +32,8 @@ ALIASES = {
     "bitsandbytes.optim.AdamW8bit": "uwudiff_amd.optim.FusedAdamW8bit",  # 8-bit block-wise moments
     "bitsandbytes.optim.Lion8bit": "uwudiff_amd.optim.FusedLion8bit",
     "schedulefree.AdamWScheduleFree": "uwudiff_amd.optim.FusedAdamWScheduleFree",  # eval-mode weights through fit
+    "transformers.optimization.Adafactor": "uwudiff_amd.optim.FusedAdafactor",  # factored second moments
+    "transformers.Adafactor": "uwudiff_amd.optim.FusedAdafactor",  # (torch.optim.Adafactor is a different rule: not aliased)
     "lightning.pytorch.callbacks.ModelCheckpoint": "uwudiff_amd.engine.ModelCheckpoint",
     "lightning.pytorch.callbacks.LearningRateMonitor": "uwudiff_amd.engine.LearningRateMonitor",
     "lightning.pytorch.callbacks.WeightAveraging": "uwudiff_amd.averaging.WeightAveraging",  # on the flat buffer

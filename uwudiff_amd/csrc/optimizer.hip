@@ -2,8 +2,9 @@
 // refresh, the weight average (update, exchange with the weights), dtype casts.  HBM-bound: AdamW moves 28 B/param, Lion and
 // AdamWFP16 20 B/param (+2 B/param for the bf16 shadow, +4 B/param for the zeroed gradient), the average's update 12 B/param.
 // Schedule-free AdamW (next to the weight average, whose exchange kernel it uses) moves AdamW's 28 B/param; its average 12 B/param.
-// Prodigy is in optimizer_prodigy.hip, the 8-bit block-wise AdamW / Lion in optimizer_8bit.hip; optimizer_shared.h holds the
-// traversal every kernel here runs on, the AdamW and Lion rules and the rounding contract all of them keep.
+// Prodigy is in optimizer_prodigy.hip, the 8-bit block-wise AdamW / Lion in optimizer_8bit.hip, Adafactor in
+// optimizer_adafactor.hip; optimizer_shared.h holds the traversal every kernel here runs on, the AdamW and Lion rules and the
+// rounding contract all of them keep.
 // Reference: src/duwu/trainer/trainer.py:52-74 (torch.optim.AdamW + Lightning gradient_clip_val),
 // src/duwu/trainer/optimizers.py (AdamWFP16), lion_pytorch.Lion (configs/demo_training*.yaml, commented alternative).
 #include "optimizer_shared.h"

@@ -29,20 +29,6 @@ __device__ __forceinline__ double prodigy_dlr(double d, double k, double lr, dou
   return d * lr * bc;
 }
 
-// fixed-order sum of one double per thread over a 256-thread workgroup (LDS tree: the same order on every run)
-__device__ __forceinline__ double block_sum_f64(double v, double* red) {
-  const int t = threadIdx.x;
-  __syncthreads();
-  red[t] = v;
-  __syncthreads();
-#pragma unroll
-  for (int s = 128; s > 0; s >>= 1) {
-    if (t < s) red[t] += red[t + s];
-    __syncthreads();
-  }
-  return red[0];
-}
-
 struct ProdigyCoef {
   double gscale, wd_coupled, b1, c1, b2, c2, b3, cs;
 };

@@ -1,5 +1,5 @@
-// What the flat-buffer optimizer kernels (optimizer.hip, optimizer_prodigy.hip, optimizer_8bit.hip) share: the one traversal,
-// the step shape on top of it, and the update rules that more than one file uses.
+// What the flat-buffer optimizer kernels (optimizer.hip, optimizer_prodigy.hip, optimizer_8bit.hip, optimizer_adafactor.hip) share:
+// the one traversal, the step shape on top of it, and the update rules and sums that more than one file uses.
 #pragma once
 #include "common.h"
 
@@ -27,6 +27,29 @@ __device__ __forceinline__ void for_each_group(int64_t n, int head, Vec vec, Ele
 // the fp32 factor every step multiplies the gradient by: the loss scale's inverse times the clip coefficient of the norm kernel
 __device__ __forceinline__ float grad_scale(float pre_scale, const float* __restrict__ clip) {
   return pre_scale * (clip ? clip[1] : 1.f);
+}
+
+// fixed-order sum of one double per thread over a 256-thread workgroup (LDS tree: the same order on every run)
+__device__ __forceinline__ double block_sum_f64(double v, double* red) {
+  const int t = threadIdx.x;
+  __syncthreads();
+  red[t] = v;
+  __syncthreads();
+#pragma unroll
+  for (int s = 128; s > 0; s >>= 1) {
+    if (t < s) red[t] += red[t + s];
+    __syncthreads();
+  }
+  return red[0];
+}
+
+// One element's write-back where the traversal is not flat_step's (the per-tensor tiles of optimizer_adafactor.hip): the parameter,
+// its bf16 shadow as flat_step's tail rounds it, and the consumed gradient.
+__device__ __forceinline__ void flat_write_back(float* __restrict__ p, bf16_t* __restrict__ pbf, float* __restrict__ g, int64_t i,
+                                                float pp, int zero_grad) {
+  p[i] = pp;
+  if (pbf) pbf[i] = (bf16_t)pp;
+  if (zero_grad) g[i] = 0.f;
 }
 
 // The common step: rule(p, g, s) updates one parameter and its NS fp32 state values from the raw gradient g (the rule scales it).

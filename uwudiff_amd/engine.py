@@ -125,6 +125,8 @@ class LearningRateMonitor:
 
     def extra(self, opt):
         out = {"d": float(opt.d)} if hasattr(opt, "d") else {}
+        if getattr(opt, "lr_t", None) is not None:  # Adafactor: the step size of the last step (with relative_step `lr` is None)
+            out["lr_t"] = float(opt.lr_t)
         if "scheduled_lr" in opt.param_groups[0]:  # schedule-free AdamW: `lr` times its own warm-up (a host float, no sync)
             out["scheduled_lr"] = float(opt.param_groups[0]["scheduled_lr"])
         return out

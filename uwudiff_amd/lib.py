@@ -42,6 +42,15 @@ class DitDesc(ctypes.Structure):
     )
 
 
+class AdafactorDesc(ctypes.Structure):
+    """UwuAdafactorDesc of include/uwu_hip.h"""
+    _fields_ = (
+        [(n, c_void_p) for n in ("p", "g", "p_bf16", "row", "col", "v", "m", "rms", "fws", "dws", "table_host", "table")]
+        + [("ntensors", c_int32)]
+        + [(n, c_int64) for n in ("n", "n_row", "n_col", "n_v", "n_fws", "n_dws")]
+    )
+
+
 P = c_void_p
 _SIGS = {
     "uwu_last_error": (c_char_p, []),
@@ -93,6 +102,13 @@ _SIGS = {
                                   c_float, P, c_int, P]),
     "uwu_prodigy_finalize": (c_int, [P, P, c_int64] + [c_double] * 7 + [c_int, P]),
     "uwu_prodigy_apply": (c_int, [P, P, P, P, c_int64, P, c_double, c_double, c_int, P]),
+    "uwu_adafactor_tiles": (c_int64, [c_int64, c_int64]),
+    "uwu_adafactor_moment_blocks": (c_int64, [c_int64, c_int64]),
+    "uwu_adafactor_ws_floats": (c_int64, [c_int64, c_int64]),
+    "uwu_adafactor_ws_doubles": (c_int64, [c_int64, c_int64]),
+    "uwu_adafactor_stats": (c_int, [P, P, P, c_int, c_double, c_double, c_int, c_float, P, P]),
+    "uwu_adafactor_norm": (c_int, [P, P, P, c_int, c_float, P, P]),
+    "uwu_adafactor_apply": (c_int, [P, P, P, c_int] + [c_double] * 3 + [c_int, c_int, c_double, c_double, c_float, P, c_int, P]),
     "uwu_ema_update": (c_int, [P, P, c_int64, c_float, c_float, P]),
     "uwu_ema_swap": (c_int, [P, P, P, c_int64, c_int, P]),
     "uwu_sfadamw_step": (c_int, [P, P, P, P, P, c_int64] + [c_double] * 7 + [c_float, P, c_int, P]),

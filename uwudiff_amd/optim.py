@@ -7,12 +7,16 @@ YAML, reference src/duwu/trainer/trainer.py:52-74, configs/demo_training_latent.
 size comes from two sums over all parameters kept on the device; ``FusedAdamW8bit`` / ``FusedLion8bit`` keep the moments as 8-bit
 codes with one scale per block of 256 elements (the state layout of ``bitsandbytes.optim.AdamW8bit`` / ``Lion8bit``);
 ``FusedAdamWScheduleFree`` is ``schedulefree.AdamWScheduleFree``, whose trained weights ``y`` are not the weights ``x`` to evaluate
-(its docstring states the rule; ``eval()`` / ``train()`` put one in place of the other).
+(its docstring states the rule; ``eval()`` / ``train()`` put one in place of the other); ``FusedAdafactor`` is
+``transformers.optimization.Adafactor``, whose rule is per tensor (row and column second moments): it walks a device table of the
+tensors the flat buffer holds.
 ``FlatFusedOptimizer`` is what they share and what
 the trainer's fused path asks for: Lightning's ``gradient_clip_val`` (global L2 norm, demo_training.yaml:12) as a device
 coefficient, one launch per flat parameter buffer (or per reduced chunk of it), the consumed gradient zeroed and the bf16
 shadow of the parameters (MFMA operands) refreshed by the same kernel.
 """
+import bisect
+import ctypes
 import math
 
 import torch
@@ -699,6 +703,257 @@ class FusedAdamWScheduleFree(FlatFusedOptimizer):
     def _nothing_held(self):
         """after ``load_state_dict``: whatever mode the state was saved in, no spare buffer holds a ``y`` of this optimizer"""
         self._held.clear()
+
+
+def flat_tensors(module):
+    """[(offset, shape), ...] of the tensors a flat-buffer module (``FlatModule``, ``LycorisNetwork``) keeps in ``flat``, with the
+    shapes as stored: what ``FusedAdafactor(tensors=)`` takes.  Host only: works on a meta-device module."""
+    layout = module.offsets if hasattr(module, "offsets") else module.P.registry
+    return [(int(off), tuple(int(d) for d in shape)) for off, shape in layout.values()]
+
+
+def adafactor_view(shape):
+    """(R, C) Adafactor sees a stored tensor as: ``[shape[0], prod(shape[1:])]`` with two or more dimensions, else (0, numel)"""
+    shape = tuple(int(d) for d in shape)
+    if len(shape) >= 2:
+        return shape[0], math.prod(shape[1:])
+    return 0, math.prod(shape)
+
+
+def adafactor_state_elems(tensors, beta1=False, n=None):
+    """fp32 state elements ``FusedAdafactor`` keeps for ``tensors`` = [(offset, shape), ...], by state key.  ``exp_avg`` (with
+    ``beta1``) is laid out as the parameters, so it has the flat buffer's ``n`` elements, padding included: give ``n``.  Pure
+    python: needs no GPU."""
+    views = [adafactor_view(shape) for _, shape in tensors]
+    out = {"exp_avg_sq_row": sum(r for r, c in views if r), "exp_avg_sq_col": sum(c for r, c in views if r),
+           "exp_avg_sq": sum(c for r, c in views if not r), "RMS": len(views)}
+    if beta1:
+        if n is None:
+            raise ValueError("adafactor_state_elems: exp_avg is as long as the flat buffer: give n")
+        out["exp_avg"] = int(n)
+    return out
+
+
+class TensorSchedule:
+    """Which tensors of a flat buffer may be updated, given the chunks handed over so far.  ``tensors`` = [(offset, numel), ...],
+    ascending and disjoint.  A tensor is given out once, by index, when the chunks seen cover all of it: chunks cut through
+    tensors, arrive in any order and may touch or overlap.  Pure python: needs no GPU."""
+
+    def __init__(self, tensors):
+        self.tensors = [(int(o), int(n)) for o, n in tensors]
+        if any(n <= 0 for _, n in self.tensors) or any(a[0] + a[1] > b[0] for a, b in zip(self.tensors, self.tensors[1:])):
+            raise ValueError("TensorSchedule: the tensors must be non-empty, ascending and disjoint")
+        self.starts = [o for o, _ in self.tensors]
+        self.covered = []  # disjoint element ranges [a, b) the chunks cover, sorted, touching ones merged
+        self.done = set()
+
+    def _touched(self, a, b):
+        """indices of the tensors that intersect [a, b)"""
+        i = bisect.bisect_right(self.starts, a) - 1
+        if i < 0 or self.tensors[i][0] + self.tensors[i][1] <= a:
+            i += 1
+        return range(i, bisect.bisect_left(self.starts, b))
+
+    def add(self, off, ln):
+        """chunk [off, off + ln) has arrived: the indices (ascending) of the tensors to launch now"""
+        a, b = int(off), int(off) + int(ln)
+        if not 0 <= a < b:
+            raise ValueError(f"chunk [{a}, {b}) is empty or starts below 0")
+        self.covered = BlockSchedule._merged(self.covered + [(a, b)])
+        x, y = next((x, y) for x, y in self.covered if x <= a and b <= y)  # the covered run the chunk now belongs to
+        out = [i for i in self._touched(x, y)
+               if i not in self.done and x <= self.tensors[i][0] and self.tensors[i][0] + self.tensors[i][1] <= y]
+        self.done.update(out)
+        return out
+
+    def pending(self):
+        """indices of the tensors that chunks have touched and that no ``add`` has given out: the partly covered ones"""
+        return sorted({i for x, y in self.covered for i in self._touched(x, y) if i not in self.done})
+
+
+class FusedAdafactor(FlatFusedOptimizer):
+    """``transformers.optimization.Adafactor`` (Shazeer & Stern, "Adafactor: Adaptive Learning Rates with Sublinear Memory Cost") on
+    a flat buffer: the second moment of a matrix is kept as one value per row and one per column instead of one per element.  The
+    rule is written out at ``uwu_adafactor_stats`` (include/uwu_hip.h); the signature and the two ``ValueError`` are the package's.
+    kohya-style trainers use ``relative_step=False, scale_parameter=False, warmup_init=False`` with a manual ``lr``.
+
+    **The unit "tensor".**  The rule is per tensor (row means, column means, a per-tensor RMS clip and parameter scale), and a tensor
+    here is an entry of ``tensors`` = [(offset, shape), ...]: the flat store's registry as stored (``flat_tensors(module)``; without
+    it the whole buffer is one 1-D tensor).  Anything of two or more dimensions is seen as ``[shape[0], prod(shape[1:])]``.  For the
+    Linears this is the package's unit.  It is NOT the package's unit for tensors that the store packs into one entry, for the 3x3
+    convolutions (stored ``(cout_store, 9 * cin_store)``: the package would factor the trailing 3 x 3 of the 4-D weight), and for
+    padded channels, which hold zero weight and zero gradient, take part in the means and stay exactly zero.  What the tests hold
+    the kernels to is the package's rule applied to the list of stored tensors in these 2-D views.
+
+    State under the package's keys, each one flat fp32 tensor: ``exp_avg_sq_row`` / ``exp_avg_sq_col`` over all factored tensors,
+    ``exp_avg_sq`` over the 1-D ones, ``exp_avg`` (as long as the parameters) only with ``beta1``, ``RMS`` one entry per tensor
+    (written when ``scale_parameter``), and ``step``.  Checkpoint interchange with the package is not claimed.
+
+    A step is three entry points (four kernel launches) per set of tensors that became ready, whatever their number: behind a
+    chunked gradient exchange a tensor is launched once the chunks seen cover all of it (``TensorSchedule``), and its result does
+    not depend on the launch it was part of, bit for bit.  Chunks that leave a touched tensor partly covered raise ``ValueError``
+    at the end of the step; by then the fully covered tensors have been updated and ``step`` has advanced (a half-applied step).  ``group["lr"]`` stays a float under the schedulers; with ``relative_step``
+    it is None and the step size is computed on the host from ``step`` (``lr_t``, logged by ``LearningRateMonitor``).  One flat
+    parameter buffer, one parameter group.  Not built: ``AdafactorSchedule``, the package's trailing-two-dims factoring of 4-D
+    tensors, 8-bit or bf16 ``exp_avg``, CAME, ``torch.optim.Adafactor`` (a different rule)."""
+
+    def __init__(self, params, lr=None, eps=(1e-30, 1e-3), clip_threshold=1.0, decay_rate=-0.8, beta1=None, weight_decay=0.0,
+                 scale_parameter=True, relative_step=True, warmup_init=False, tensors=None):
+        if lr is not None and relative_step:
+            raise ValueError("Cannot combine manual `lr` and `relative_step=True` options")
+        if warmup_init and not relative_step:
+            raise ValueError("`warmup_init=True` requires `relative_step=True`")
+        if lr is None and not relative_step:
+            raise ValueError("`relative_step=False` needs a manual `lr`")
+        if not clip_threshold > 0.0:
+            raise ValueError(f"Invalid clip_threshold value: {clip_threshold}")
+        if beta1 is not None and not 0.0 <= beta1 < 1.0:
+            raise ValueError(f"Invalid beta1 value: {beta1}")
+        super().__init__(params, dict(lr=lr, eps=tuple(eps), clip_threshold=clip_threshold, decay_rate=decay_rate, beta1=beta1,
+                                      weight_decay=weight_decay, scale_parameter=bool(scale_parameter),
+                                      relative_step=bool(relative_step), warmup_init=bool(warmup_init)))
+        ps = [p for g in self.param_groups for p in g["params"]]
+        if len(ps) != 1:
+            raise NotImplementedError("FusedAdafactor expects one flat parameter buffer")
+        n = ps[0].numel()
+        self.tensors = self.check_tensors(tensors if tensors is not None else [(0, (n,))], n)
+        self.lr_t = None  # the step size of the last step before the parameter scale (a host float)
+        self._dev = None  # the table, the workspaces and the tiling of every tensor, built at the first step
+        self._lists = {}  # tuple of tensor indices -> (host launch list, device copy)
+        self._sched = self._desc = None
+
+    @staticmethod
+    def check_tensors(tensors, n):
+        """``tensors`` sorted by offset as [(offset, (R, C)), ...] after the checks the entry points repeat on the table: inside the
+        buffer of ``n`` elements, offsets that are multiples of 4 elements, R * C < 2^31, no overlap.  Pure python."""
+        out = sorted((int(off), adafactor_view(shape)) for off, shape in tensors)
+        if not out:
+            raise ValueError("FusedAdafactor: tensors is empty")
+        end = 0
+        for off, (r, c) in out:
+            numel = r * c if r else c
+            if numel < 1 or numel >= 2 ** 31:
+                raise ValueError(f"FusedAdafactor: the tensor at {off} has {numel} elements (needs 1 <= R * C < 2^31)")
+            if off % 4:
+                raise ValueError(f"FusedAdafactor: the tensor at {off} is misaligned (offsets are multiples of 4 elements)")
+            if off < end:
+                raise ValueError(f"FusedAdafactor: the tensor at {off} overlaps its predecessor (or starts below 0)")
+            if off + numel > n:
+                raise ValueError(f"FusedAdafactor: the tensor [{off}, {off + numel}) is out of range of the buffer of {n} elements")
+            end = off + numel
+        return out
+
+    def step_size(self, group, step):
+        """``lr_t`` before the parameter scale: the package's ``_get_lr`` without ``max(eps[1], RMS)``.  A host float."""
+        if not group["relative_step"]:
+            return float(group["lr"])
+        return min(1e-6 * step if group["warmup_init"] else 1e-2, 1.0 / math.sqrt(step))
+
+    def _device_side(self, p):
+        """the table (host and device), the workspaces and the per-tensor workgroup counts; built once per device"""
+        if self._dev is not None and self._dev["device"] == p.device:
+            return self._dev
+        lib = L.load()
+        rows, tiles, mblocks = [], [], []
+        o_row = o_col = o_v = o_f = o_d = 0
+        for off, (r, c) in self.tensors:
+            rows.append([off, r, c, o_row, o_col, o_v, o_f, o_d])
+            if r:
+                o_row, o_col = o_row + r, o_col + c
+            else:
+                o_v += c
+            o_f += lib.uwu_adafactor_ws_floats(r, c)
+            o_d += lib.uwu_adafactor_ws_doubles(r, c)
+            tiles.append(lib.uwu_adafactor_tiles(r, c))
+            mblocks.append(lib.uwu_adafactor_moment_blocks(r, c))
+        host = torch.tensor(rows, dtype=torch.int64)
+        self._dev = dict(device=p.device, host=host, table=host.to(p.device), tiles=tiles, mblocks=mblocks,
+                         fws=torch.empty(max(o_f, 1), device=p.device, dtype=torch.float32),
+                         dws=torch.empty(max(o_d, 1), device=p.device, dtype=torch.float64))
+        self._lists = {}
+        return self._dev
+
+    def _init_state(self, p, st):
+        n = adafactor_state_elems([(off, (r, c) if r else (c,)) for off, (r, c) in self.tensors])
+        st["step"] = 0
+        for k in ("exp_avg_sq_row", "exp_avg_sq_col", "exp_avg_sq", "RMS"):  # (an empty tensor has no pointer: one spare element)
+            st[k] = _zeros_like(torch.empty(max(n[k], 1), device=p.device, dtype=torch.float32))
+        if self.param_groups[0]["beta1"] is not None:
+            st["exp_avg"] = _zeros_like(p.data)
+
+    def _launch_list(self, dev, ids):
+        key = tuple(ids)
+        hit = self._lists.get(key)
+        if hit is None:
+            if len(self._lists) >= 256:  # (a chunking that changes every step: do not keep every list it ever made)
+                self._lists = {}
+            t_start, m_start = [0], [0]
+            for i in ids:
+                t_start.append(t_start[-1] + dev["tiles"][i])
+                m_start.append(m_start[-1] + dev["mblocks"][i])
+            host = torch.tensor(list(ids) + t_start + m_start, dtype=torch.int64)
+            hit = self._lists[key] = (host, host.to(dev["device"]))
+        return hit
+
+    def descriptor(self, p, st, p_ptr, g_ptr, shadow_ptr):
+        """the ``UwuAdafactorDesc`` of parameter ``p`` with state ``st``: the buffers' BASE pointers and their lengths"""
+        dev = self._device_side(p)
+        if len(st["RMS"]) < len(self.tensors) or ("exp_avg" in st and st["exp_avg"].numel() != p.numel()):
+            raise ValueError("FusedAdafactor: the state does not fit the tensors (RMS or exp_avg has the wrong length)")
+        d = L.AdafactorDesc()
+        d.p, d.g, d.p_bf16 = p_ptr, g_ptr, shadow_ptr
+        d.row, d.col, d.v = L.ptr(st["exp_avg_sq_row"]), L.ptr(st["exp_avg_sq_col"]), L.ptr(st["exp_avg_sq"])
+        d.m, d.rms = L.ptr(st.get("exp_avg")), L.ptr(st["RMS"])
+        d.fws, d.dws = L.ptr(dev["fws"]), L.ptr(dev["dws"])
+        d.table_host, d.table, d.ntensors = dev["host"].data_ptr(), L.ptr(dev["table"]), len(self.tensors)
+        d.n, d.n_row, d.n_col, d.n_v = p.numel(), st["exp_avg_sq_row"].numel(), st["exp_avg_sq_col"].numel(), st["exp_avg_sq"].numel()
+        d.n_fws, d.n_dws = dev["fws"].numel(), dev["dws"].numel()
+        return d
+
+    def pass_calls(self, group, step, desc, ids, pre_scale, clip_ptr, zero_grad):
+        """[(entry point, arguments), ...]: the three passes over the tensors ``ids`` (ascending table indices) at ``step``"""
+        host, devlist = self._launch_list(self._dev, ids)
+        head = (ctypes.byref(desc), host.data_ptr(), L.ptr(devlist), len(ids))
+        beta2t = 1.0 - math.pow(step, group["decay_rate"])
+        self.lr_t = self.step_size(group, step)
+        sp, b1 = int(group["scale_parameter"]), group["beta1"]
+        return [("uwu_adafactor_stats", (*head, beta2t, float(group["eps"][0]), sp, pre_scale, clip_ptr, L.stream())),
+                ("uwu_adafactor_norm", (*head, pre_scale, clip_ptr, L.stream())),
+                ("uwu_adafactor_apply", (*head, self.lr_t, float(group["eps"][1]), float(group["clip_threshold"]), sp,
+                                         int(b1 is not None), float(b1 or 0.0), float(group["weight_decay"]), pre_scale, clip_ptr,
+                                         zero_grad, L.stream()))]
+
+    def _launch(self, group, st, p_ptr, g_ptr, shadow_ptr, off, ln, pre_scale, clip_ptr, zero_grad):
+        if self._sched is None:
+            self._sched = TensorSchedule([(o, r * c if r else c) for o, (r, c) in self.tensors])
+        ids = self._sched.add(off, ln)
+        if not ids:
+            return
+        if self._desc is None:  # (``_launch`` is handed the chunk's pointers)
+            p = next(q for q in group["params"] if self.state[q] is st)
+            self._desc = self.descriptor(p, st, p_ptr - 4 * off, g_ptr - 4 * off,
+                                         shadow_ptr - 2 * off if shadow_ptr is not None else None)
+        for name, args in self.pass_calls(group, int(st["step"]), self._desc, ids, pre_scale, clip_ptr, zero_grad):
+            L.call(name, *args)
+
+    def _finish(self, group, p, st, shadow):
+        # (raises after the launches: the tensors the chunks did cover are updated and ``step`` has advanced -- the step is then half
+        # applied, as with the 8-bit optimizers' partly covered blocks; the chunking is the caller's to repair)
+        sched, self._sched, self._desc = self._sched, None, None
+        left = sched.pending() if sched is not None else []
+        if left:
+            raise ValueError(f"FusedAdafactor: the chunks leave tensors partly covered (the tensors at offsets "
+                             f"{[self.tensors[i][0] for i in left]}); their gradient was consumed by no launch")
+
+    @torch.no_grad()
+    def step(self, *args, **kwargs):
+        self._sched = self._desc = None  # (a step that raised between its launches leaves no schedule behind)
+        for group in self.param_groups:  # the entry points take raw pointers: the shadow's dtype is checked here, before any launch
+            for p in group["params"]:
+                shadow = _shadow_of(p)
+                if shadow is not None and shadow.dtype != torch.bfloat16:
+                    raise L.UwuError(f"uwu_adafactor_apply: the shadow must be bfloat16, got {shadow.dtype}")
+        return super().step(*args, **kwargs)
 
 
 def cosine_lr(base_lr, step, T_max, eta_min):
